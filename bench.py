@@ -3,14 +3,27 @@
 bit-exact vs amvlib) on its configs[1].
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full  (everything below: gates, roofline, CPU path, other configs)
     python bench.py --gpus N --steps K --warmup W          (starts the N ranks itself, one child process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W     (--gpus must equal WORLD_SIZE)
 
+A plain run does what the headline needs and nothing else: it makes the inputs, makes the first call (whose statuses must
+be clean), warms up, times --steps steps, writes --dump-outputs if asked and prints the line (metric, value, unit,
+ms_per_step, ...).  --full adds everything else this file measures or checks: the gates against the CPU oracle and the
+second entropy kernel before timing, per-kernel times (HIP events inside the timed region) with the roofline, the CPU
+baseline, the other BASELINE configs (config.secondary) and, under ranks, the strong-scaling legs.
+
+--dump-outputs DIR: after the timed steps, what the last one handed its caller, as DIR/<name>.npy in float32 (float64 for
+offsets and indices), 64 MB at most: decode -- sampled frames' BGR rows and the frames' statuses; encode -- every chunk's
+offset and length and sampled chunks' bytes; adpcm -- sampled chunks and the PCM decoded from them; coresident -- both.
+The samples are a fixed seeded choice and the inputs are seeded, so two builds run with the same arguments can be
+compared file for file.
+
 Exit codes: 0 clean; 2 more GPUs asked for than visible; 3 a leg beside the headline hung (the line is written first);
 4 one raised a device / RCCL error, on this rank or on a peer (the line is written first).
 
-The line of a run with ranks is as complete as the single-GPU one: `cpu_baseline` (rank 0 runs the CPU path, the others wait
+The line of a run with ranks and --full is as complete as the single-GPU one: `cpu_baseline` (rank 0 runs the CPU path, the others wait
 in a barrier outside every timed region), configs[3] as stated (`strong10k_*`), and every other BASELINE config run by every
 rank on frames of its own -- rates summed over the ranks, times the slowest rank's -- with `rccl_ranks`, `run_status` and
 `strong10k_status` in front (CONFIG_HEAD_RANKS).
@@ -20,7 +33,7 @@ HBM when the timed region starts; results stay in HBM.  Frames shard by contiguo
 process per GPU, no collective inside the codec path ("scaling": "weak": every GPU works on its own
 --frames frames).  Synthetic sources are made on the device, outside the timed region, by the
 library's generator (+ encoder), both proven byte-identical to the CPU oracle by the tests and
-spot-checked again here before anything is timed.
+(--full) spot-checked again here before anything is timed.
 
   --workload decode      (default) --frames (160 000) chunks of WxH (160x120) -> BGR24 frames  configs[1], [3]
   --workload encode      RGB24 frames of WxH (320x240) -> chunks; the round trip through the
@@ -31,7 +44,7 @@ spot-checked again here before anything is timed.
   --workload amvlib      the drop-in surface, one frame per call: AmvReadNextFrame / AmvVideoDecode /
                          AmvAudioDecode from a C host over AMV files (PCIe inclusive; not the headline)
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (--full):
   roofline     the dominant kernel against the HBM roof: algorithmic bytes of the path per launch
                (video: chunk bytes + 3*W*H per frame; audio: chunk bytes + 2 per sample)
                / that kernel's mean duration measured with HIP events on the launch stream inside the
@@ -248,14 +261,15 @@ def make_video_stream(E, first, n, w, h, noise_every=0):
     return d_blob, pos, d_offs, d_lens, int(d_lens.sum().item())   # pos: the bytes of the blob the stream occupies
 
 
-def timed(E, step, steps, warmup, finish=None):
-    """finish: what a pipelined step loop still owes after its last step (inside the timed region)"""
+def timed(E, step, steps, warmup, finish=None, profile=True):
+    """finish: what a pipelined step loop still owes after its last step (inside the timed region); profile: the contexts
+    record every launch of the timed steps with HIP events (kernel_times reads them; --full)"""
     for _ in range(warmup):
         step()
     if finish:
         finish()
     torch.cuda.synchronize()
-    for c in [E.ctx] + getattr(E, "extra_ctx", []):
+    for c in ([E.ctx] + getattr(E, "extra_ctx", [])) if profile else []:
         c.prof_enable(True)
         c.prof_reset()
     if E.world > 1:
@@ -270,9 +284,47 @@ def timed(E, step, steps, warmup, finish=None):
     if E.world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    for c in [E.ctx] + getattr(E, "extra_ctx", []):
+    for c in ([E.ctx] + getattr(E, "extra_ctx", [])) if profile else []:
         c.prof_enable(False)
     return E.sh.max_over_ranks(elapsed, E.dev)
+
+
+DUMP_BYTES = 64 * 1000 * 1000   # --dump-outputs: what the files of one run hold at most, together
+
+
+def sample_rows(n, row_bytes, budget):
+    """--dump-outputs: the rows (frames, chunks) of an output of n rows whose float32 copies fit in `budget` bytes -- all
+    of them when they fit, else a fixed seeded choice, sorted"""
+    k = max(1, min(n, int(budget // (4 * max(row_bytes, 1)))))
+    if k == n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(SEED).choice(n, k, replace=False))
+
+
+def frames_for_dump(prefix, d_out, d_st, w, h, budget):
+    """a decode's output as its caller gets it: the BGR rows (w*3 bytes of each stride) of sampled frames, and every
+    frame's status -- only the sampled frames' (frame_index) when the batch has more than a million frames"""
+    n = int(d_st.numel())
+    idx = sample_rows(n, h * w * 3 + 2, budget - 4e6)                # + 2: the index's 8 bytes per frame
+    pick = torch.from_numpy(idx).to(d_out.device)
+    return {prefix + "frames": d_out[pick, :, : w * 3].cpu().numpy().astype(np.float32),
+            prefix + "frame_index": idx.astype(np.float64),
+            prefix + "status": (d_st if 4 * n <= 4e6 else d_st[pick]).cpu().numpy().astype(np.float32)}
+
+
+def dump_outputs(E, args, make):
+    """--dump-outputs DIR: make() -> {name: numpy array, already float32 / float64}, written as DIR/<name>.npy by rank 0;
+    without the option nothing is made"""
+    if not args.dump_outputs or E.rank != 0:
+        return
+    arrays = make()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_BYTES))
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
 
 def kernel_times(E, ids, ctx=None, steps=1):
@@ -372,12 +424,12 @@ def cpu_cores():
 def cpu_leg(E, args):
     """does THIS rank run the CPU path beside the line?  Rank 0 does, whatever the world size: the host's cores are one
     resource, the figure is per host, and the other ranks wait for it in cpu_leg_done()'s barrier -- outside every timed
-    region (timed() brackets its own with barriers)"""
-    return E.rank == 0 and not args.no_cpu_baseline
+    region (timed() brackets its own with barriers).  Only under --full."""
+    return args.full and E.rank == 0 and not args.no_cpu_baseline
 
 
 def cpu_leg_done(E, args):
-    if E.world > 1 and not args.no_cpu_baseline:
+    if E.world > 1 and args.full and not args.no_cpu_baseline:
         dist.barrier()
 
 
@@ -413,39 +465,10 @@ def roofline(kern, algo_bytes, elapsed_per_step, traffic, extra=None):
 
 
 # ---------------------------------------------------------------------------------------------
-def run_decode(E, args):
+def decode_gate(E, orc, kind, first, n, w, h, d_blob, cap, d_offs, d_lens, d_out, amv_chunks):
+    """--full: the batch the first call decoded, checked before anything is timed -- sample frames against the CPU oracle
+    (checker only), their chunks against the oracle's encoder or the clip -> the chunk offsets and lengths on the host"""
     ctx, pkg, dev, stream = E.ctx, E.pkg, E.dev, E.stream
-    w, h, n = args.width or 160, args.height or 120, args.frames or DECODE_FRAMES
-    first = E.rank * n
-    kind = getattr(args, "stream", "synthetic") or "synthetic"
-    orc = entry.load_oracle()
-    if kind == "amv1":
-        # the reference's own clip (C-AMVDecoder/bin/AMV1.amv, 128x96, 252 frames, chunks of 1 410 - 2 924 bytes), its chunks
-        # laid out back to back over and over until there are n of them: a real clip's spread of chunk sizes, device-resident
-        info, amv_chunks, _ = orc.parse_amv(open(os.path.join(ROOT, "tests", "golden", "AMV1.amv"), "rb").read())
-        w, h = info["width"], info["height"]
-        once = np.frombuffer(b"".join(c + b"\0" * (-len(c) % 4) for c in amv_chunks), np.uint8)
-        lens1 = np.array([len(c) for c in amv_chunks], np.int64)
-        offs1 = np.concatenate([[0], np.cumsum((lens1 + 3) & ~3)[:-1]])
-        reps = (n + len(lens1) - 1) // len(lens1)
-        d_blob = torch.from_numpy(once.copy()).to(dev).repeat(reps)
-        cap = int(d_blob.numel())
-        d_offs = (torch.from_numpy(offs1).to(dev)[None, :] + torch.arange(reps, device=dev)[:, None] * once.size).reshape(-1)[:n].contiguous()
-        d_lens = torch.from_numpy(lens1.astype(np.int32)).to(dev).repeat(reps)[:n].contiguous()
-        stream_bytes = int(d_lens.sum().item())
-    else:
-        d_blob, cap, d_offs, d_lens, stream_bytes = make_video_stream(E, first, n, w, h, 16 if kind == "mixed" else 0)
-    d_out = torch.empty((n, h, ctx.stride(w)), dtype=torch.uint8, device=dev)
-    d_st = torch.empty(n, dtype=torch.int32, device=dev)
-
-    def step():
-        ctx.decode_batch_dev(d_blob, cap, d_offs, d_lens, n, w, h, 0, d_out, d_st, stream)
-
-    # correctness gate before any timing: sample frames against the CPU oracle (checker only)
-    step()
-    torch.cuda.synchronize()
-    if int((d_st != 0).sum().item()) != 0:
-        raise SystemExit("decode reported errors on the synthetic stream")
     offs_h, lens_h = d_offs.cpu().numpy(), d_lens.cpu().numpy()
     for i in sorted({0, 1, 15, n // 2, n - 1} & set(range(n))):
         ch = d_blob[int(offs_h[i]):int(offs_h[i]) + int(lens_h[i])].cpu().numpy().tobytes()
@@ -475,20 +498,62 @@ def run_decode(E, args):
     if not same:
         raise SystemExit("the batch decodes differently through the serial entropy kernel")
     del d_ref, d_st2
+    return offs_h, lens_h
+
+
+def run_decode(E, args):
+    ctx, pkg, dev, stream = E.ctx, E.pkg, E.dev, E.stream
+    w, h, n = args.width or 160, args.height or 120, args.frames or DECODE_FRAMES
+    first = E.rank * n
+    kind = getattr(args, "stream", "synthetic") or "synthetic"
+    orc = entry.load_oracle()
+    if kind == "amv1":
+        # the reference's own clip (C-AMVDecoder/bin/AMV1.amv, 128x96, 252 frames, chunks of 1 410 - 2 924 bytes), its chunks
+        # laid out back to back over and over until there are n of them: a real clip's spread of chunk sizes, device-resident
+        info, amv_chunks, _ = orc.parse_amv(open(os.path.join(ROOT, "tests", "golden", "AMV1.amv"), "rb").read())
+        w, h = info["width"], info["height"]
+        once = np.frombuffer(b"".join(c + b"\0" * (-len(c) % 4) for c in amv_chunks), np.uint8)
+        lens1 = np.array([len(c) for c in amv_chunks], np.int64)
+        offs1 = np.concatenate([[0], np.cumsum((lens1 + 3) & ~3)[:-1]])
+        reps = (n + len(lens1) - 1) // len(lens1)
+        d_blob = torch.from_numpy(once.copy()).to(dev).repeat(reps)
+        cap = int(d_blob.numel())
+        d_offs = (torch.from_numpy(offs1).to(dev)[None, :] + torch.arange(reps, device=dev)[:, None] * once.size).reshape(-1)[:n].contiguous()
+        d_lens = torch.from_numpy(lens1.astype(np.int32)).to(dev).repeat(reps)[:n].contiguous()
+        stream_bytes = int(d_lens.sum().item())
+    else:
+        d_blob, cap, d_offs, d_lens, stream_bytes = make_video_stream(E, first, n, w, h, 16 if kind == "mixed" else 0)
+    d_out = torch.empty((n, h, ctx.stride(w)), dtype=torch.uint8, device=dev)
+    d_st = torch.empty(n, dtype=torch.int32, device=dev)
+
+    def step():
+        ctx.decode_batch_dev(d_blob, cap, d_offs, d_lens, n, w, h, 0, d_out, d_st, stream)
+
+    # the first call, outside the timed region, and the statuses it returned
+    step()
+    torch.cuda.synchronize()
+    if int((d_st != 0).sum().item()) != 0:
+        raise SystemExit("decode reported errors on the synthetic stream")
+    if args.full:
+        offs_h, lens_h = decode_gate(E, orc, kind, first, n, w, h, d_blob, cap, d_offs, d_lens, d_out,
+                                     amv_chunks if kind == "amv1" else None)
 
     ids = (pkg.K_UNSTUFF, pkg.K_HUFFMAN, pkg.K_HUFFMAN_SERIAL, pkg.K_RECON)
-    one_call = None
+    one_call = kern = None
     if not args.pipelined:
-        elapsed = timed(E, step, args.steps, args.warmup)
-        kern = kernel_times(E, ids, steps=args.steps)
+        elapsed = timed(E, step, args.steps, args.warmup, profile=args.full)
+        dump_outputs(E, args, lambda: frames_for_dump("decode_", d_out, d_st, w, h, DUMP_BYTES))
+        if args.full:
+            kern = kernel_times(E, ids, steps=args.steps)
     else:
         # The step loop of a caller with the next batch in hand (a player or transcoder going through windows of frames):
         # batch k + 1 is submitted before batch k is collected, so its entropy stage runs beside batch k's reconstruction.
         # Every batch is decoded in full into buffers of its own (two sets, used in turn); K steps = K batches, the
         # pipeline's fill and drain are inside the timed region.
-        few = max(3, args.steps // 4)
-        t1 = timed(E, step, few, 1)                    # for comparison: the one-call form, a batch at a time
-        one_call = {"ms_per_step": 1e3 * t1 / few, "steps": few, "kernels": kernel_times(E, ids, steps=few)}
+        if args.full:
+            few = max(3, args.steps // 4)
+            t1 = timed(E, step, few, 1)                    # for comparison: the one-call form, a batch at a time
+            one_call = {"ms_per_step": 1e3 * t1 / few, "steps": few, "kernels": kernel_times(E, ids, steps=few)}
         outs = [(d_out, d_st), (torch.empty_like(d_out), torch.empty_like(d_st))]
         fly = {"k": 0, "open": 0}
 
@@ -508,52 +573,57 @@ def run_decode(E, args):
         for o, s in outs:
             o.fill_(0x5A)
             s.fill_(-1)
-        elapsed = timed(E, step_pipelined, args.steps, args.warmup, finish)
-        kern = kernel_times(E, ids, steps=args.steps)
-        # both buffer sets hold the batch, bit for bit what the one-call form (checked against the oracle above) wrote
-        if int((outs[1][1] != 0).sum().item()) or int((outs[0][1] != 0).sum().item()) or not torch.equal(outs[0][0], outs[1][0]):
-            raise SystemExit("pipelined decode: the two buffer sets differ")
-        step()
-        torch.cuda.synchronize()
-        if not torch.equal(d_out, outs[1][0]):
-            raise SystemExit("pipelined decode differs from the one-call form")
+        elapsed = timed(E, step_pipelined, args.steps, args.warmup, finish, profile=args.full)
+        dump_outputs(E, args, lambda: frames_for_dump("decode_", *outs[(fly["k"] - 1) & 1], w, h, DUMP_BYTES))
+        if args.full:
+            kern = kernel_times(E, ids, steps=args.steps)
+            # both buffer sets hold the batch, bit for bit what the one-call form (checked against the oracle above) wrote
+            if int((outs[1][1] != 0).sum().item()) or int((outs[0][1] != 0).sum().item()) or not torch.equal(outs[0][0], outs[1][0]):
+                raise SystemExit("pipelined decode: the two buffer sets differ")
+            step()
+            torch.cuda.synchronize()
+            if not torch.equal(d_out, outs[1][0]):
+                raise SystemExit("pipelined decode differs from the one-call form")
         del outs
-    workspace = ctx.decode_workspace_per_frame()     # device bytes the context holds per frame of this batch
-    ctx.entropy_stats(True)          # one extra, untimed step: how many synchronisation rounds the frames needed
-    step()
-    sync = ctx.entropy_stats(False)
 
     result = base_result(E, args, "AMV frames/sec/GPU (%dx%d decode, bit-exact)" % (w, h), "frames/s", n, elapsed)
     result["config"] = {"workload": "%dx%d AMV decode, %d-frame %s stream per GPU, chunks resident in HBM"
                                     % (w, h, n, {"synthetic": "synthetic", "mixed": "mixed (synthetic + noise)", "amv1": "AMV1.amv looped"}[kind]),
                         "frames_per_gpu": n, "mean_chunk_bytes": stream_bytes / n, "parallelism": "frame-range x%d" % E.world,
-                        "per_gpu_frames_per_s": result["value"] / E.world,
-                        "gate": "every frame == a second decode through the serial entropy kernel (device compare); frames 0, 1, "
-                                "n/2, n-1 == the CPU oracle; their chunks == the oracle's encoder"}
-    result["config"]["decode_workspace_bytes_per_frame"] = workspace
-    result["config"]["handed_to_serial"] = int(sync["handed_to_serial"])   # frames of the batch the parallel entropy kernels gave up on
+                        "per_gpu_frames_per_s": result["value"] / E.world}
     result["config"]["stream"] = {"synthetic": "seeded synthetic source (BASELINE.md section 4), every frame",
                                   "mixed": "the synthetic source with every 16th frame replaced by white noise: chunk sizes from %d to %d bytes"
                                            % (int(d_lens.min().item()), int(d_lens.max().item())),
                                   "amv1": "the reference's clip AMV1.amv (128x96, 252 frames, chunks of %d - %d bytes) repeated"
                                           % (int(d_lens.min().item()), int(d_lens.max().item()))}[kind]
-    if one_call:
+    if args.pipelined:
         result["config"]["calls"] = ("amvhip_decode_submit_dev / _collect_dev, batch k+1 submitted before batch k is collected "
                                      "(entropy stage of one batch beside the reconstruction of the one before), two sets of output buffers")
-        result["config"]["one_call_form"] = one_call   # amvhip_decode_batch_dev, one batch at a time, same stream
-    result["roofline"] = roofline(
-        kern, stream_bytes + n * 3 * w * h, elapsed / args.steps,
-        (lambda dom: profiled_traffic("", dom)) if (w, h, n) == (160, 120, DECODE_FRAMES) else
-        ((lambda dom: profiled_traffic("_decode320", dom)) if (w, h, n) == (320, 240, 128000) else None),
-        {"entropy_sync_rounds": {"mean": sync["rounds"] / max(sync["frames"], 1), "max": sync["max_rounds"]}})
+    if args.full:
+        workspace = ctx.decode_workspace_per_frame()     # device bytes the context holds per frame of this batch
+        ctx.entropy_stats(True)          # one extra, untimed step: how many synchronisation rounds the frames needed
+        step()
+        sync = ctx.entropy_stats(False)
+        result["config"]["gate"] = ("every frame == a second decode through the serial entropy kernel (device compare); frames 0, 1, "
+                                    "n/2, n-1 == the CPU oracle; their chunks == the oracle's encoder")
+        result["config"]["decode_workspace_bytes_per_frame"] = workspace
+        result["config"]["handed_to_serial"] = int(sync["handed_to_serial"])   # frames of the batch the parallel entropy kernels gave up on
+        if one_call:
+            result["config"]["one_call_form"] = one_call   # amvhip_decode_batch_dev, one batch at a time, same stream
+        result["roofline"] = roofline(
+            kern, stream_bytes + n * 3 * w * h, elapsed / args.steps,
+            (lambda dom: profiled_traffic("", dom)) if (w, h, n) == (160, 120, DECODE_FRAMES) else
+            ((lambda dom: profiled_traffic("_decode320", dom)) if (w, h, n) == (320, 240, 128000) else None),
+            {"entropy_sync_rounds": {"mean": sync["rounds"] / max(sync["frames"], 1), "max": sync["max_rounds"]}})
 
-    if (w, h, n) == (160, 120, DECODE_FRAMES):
-        pt = profiled_path_traffic("", ("amv_unstuff_kernel", "amv_huffman_fast_kernel", "amv_reconstruct_kernel"))
-        if pt:
-            result["roofline"]["path_traffic"] = pt            # all three decode kernels, counter bytes per step
-            result["config"]["decode_traffic_ratio"] = pt / (stream_bytes + n * 3 * w * h)
+        if (w, h, n) == (160, 120, DECODE_FRAMES):
+            pt = profiled_path_traffic("", ("amv_unstuff_kernel", "amv_huffman_fast_kernel", "amv_reconstruct_kernel"))
+            if pt:
+                result["roofline"]["path_traffic"] = pt            # all three decode kernels, counter bytes per step
+                result["config"]["decode_traffic_ratio"] = pt / (stream_bytes + n * 3 * w * h)
 
-    if E.dist and getattr(args, "strong_leg", True):   # config 4 as BASELINE.json states it, beside the weak-scaling line above
+    # config 4 as BASELINE.json states it, beside the weak-scaling line above: under ranks with --full, or asked for (--strong)
+    if E.dist and getattr(args, "strong_leg", True) and (args.full or args.strong):
         result["config"]["scaling_modes"] = {"weak": "value / ms_per_step of this line: every GPU decodes its own %d frames" % n,
                                              "strong": "config4_strong_10k (flat: strong10k_*)"}
         guarded_strong(E, result, lambda: run_strong(E, args, w, h))
@@ -760,30 +830,10 @@ def run_strong(E, args, w, h, n_total=10000, share=None):
 
 
 # ---------------------------------------------------------------------------------------------
-def run_encode(E, args):
-    ctx, pkg, dev, stream = E.ctx, E.pkg, E.dev, E.stream
-    w, h, n = args.width or 320, args.height or 240, args.frames or 8000
-    if args.psnr_floor is None:
-        args.psnr_floor = 26.6 if (w, h) == (320, 240) else 25.4
-    first = E.rank * n
-    d_rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
-    ctx.synth_frames_dev(SEED, first, n, w, h, d_rgb, stream)
-    cap = max(1 << 20, n * w * h)
-    d_blob = torch.zeros(cap, dtype=torch.uint8, device=dev)
-    d_offs = torch.zeros(n, dtype=torch.int64, device=dev)
-    d_lens = torch.zeros(n, dtype=torch.int32, device=dev)
-
-    def step():
-        ctx.encode_batch_dev(d_rgb, w * 3, 0, n, w, h, pkg.QBIAS_AMV, d_blob, cap, d_offs, d_lens, stream)
-
-    # gate: chunks byte-identical to the oracle's encoder on sample frames; whole batch round-trips through
-    # the bit-exact decoder with PSNR against the source above the stated floor
-    step()
-    torch.cuda.synchronize()
-    stream_bytes = int(d_lens.sum().item())
-    if int(d_offs[-1].item()) + int(d_lens[-1].item()) > cap:
-        raise SystemExit("encoded stream overflowed its buffer")
-    orc = entry.load_oracle()
+def encode_gate(E, args, orc, first, n, w, h, d_rgb, d_blob, cap, d_offs, d_lens):
+    """--full: chunks byte-identical to the oracle's encoder on sample frames; whole batch round-trips through the
+    bit-exact decoder with PSNR against the source above the stated floor -> (PSNR of the batch, of frame 0 by the CPU)"""
+    ctx, dev, stream = E.ctx, E.dev, E.stream
     offs_h, lens_h = d_offs.cpu().numpy(), d_lens.cpu().numpy()
     for i in sorted({0, 1, n // 2, n - 1}):
         ch = d_blob[int(offs_h[i]):int(offs_h[i]) + int(lens_h[i])].cpu().numpy().tobytes()
@@ -803,17 +853,58 @@ def run_encode(E, args):
     one = orc.psnr(d_out[0, :, : w * 3].reshape(h, w, 3).flip(-1).cpu().numpy(), d_rgb[0].cpu().numpy())
     if psnr < args.psnr_floor:
         raise SystemExit("round-trip PSNR %.2f dB is below the %.1f dB floor" % (psnr, args.psnr_floor))
+    return psnr, one
 
-    elapsed = timed(E, step, args.steps, args.warmup)
-    kern = kernel_times(E, (pkg.K_FDCT, pkg.K_PACK, pkg.K_PACK_SERIAL, pkg.K_COMPACT), steps=args.steps)
+
+def chunks_for_dump(prefix, d_blob, d_offs, d_lens, budget):
+    """an encode's output as its caller gets it: every chunk's offset and length, and the bytes of sampled chunks laid end
+    to end (chunk_index says which)"""
+    offs, lens = d_offs.cpu().numpy(), d_lens.cpu().numpy()
+    idx = sample_rows(len(lens), int(lens.max()) + 2, budget - 12 * len(lens) - 4e6)
+    blob = d_blob[: int((offs + lens).max())].cpu().numpy()
+    return {prefix + "offsets": offs.astype(np.float64), prefix + "lengths": lens.astype(np.float32),
+            prefix + "chunk_index": idx.astype(np.float64),
+            prefix + "chunk_bytes": np.concatenate([blob[int(offs[i]):int(offs[i]) + int(lens[i])] for i in idx]).astype(np.float32)}
+
+
+def run_encode(E, args):
+    ctx, pkg, dev, stream = E.ctx, E.pkg, E.dev, E.stream
+    w, h, n = args.width or 320, args.height or 240, args.frames or 8000
+    if args.psnr_floor is None:
+        args.psnr_floor = 26.6 if (w, h) == (320, 240) else 25.4
+    first = E.rank * n
+    d_rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=dev)
+    ctx.synth_frames_dev(SEED, first, n, w, h, d_rgb, stream)
+    cap = max(1 << 20, n * w * h)
+    d_blob = torch.zeros(cap, dtype=torch.uint8, device=dev)
+    d_offs = torch.zeros(n, dtype=torch.int64, device=dev)
+    d_lens = torch.zeros(n, dtype=torch.int32, device=dev)
+
+    def step():
+        ctx.encode_batch_dev(d_rgb, w * 3, 0, n, w, h, pkg.QBIAS_AMV, d_blob, cap, d_offs, d_lens, stream)
+
+    # the first call, outside the timed region
+    step()
+    torch.cuda.synchronize()
+    stream_bytes = int(d_lens.sum().item())
+    if int(d_offs[-1].item()) + int(d_lens[-1].item()) > cap:
+        raise SystemExit("encoded stream overflowed its buffer")
+    orc = entry.load_oracle()
+    if args.full:
+        psnr, one = encode_gate(E, args, orc, first, n, w, h, d_rgb, d_blob, cap, d_offs, d_lens)
+
+    elapsed = timed(E, step, args.steps, args.warmup, profile=args.full)
+    dump_outputs(E, args, lambda: chunks_for_dump("encode_", d_blob, d_offs, d_lens, DUMP_BYTES))
     result = base_result(E, args, "AMV frames/sec/GPU (%dx%d encode, PSNR-checked round trip)" % (w, h), "frames/s", n, elapsed)
     result["config"] = {"workload": "%dx%d AMV encode (rgb24 -> yuvj420p, fdct, quantise, Huffman), %d synthetic frames per GPU "
                                     "resident in HBM" % (w, h, n),
-                        "frames_per_gpu": n, "mean_chunk_bytes": stream_bytes / n, "parallelism": "frame-range x%d" % E.world,
-                        "round_trip_psnr_db": psnr, "psnr_floor_db": args.psnr_floor, "frame0_psnr_db_cpu_checker": one,
-                        "bit_exact_vs_cpu_encoder": True}
-    result["roofline"] = roofline(kern, stream_bytes + n * 3 * w * h, elapsed / args.steps,
-                                  (lambda dom: profiled_traffic("_encode", dom)) if (w, h, n) == (320, 240, 8000) else None)
+                        "frames_per_gpu": n, "mean_chunk_bytes": stream_bytes / n, "parallelism": "frame-range x%d" % E.world}
+    if args.full:
+        kern = kernel_times(E, (pkg.K_FDCT, pkg.K_PACK, pkg.K_PACK_SERIAL, pkg.K_COMPACT), steps=args.steps)
+        result["config"].update({"round_trip_psnr_db": psnr, "psnr_floor_db": args.psnr_floor, "frame0_psnr_db_cpu_checker": one,
+                                 "bit_exact_vs_cpu_encoder": True})
+        result["roofline"] = roofline(kern, stream_bytes + n * 3 * w * h, elapsed / args.steps,
+                                      (lambda dom: profiled_traffic("_encode", dom)) if (w, h, n) == (320, 240, 8000) else None)
 
     if cpu_leg(E, args):
         import concurrent.futures
@@ -919,46 +1010,65 @@ def run_adpcm(E, args, with_video=False):
             ctx.decode_batch_dev(d_blob, cap, d_voffs, d_vlens, n, w, h, 0, d_out, d_st, stream)
         audio()
 
+    # the first call, outside the timed region (with --full: checked against the oracle and the exhaustive ADPCM route)
     step()
     torch.cuda.synchronize()
-    orc = audio_gate(E, A, na)
-    got = d_pcm2[: spf * min(na, 64)].cpu().numpy()
-    chunks_h = d_chunks[: clen * min(na, 64)].cpu().numpy()
-    for i in range(min(na, 64)):
-        want, _ = orc.adpcm_decode_chunk(chunks_h[i * clen:(i + 1) * clen])
-        if not (got[i * spf:(i + 1) * spf] == want[:spf]).all():
-            raise SystemExit("HIP ADPCM decode differs from the oracle at chunk %d" % i)
-    if with_video:
-        if int((d_st != 0).sum().item()) != 0:
-            raise SystemExit("decode reported errors on the synthetic stream")
-        offs_h, lens_h = d_voffs.cpu().numpy(), d_vlens.cpu().numpy()
-        for i in sorted({0, n - 1}):
-            ch = d_blob[int(offs_h[i]):int(offs_h[i]) + int(lens_h[i])].cpu().numpy().tobytes()
-            want, st, _ = orc.decode_frame(ch, w, h)
-            if st != 0 or not (d_out[i].cpu().numpy() == want).all():
-                raise SystemExit("HIP decode differs from the oracle at frame %d" % (first + i))
+    if with_video and int((d_st != 0).sum().item()) != 0:
+        raise SystemExit("decode reported errors on the synthetic stream")
+    if args.full:
+        orc = audio_gate(E, A, na)
+        got = d_pcm2[: spf * min(na, 64)].cpu().numpy()
+        chunks_h = d_chunks[: clen * min(na, 64)].cpu().numpy()
+        for i in range(min(na, 64)):
+            want, _ = orc.adpcm_decode_chunk(chunks_h[i * clen:(i + 1) * clen])
+            if not (got[i * spf:(i + 1) * spf] == want[:spf]).all():
+                raise SystemExit("HIP ADPCM decode differs from the oracle at chunk %d" % i)
+        if with_video:
+            offs_h, lens_h = d_voffs.cpu().numpy(), d_vlens.cpu().numpy()
+            for i in sorted({0, n - 1}):
+                ch = d_blob[int(offs_h[i]):int(offs_h[i]) + int(lens_h[i])].cpu().numpy().tobytes()
+                want, st, _ = orc.decode_frame(ch, w, h)
+                if st != 0 or not (d_out[i].cpu().numpy() == want).all():
+                    raise SystemExit("HIP decode differs from the oracle at frame %d" % (first + i))
 
-    elapsed = timed(E, step, args.steps, args.warmup)
+    elapsed = timed(E, step, args.steps, args.warmup, profile=args.full)
+
+    def outputs():
+        # the audio's two outputs, chunk by chunk: the ADPCM chunks and the PCM decoded from them (half the room when the
+        # video's frames are there too)
+        room = DUMP_BYTES // 2 if with_video else DUMP_BYTES
+        idx = sample_rows(na, clen + spf + 2, room - 4e6)
+        pick = torch.from_numpy(idx).to(dev)
+        out = {"adpcm_chunk_index": idx.astype(np.float64),
+               "adpcm_chunks": d_chunks[: na * clen].view(na, clen)[pick].cpu().numpy().astype(np.float32),
+               "adpcm_pcm": d_pcm2[: na * spf].view(na, spf)[pick].cpu().numpy().astype(np.float32)}
+        if with_video:
+            out.update(frames_for_dump("decode_", d_out, d_st, w, h, DUMP_BYTES - room))
+        return out
+
+    dump_outputs(E, args, outputs)
     audio_bytes = na * (clen + 2 * spf)
     if with_video:
-        kern = kernel_times(E, (pkg.K_UNSTUFF, pkg.K_HUFFMAN, pkg.K_HUFFMAN_SERIAL, pkg.K_RECON), steps=args.steps)
-        audio_kern = kernel_times(E, (pkg.K_ADPCM_DEC, pkg.K_ADPCM_ENC), actx, steps=args.steps)   # on the second stream, overlapped with the video kernels
         result = base_result(E, args, "AMV frames/sec/GPU (%dx%d decode with co-resident IMA-ADPCM, bit-exact)" % (w, h),
                              "frames/s", n, elapsed)
         result["config"] = {"workload": "%dx%d AMV decode of %d frames per GPU on one HIP stream, IMA-ADPCM encode + decode of "
                                         "the frames' %d-sample audio chunks on a second stream" % (w, h, n, spf),
                             "frames_per_gpu": n, "mean_chunk_bytes": stream_bytes / n, "parallelism": "frame-range x%d" % E.world,
                             "adpcm_samples_per_s": 2.0 * na * spf * args.steps * E.world / elapsed}
-        result["roofline"] = roofline(kern, stream_bytes + n * 3 * w * h, elapsed / args.steps, None,
-                                      {"co_resident_audio_kernels": audio_kern, "audio_algorithmic_bytes_per_step": audio_bytes})
+        if args.full:
+            kern = kernel_times(E, (pkg.K_UNSTUFF, pkg.K_HUFFMAN, pkg.K_HUFFMAN_SERIAL, pkg.K_RECON), steps=args.steps)
+            audio_kern = kernel_times(E, (pkg.K_ADPCM_DEC, pkg.K_ADPCM_ENC), actx, steps=args.steps)   # on the second stream, overlapped with the video kernels
+            result["roofline"] = roofline(kern, stream_bytes + n * 3 * w * h, elapsed / args.steps, None,
+                                          {"co_resident_audio_kernels": audio_kern, "audio_algorithmic_bytes_per_step": audio_bytes})
     else:
-        kern = kernel_times(E, (pkg.K_ADPCM_DEC, pkg.K_ADPCM_ENC), steps=args.steps)
         result = base_result(E, args, "IMA-ADPCM samples/sec/GPU (encode + decode, bit-exact)", "samples/s", 2 * na * spf, elapsed)
         result["dtype"] = "int32"
         result["config"] = {"workload": "%d AMV audio chunks of %d samples per GPU: PCM -> ADPCM (step index carried through "
                                         "the stream, as the reference encoder does) -> PCM" % (na, spf),
                             "chunks_per_gpu": na, "parallelism": "chunk-range x%d" % E.world}
-        result["roofline"] = roofline(kern, audio_bytes, elapsed / args.steps, profiled_adpcm_traffic if na == 200000 else None)
+        if args.full:
+            kern = kernel_times(E, (pkg.K_ADPCM_DEC, pkg.K_ADPCM_ENC), steps=args.steps)
+            result["roofline"] = roofline(kern, audio_bytes, elapsed / args.steps, profiled_adpcm_traffic if na == 200000 else None)
 
     if cpu_leg(E, args) and not with_video:
         m = min(na, 4096)
@@ -1049,15 +1159,16 @@ def run_amvlib(E, args):
     rates = {"AMV1.amv 128x96 (252 frames x 40 passes)": play(amv1, 40),
              "synthetic 160x120 (%d frames x 4 passes)" % n: play(synth, 4),
              "synthetic 160x120, AMVHIP_READAHEAD=1 (one frame per GPU round trip)": play(synth, 1, readahead=1) if n <= 4000 else None}
-    # gate: the file decodes to the oracle's frames through the same surface (first frames; the tests cover the rest)
-    amv = lib.AmvOpen(synth.encode())
-    for i in range(3):
-        assert lib.AmvReadNextFrame(amv) == 0 and lib.AmvVideoDecode(amv) == 0
-        got = np.frombuffer(__import__("ctypes").string_at(amv.contents.videobuf.fbmpdat, w * h * 3), np.uint8)
-        ch = blob[int(offs[i]):int(offs[i]) + int(lens[i])].tobytes()
-        if not (got == orc.decode_frame(ch, w, h)[0].ravel()).all():
-            raise SystemExit("amvlib surface differs from the oracle at frame %d" % i)
-    lib.AmvClose(amv)
+    if args.full:
+        # gate: the file decodes to the oracle's frames through the same surface (first frames; the tests cover the rest)
+        amv = lib.AmvOpen(synth.encode())
+        for i in range(3):
+            assert lib.AmvReadNextFrame(amv) == 0 and lib.AmvVideoDecode(amv) == 0
+            got = np.frombuffer(__import__("ctypes").string_at(amv.contents.videobuf.fbmpdat, w * h * 3), np.uint8)
+            ch = blob[int(offs[i]):int(offs[i]) + int(lens[i])].tobytes()
+            if not (got == orc.decode_frame(ch, w, h)[0].ravel()).all():
+                raise SystemExit("amvlib surface differs from the oracle at frame %d" % i)
+        lib.AmvClose(amv)
 
     value = rates["synthetic 160x120 (%d frames x 4 passes)" % n]
     result = {"metric": "AMV frames/sec through the amvlib call surface (AmvReadNextFrame + AmvVideoDecode + AmvAudioDecode, "
@@ -1066,6 +1177,8 @@ def run_amvlib(E, args):
               "data": "synthetic", "config": {"workload": "amvlib player loop over a muxed %d-frame 160x120 AMV file, one frame per "
                                                           "call, host buffers (PCIe inclusive), read-ahead windows behind the calls" % n,
                                               "frames_per_s": rates}}
+    if not args.full:
+        return result
     m = min(n, 1024)
     t = time.perf_counter()
     orc.decode_batch(blob, offs[:m].astype(np.uint64), lens[:m].astype(np.uint32), w, h, 0, threads=1)
@@ -1110,6 +1223,7 @@ def run_secondary(E, args, result):
         a.steps, a.warmup = min(args.steps, 10), min(args.warmup, 2)
         a.cpu_sample, a.cpu_seconds = 512, 1.0     # bounded CPU legs: every entry carries the CPU path beside it
         a.strong_leg = False                       # configs[3] as stated rides on the headline only
+        a.dump_outputs = None                      # --dump-outputs: the headline's outputs, not a leg's
         for k, v in over.items():
             setattr(a, k, v)
         torch.cuda.synchronize()
@@ -1286,7 +1400,7 @@ def run_workload(E, args):
     if args.workload == "decode":
         result = run_decode(E, args)
         plain = not (args.frames or args.width or args.height or args.pipelined or args.stream != "synthetic")
-        if plain and not args.no_secondary and not E.failed:
+        if plain and args.full and not args.no_secondary and not E.failed:
             run_secondary(E, args, result)
     elif args.workload == "encode":
         result = run_encode(E, args)
@@ -1318,15 +1432,29 @@ def parse_args(argv=None):
                          "batch k is collected) instead of amvhip_decode_batch_dev, a batch at a time")
     ap.add_argument("--strong", action="store_true",
                     help="decode: also run configs[3] as stated (one 10 000-frame stream scattered from rank 0, decoded, gathered "
-                         "back) and report it under config.config4_strong_10k; always on when WORLD_SIZE > 1")
+                         "back) and report it under config.config4_strong_10k; always on with --full when WORLD_SIZE > 1")
     ap.add_argument("--cpu-sample", type=int, default=4096, help="frames of the stream the CPU baseline decodes")
     ap.add_argument("--cpu-seconds", type=float, default=5.0, help="bound on the all-core part of the CPU baseline")
     ap.add_argument("--stream", choices=("synthetic", "mixed", "amv1"), default="synthetic",
                     help="decode: the seeded synthetic source; the same with every 16th frame noise (chunk sizes spread over 20x); "
                          "the reference's clip AMV1.amv (128x96) repeated")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default line only: skip the other BASELINE configs (config.secondary)")
-    return ap.parse_args(argv)
+                    help="with --full: skip the other BASELINE configs (config.secondary)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the gates against the CPU oracle and the second entropy kernel, "
+                         "per-kernel times and roofline, the CPU baseline, the other BASELINE configs (config.secondary) and, "
+                         "under ranks, the strong-scaling legs; without it a run sets up, warms up, times the steps and "
+                         "writes the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller as DIR/<name>.npy (float32, "
+                         "float64 for offsets and indices; at most 64 MB in all, a fixed seeded sample of frames or chunks "
+                         "where the whole output is larger)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload == "amvlib":
+        ap.error("--dump-outputs: the amvlib workload runs in a C host; its frames never reach this process")
+    return args
 
 
 def main():

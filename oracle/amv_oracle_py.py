@@ -47,6 +47,16 @@ def build(force=False):
             subprocess.run(["make", "-C", HERE, "-s", "ref"], check=True)
 
 
+def build_lavc():
+    """make -C oracle lavc: the AVCodec plugin and its C host into _ref/, only where the reference's FFmpeg tree exists
+    (the Makefile looks, and decides what is out of date); needs the product's libamvhip.so, so it runs after
+    amv-codec-tools_amd/build.py"""
+    import fcntl
+    with open(os.path.join(HERE, ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        subprocess.run(["make", "-C", HERE, "-s", "lavc"], check=True)
+
+
 _lib = None
 
 

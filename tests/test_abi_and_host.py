@@ -215,7 +215,7 @@ def test_avcodec_plugin_tables(pkg):
     """libamvhip_lavc.so (built where the reference's avcodec.h exists) exports the four tables allcodecs.c registers,
     laid out as `struct AVCodec` (avcodec.h:2149-2170): name, type, id, priv_data_size, init, encode, close, decode"""
     import ctypes
-    path = os.path.join(os.path.dirname(pkg.LIB_PATH), "libamvhip_lavc.so")
+    path = os.path.join(ROOT, "oracle", "_ref", "libamvhip_lavc.so")
     if not os.path.exists(path):
         pytest.skip("the plugin is compiled against /root/reference's avcodec.h; not built here")
     pkg.load_library()

@@ -7,6 +7,8 @@ import subprocess
 import sys
 import textwrap
 
+import pytest
+
 from conftest import ROOT
 
 BENCH = os.path.join(ROOT, "bench.py")
@@ -217,7 +219,7 @@ RANK_STUB = """
             r["config"] = dict({"workload": metric, "parallelism": "frame-range x%%d" %% E.world, "frames_per_gpu": units,
                                 "mean_chunk_bytes": 3500.0, "handed_to_serial": 0}, **cfg)
             r["roofline"] = bench.roofline({"k": {"launches": 1, "ms_per_step": 1.0, "ms_per_launch": 1.0}}, 1e6, 0.01, None)
-            if metric.startswith("160x120") and E.dist and getattr(args, "strong_leg", True):
+            if metric.startswith("160x120") and E.dist and getattr(args, "strong_leg", True) and (args.full or args.strong):
                 bench.guarded_strong(E, r, lambda: {"ms_per_step": 0.9, "frames_per_s": 1.1e7, "rccl_ranks": dist.get_world_size(),
                                                     "phase_ms_max_over_ranks": {"scatter": 0.1, "decode": 0.5, "gather": 0.3}})
                 share = bench.balanced_src_share(E.world)
@@ -252,7 +254,7 @@ def test_two_rank_line_carries_every_config_and_the_cpu_path(tmp_path):
     CPU leg, the other rank waiting in the barrier), rccl_ranks / run_status / strong10k_status and all five BASELINE configs
     with their CPU path inside the first 24 scalars of `config`"""
     child = _stub(tmp_path, RANK_STUB % {"root": ROOT})
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"], child)
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], child)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["cpu_baseline"]["value"] == 5.0
@@ -278,12 +280,53 @@ def test_two_rank_line_carries_every_config_and_the_cpu_path(tmp_path):
     assert list(cfg).index("strong10k_scatter_ms") < list(cfg).index("strong10k_srcshare") < list(cfg).index("parallelism")
 
 
+def test_plain_two_rank_line_is_the_headline_alone(tmp_path):
+    """without --full a run with ranks times the headline and writes its line: no CPU path, no other BASELINE config, no
+    strong-scaling leg -- and the same weak value over the same reductions"""
+    child = _stub(tmp_path, RANK_STUB % {"root": ROOT})
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"], child)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads(r.stdout)
+    assert line["n_gpus"] == 2 and abs(line["value"] - 2 * 160000 * 2 / 0.02) < 1e-3 and line["ms_per_step"] == 1e3 * 0.02 / 2
+    assert "cpu_baseline" not in line and "secondary" not in line["config"] and line["config"]["run_status"] == "ok"
+    assert not [k for k in line["config"] if k.startswith(("strong10k", "config4", "c320_", "enc320_", "adpcm_"))]
+
+
+def test_dump_outputs_is_bounded_seeded_and_lazy(tmp_path):
+    """--dump-outputs: the frames' BGR rows without the stride's padding, a fixed seeded sample when the batch is larger
+    than 64 MB in float32, the statuses, all float32 / float64; nothing is made without the option"""
+    sys.path.insert(0, ROOT)
+    import bench
+    import numpy as np
+    import torch
+    n, w, h, stride = 3000, 160, 120, 512
+    d_out = torch.full((n, h, stride), 0xFF, dtype=torch.uint8)
+    d_out[:, :, : w * 3] = (torch.arange(n) % 251).to(torch.uint8)[:, None, None]
+    d_st = torch.zeros(n, dtype=torch.int32)
+    E, args = bench.Env(), bench.parse_args(["--dump-outputs", str(tmp_path / "a")])
+    bench.dump_outputs(E, args, lambda: bench.frames_for_dump("decode_", d_out, d_st, w, h, bench.DUMP_BYTES))
+    bench.dump_outputs(E, bench.parse_args(["--dump-outputs", str(tmp_path / "b")]),
+                       lambda: bench.frames_for_dump("decode_", d_out, d_st, w, h, bench.DUMP_BYTES))
+    bench.dump_outputs(E, bench.parse_args([]), lambda: 1 / 0)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["decode_frame_index.npy", "decode_frames.npy", "decode_status.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64e6
+    for f in files:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    frames, idx = np.load(tmp_path / "a" / "decode_frames.npy"), np.load(tmp_path / "a" / "decode_frame_index.npy")
+    assert frames.dtype == np.float32 and frames.shape[1:] == (h, w * 3) and 100 < len(idx) < n
+    assert (np.diff(idx) > 0).all() and (frames[:, 0, 0] == idx % 251).all() and not (frames == 0xFF).any()
+    assert len(np.load(tmp_path / "a" / "decode_status.npy")) == n
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--workload", "amvlib", "--dump-outputs", str(tmp_path / "c")])
+
+
 def test_a_rank_that_fails_in_a_leg_tells_its_peers_and_the_line_still_goes_out(tmp_path):
     """rank 1 raises inside the co-resident leg: it sets the flag in the store and leaves with EXIT_FAILED; rank 0 -- blocked
     in that leg's reduction -- learns it from the store (or from the backend), writes the line with what had finished and
     run_status = "error: ...", and leaves non-zero too.  Seconds, not the leg's watchdog."""
     child = _stub(tmp_path, RANK_STUB % {"root": ROOT})
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"], child, {"STUB_FAIL": "1:coresident:raise"}, timeout=100)
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], child, {"STUB_FAIL": "1:coresident:raise"}, timeout=100)
     assert r.returncode == 4, r.stderr[-3000:]
     line = json.loads(r.stdout)
     assert line["config"]["run_status"].startswith("error:") and line["config"]["strong10k_status"] == "ok"
@@ -295,7 +338,7 @@ def test_a_rank_that_hangs_in_a_leg_ends_the_run_with_the_line_written(tmp_path)
     """rank 1 never comes back from the encode leg: every rank's watchdog fires after AMV_BENCH_LEG_SECONDS, rank 0 writes
     the line with run_status = "hung in leg encode_320x240 on rank 0" and both leave with EXIT_HUNG"""
     child = _stub(tmp_path, RANK_STUB % {"root": ROOT})
-    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1"], child, {"STUB_FAIL": "1:encode:hang", "AMV_BENCH_LEG_SECONDS": "3"},
+    r = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], child, {"STUB_FAIL": "1:encode:hang", "AMV_BENCH_LEG_SECONDS": "3"},
              timeout=100)
     assert r.returncode == 3, r.stderr[-3000:]
     line = json.loads(r.stdout)
