@@ -10,13 +10,12 @@
 //      copies the scan into a workspace as big-endian words with the byte after every FF removed
 //      (ReadByte, AmvJpeg.c:1061-1071), so that a decoder state is just a bit index.
 //
-//   amv_huffman_sync2_kernel<L> (records form) and amv_huffman_sync_kernel<L> (dense form: coefficient lines)
-//   (independent waves sharing the tables, up to 13 per workgroup, one workgroup per CU -- dense: 10 x 2; L lanes per
-//   frame, 64/L frames per wave; waves take tasks of 64/L frames from an atomic queue)
+//   amv_huffman_sync2_kernel<L>
+//   (independent waves sharing the tables, up to 13 per workgroup, one workgroup per CU; L lanes per frame, 64/L frames
+//   per wave; waves take tasks of 64/L frames from an atomic queue)
 //   0. a lane reads its part of the stream through a 16-word window in LDS that it refills from the
 //      workspace (L2) with 16-byte loads whenever any lane of the wave has used its window up, so a
-//      wave needs 4 KB of LDS whatever the frame size (dense form: the frames' coefficient lines are
-//      zeroed first);
+//      wave needs 4 KB of LDS whatever the frame size;
 //   1. the bit stream is cut into L equal subsequences; lane i walks subsequence i from a GUESSED
 //      state (its first bit, "the DC symbol of block 0 comes next") up to the first symbol boundary
 //      past its end and remembers the state it arrives in: (bit, index in block, block in MCU).
@@ -25,32 +24,27 @@
 //      bit / closes the block and carries on.  The true decoder of a valid stream never takes
 //      those branches, and a stream with a real error is caught in pass 4, which is strict;
 //   2. the lanes find the state the decoder is in where their share starts.  Lane 0's start is exact; a lane whose left
-//      neighbour is final takes that lane's arrival as its own final start.  Dense form (amv_huffman_sync_kernel): every
-//      lane takes its left neighbour's arrival state as its start state and walks again if that changed -- after round r
-//      lanes 0..r are exact, and in practice wrong starts fall into step with the true decoder with a chance of 0.8 per
-//      1 750 bits (the slow part is the luma/chroma phase of the MCU, a 1-in-6 guess), so the loop ends early (worst case
-//      L-1 rounds: still correct).  Records form (amv_huffman_sync2_kernel, round 5): the lanes REMEMBER their walks
-//      (start -> arrival per share), finality is a prefix scan over the lanes' "which of my walks starts where yours
-//      arrived" maps, and lanes with nothing to walk try candidate starts for the shares that are still open: the worst
-//      frame of 10 000 takes 6 rounds instead of 9 (the kernel has the details; tools/sim_sync.c is a CPU model of it).
+//      neighbour is final takes that lane's arrival as its own final start.  Wrong starts fall into step with the true
+//      decoder with a chance of 0.8 per 1 750 bits (the slow part is the luma/chroma phase of the MCU, a 1-in-6 guess).
+//      The lanes REMEMBER their walks (start -> arrival per share), finality is a prefix scan over the lanes' "which of
+//      my walks starts where yours arrived" maps, and lanes with nothing to walk try candidate starts for the shares that
+//      are still open: the worst frame of 10 000 takes 6 rounds instead of the 9 of re-walking from the left
+//      neighbour's arrival alone (the kernel has the details; tools/sim_sync.c is a CPU model of it).
 //      These walks only look at symbol lengths and index advances;
 //      the number of lanes per frame follows the batch size (huffman_sync_lanes): as many as keep every task resident at
 //      once, because the launch lasts as long as one task does;
-//   3. a prefix sum of "blocks finished per lane" gives every lane its first block number;
-//   3'. records form: a prefix sum of "value-carrying symbols per lane" gives every lane its first record;
-//   4. one strict pass decodes values and writes them: records form, one 32-bit word per DC coefficient
+//   3. a prefix sum of "blocks finished per lane" gives every lane its first block number, and one of "value-carrying
+//      symbols per lane" its first record;
+//   4. one strict pass decodes values and writes them as records, one 32-bit word per DC coefficient
 //      and per non-zero AC coefficient (index, block modulo 64, value) in stream order, staged per lane
 //      in LDS and stored as aligned 32-byte pieces, + where the records of every MCU-row segment lie -- what
-//      amv_reconstruct_kernel scatters into LDS; dense form, 2-byte stores into the frame's zeroed
-//      coefficient lines.  DC prediction (ycoef/ucoef/vcoef, AmvJpeg.c:1200-1221) is a running sum per
-//      component: each lane's sums count from its own start,
-//   5. a prefix sum over the lanes' totals gives every lane its three bases: records form, they go into
-//      the frame's lane table and the reader adds them; dense form, the lane adds them to the DC values
-//      it stored itself.
-//   The records form walks in arithmetic on a state chosen for it (fast_skip, fast_stride: "One lane per frame"
-//   below says how); the dense form keeps the select-based walks (walk_skip, walk_write).
+//      amv_reconstruct_kernel scatters into LDS.  DC prediction (ycoef/ucoef/vcoef, AmvJpeg.c:1200-1221) is a
+//      running sum per component: each lane's sums count from its own start,
+//   5. a prefix sum over the lanes' totals gives every lane its three bases; they go into the frame's lane table and
+//      the reader adds them.
+//   The walks are arithmetic on a state chosen for them (fast_skip, fast_stride: "One lane per frame" below says how).
 //
-//   amv_huffman_fast_kernel (one lane per frame, records form: what a batch that fills the chip that way gets)
+//   amv_huffman_fast_kernel (one lane per frame: what a batch that fills the chip that way gets)
 //      passes 1-3 and 5 fall away, pass 4 is fast_stride without a share limit; records leave as whole lines.
 //
 // Statuses equal the serial kernel's bit for bit (tests): the first error on the true path stops
@@ -73,13 +67,6 @@ constexpr uint32_t kRingWords = 16;       // LDS words per lane: the window of i
 // two pieces.
 constexpr uint32_t kDummyRecord = 0x8000u;    // bit 15: a filler no block owns
 constexpr uint32_t kNever = 0xffffffffu;
-constexpr uint32_t kTableBytes = (4u << kLut1Bits) * 2u + (4u << kM2Bits) * 2u;   // m1 + m2 of HuffDecodeImage, contiguous
-
-struct State {
-    uint32_t p;   // bit index in the unstuffed stream
-    uint32_t k;   // next coefficient index in the block, 0 = the DC symbol comes next
-    uint32_t k6;  // block inside the MCU, 0..5
-};
 
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -272,19 +259,6 @@ __global__ __launch_bounds__(256) void amv_unstuff_kernel(
     }
 }
 
-// =============================================================================================
-// walks.  Table entries (HuffDecodeImage::m1/m2): bits 0-4 code length + magnitude bits (0 = no
-// such code), bits 5-10 how far the coefficient index moves (run + 1; 1 for a DC symbol; 63 for
-// end-of-block, which with k >= 1 always reaches 64), bits 11-14 magnitude bits; in m1 bit 15
-// means "the code is longer than 9 bits, see m2".
-//
-// Codes longer than 9 bits sit at the top of the 9-bit prefix space (canonical codes ascend with
-// length): in every table they are the prefixes [507, 512) or fewer, i.e. they all begin with six
-// one-bits, and a code is at most 16 bits long.  m2 is therefore indexed by the ten bits behind those
-// six, 1024 entries per table: its address follows from the window alone, both levels are read
-// together and the right one is selected afterwards -- no dependent second LDS round trip, no branch.
-// =============================================================================================
-
 namespace {
 
 // A lane's view of its frame's unstuffed words.  The frame stays in the global workspace (L2); the lane
@@ -302,15 +276,8 @@ struct Stream {
     uint4 pf0, pf1;      // words [hi, hi + 8), requested
 };
 
-// A walk may run kStride symbols between services: a symbol is at most 27 bits (16 code + 11 magnitude),
-// so 10 of them move the read index by at most 9 words, and a service leaves every lane >= 9 words.
-constexpr int kStride = 10;
 // the writing walk runs 8 symbols between services: at most 8 new records then join at most 7 staged ones
 constexpr int kStrideWrite = 8;
-
-__device__ __forceinline__ uint32_t ring_word(const Stream& s, uint32_t x) {
-    return s.ring[(x & (kRingWords - 1u)) * kWave];
-}
 
 __device__ __forceinline__ uint4 stream_piece(const Stream& s, uint32_t x) {
     uint4 v = make_uint4(0, 0, 0, 0);
@@ -318,132 +285,10 @@ __device__ __forceinline__ uint4 stream_piece(const Stream& s, uint32_t x) {
     return v;
 }
 
-__device__ __forceinline__ void ring_put(const Stream& s, uint32_t x, const uint4& v) {   // x: multiple of 4
-    uint32_t* d = s.ring + (x & (kRingWords - 1u)) * kWave;
-    d[0] = v.x; d[kWave] = v.y; d[2 * kWave] = v.z; d[3 * kWave] = v.w;
-}
-
 __device__ __forceinline__ void stream_request(Stream& s) {
     s.pf0 = stream_piece(s, s.hi);
     s.pf1 = stream_piece(s, s.hi + 4u);
 }
-
-// the requested words take the place of the older half of the window; the next eight are requested
-__device__ __forceinline__ void stream_advance(Stream& s) {
-    ring_put(s, s.hi, s.pf0);
-    ring_put(s, s.hi + 4u, s.pf1);
-    s.hi += 8u;
-    stream_request(s);
-}
-
-// start of a walk at word `from`: the window holds words [from & ~7, +16)
-__device__ __forceinline__ void stream_open(Stream& s, uint32_t from) {
-    const uint32_t lo = from & ~7u;
-    const uint4 a = stream_piece(s, lo), b = stream_piece(s, lo + 4u), c = stream_piece(s, lo + 8u), d = stream_piece(s, lo + 12u);
-    ring_put(s, lo, a);
-    ring_put(s, lo + 4u, b);
-    ring_put(s, lo + 8u, c);
-    ring_put(s, lo + 12u, d);
-    s.hi = lo + kRingWords;
-    stream_request(s);
-}
-
-// between strides: a lane whose read index is within 9 words of the window's end moves the window on
-// (once, with words that arrived long ago; a second time, waiting, only after a run of maximal symbols)
-__device__ __forceinline__ void stream_service(Stream& s, uint32_t widx) {
-    while (widx + 9u > s.hi) stream_advance(s);
-}
-
-// tab = table number << kLut1Bits; v = the next 32 bits of the stream
-__device__ __forceinline__ uint32_t lookup(const uint16_t* __restrict__ m1, const uint16_t* __restrict__ m2,
-                                           uint32_t tab, uint32_t v) {
-    const uint32_t e1 = m1[tab + (v >> (32 - kLut1Bits))];
-    const uint32_t e2 = m2[(tab << 1) + ((v >> (32 - 6 - kM2Bits)) & ((1u << kM2Bits) - 1u))];
-    return (e1 & 0x8000u) ? e2 : e1;
-}
-
-// table of the symbol that comes next: k = 0 -> DC, else AC; blocks 4 and 5 of an MCU are chroma
-__device__ __forceinline__ uint32_t table_of(uint32_t k, uint32_t k6) {
-    return ((k ? 2u : 0u) + (k6 >= 4u ? 1u : 0u)) << kLut1Bits;
-}
-
-// The bit window of a walk: two consecutive stream words hi:lo and bo in [1, 32], the number of bits of hi that are
-// used up; the next 32 bits of the stream are ({hi, lo} >> (32 - bo)) -- one v_alignbit_b32.  nextw is the word
-// after lo, widx the index of the word after that (fetched from the lane's ring while the look-ups are in flight).
-struct Window {
-    uint32_t hi, lo, nextw, widx, bo;
-};
-
-__device__ __forceinline__ Window window_open(Stream& w, uint32_t p) {
-    const uint32_t b = p & 31u, w0 = p >> 5;
-    stream_open(w, w0);
-    Window x;
-    x.bo = b ? b : 32u;                                   // a word boundary: "all of the word before is used up"
-    const uint32_t base = b ? w0 : w0 - 1u;               // (then hi is never looked at; any ring word will do)
-    x.hi = ring_word(w, base);
-    x.lo = ring_word(w, base + 1u);
-    x.nextw = ring_word(w, base + 2u);
-    x.widx = base + 3u;
-    return x;
-}
-
-__device__ __forceinline__ uint32_t window_bits(const Window& x) {
-    return __builtin_amdgcn_alignbit(x.hi, x.lo, 32u - x.bo);
-}
-
-// `used` (<= 27) bits consumed; cand = the ring word at x.widx
-__device__ __forceinline__ void window_consume(Window& x, uint32_t used, uint32_t cand) {
-    x.bo += used;
-    const bool step = x.bo > 32u;
-    x.hi = step ? x.lo : x.hi;
-    x.lo = step ? x.nextw : x.lo;
-    x.nextw = step ? cand : x.nextw;
-    x.widx += step ? 1u : 0u;
-    x.bo -= step ? 32u : 0u;
-}
-
-// Speculative walk from `s` while s.p < limit: where symbols start and how the block position
-// moves, nothing else.  Returns the number of blocks finished.  A stride of kStride symbols is straight-line code
-// (a lane that is past its limit goes through the motions without moving), so that the scheduler can overlap the
-// table look-up of one symbol with the bookkeeping of the one before.
-__device__ __forceinline__ uint32_t walk_skip(Stream& w, const uint16_t* __restrict__ m1,
-                                              const uint16_t* __restrict__ m2, State& s, uint32_t limit) {
-    uint32_t p = s.p, k = s.k, k6 = s.k6, nblk = 0;
-    bool active = p < limit;
-    if (!__ballot(active)) return 0u;
-    Window x = window_open(w, active ? p : 0u);
-    uint32_t tab = table_of(k, k6);
-    while (__ballot(active) != 0ull) {
-        if (active) stream_service(w, x.widx);
-#pragma unroll
-        for (int it = 0; it < kStride; ++it) {
-            const uint32_t cand = ring_word(w, x.widx);        // the word after nextw, in flight with the look-ups
-            const uint32_t e = lookup(m1, m2, tab, window_bits(x));
-            const uint32_t used = active ? max(e & 31u, 1u) : 0u;   // nonsense under a guessed start: slip one bit
-            const uint32_t kn = k + (active ? (e >> 5) & 63u : 0u);
-            p += used;
-            window_consume(x, used, cand);
-            const bool end = kn >= 64u;                        // end of block, a full block, or an over-long run
-            k = end ? 0u : kn;
-            k6 = end ? (k6 == 5u ? 0u : k6 + 1u) : k6;
-            nblk += end ? 1u : 0u;
-            tab = table_of(k, k6);
-            active = active && p < limit;
-        }
-    }
-    s.p = p; s.k = k; s.k6 = k6;
-    return nblk;
-}
-
-struct WriteResult {
-    uint32_t err;        // kStFormat / kStOverrun when the walk hit a real error
-    uint32_t err_blk;    // absolute block the error hit
-    uint32_t stop_p;     // bits consumed when the walk ended (FORMAT: incl. the reference's 17-bit give-up)
-    bool done;           // the frame's last block was finished here
-    uint32_t dc_first;   // first block whose DC symbol this lane decoded, and how many follow
-    uint32_t dc_count;
-    int sum[3];          // the lane's DC differences added up per component (Y, Cb, Cr)
-};
 
 // The MCU-row segments amv_reconstruct_kernel works in: kSegMcus MCUs, the last one of a row shorter.
 struct SegGeom {
@@ -475,82 +320,14 @@ __device__ __forceinline__ void stage_flush(const uint32_t* stage, uint32_t* __r
     }
 }
 
-// The strict, writing walk (HufBlock / DecodeElement, AmvJpeg.c:842-974) from an exact state into the frame's
-// (zeroed) coefficient lines: the dense form.  A stride of kStride symbols is straight-line code -- every lane goes
-// through every step, a lane that has stopped (end of frame, error, end of its share) without moving -- with
-// conditional 2-byte stores.  (The records form has walks of its own: fast_stride, below.)
-__device__ __forceinline__ WriteResult walk_write(Stream& w, const uint16_t* __restrict__ m1,
-                                                  const uint16_t* __restrict__ m2, State s, uint32_t limit,
-                                                  uint32_t blk, uint32_t blocks_per_frame, int16_t* __restrict__ coef) {
-    WriteResult r{0u, 0u, 0u, false, 0u, 0u, {0, 0, 0}};
-    uint32_t p = s.p, k = s.k, k6 = s.k6;
-    r.dc_first = blk + (k ? 1u : 0u);
-    int s0 = 0, s1 = 0, s2 = 0;
-    bool alive = p < limit;
-    uint32_t stop = 0;           // why the lane stopped: 1 invalid code, 2 index past 63, 3 the frame's last block is done
-    Window x = window_open(w, p);
-    uint32_t tab = table_of(k, k6);
-    while (__ballot(alive) != 0ull) {
-        if (alive) stream_service(w, x.widx);
-#pragma unroll
-        for (int it = 0; it < kStride; ++it) {
-            const uint32_t cand = ring_word(w, x.widx);
-            const uint32_t v = window_bits(x);
-            const uint32_t e = lookup(m1, m2, tab, v);
-            const uint32_t used = e & 31u, size = (e >> 11) & 15u, adv = (e >> 5) & 63u;
-            const bool bad = used == 0u;                         // no code matches: FUNC_FORMAT_ERROR, AmvJpeg.c:887
-            const bool isdc = k == 0u;
-            const bool iseob = !isdc && adv == 63u;              // end of block (:959-964)
-            const uint32_t idx = k + adv - 1u;                   // AC: where the coefficient goes
-            const bool over = !bad && !isdc && !iseob && idx > 63u;   // the reference writes out of bounds here (:967-969)
-            // magnitude bits -> value (:924-933): the `size` bits behind the code; size 0 gives 0
-            const uint32_t mag = __builtin_amdgcn_ubfe(v, 32u - used, size);
-            const uint32_t full = (1u << size) - 1u;
-            const int val = (int)mag - (mag <= (full >> 1) ? (int)full : 0);
-            // consume (a code that matches nothing consumes nothing; the reference has read 17 bits by then)
-            const uint32_t eat = (alive && !bad) ? used : 0u;
-            p += eat;
-            window_consume(x, eat, cand);
-            const bool good = alive && !bad && !over;
-            const bool dc = isdc && good;                        // DC difference (:945-951), summed per component (:1200-1221)
-            const int t = (k6 < 4u ? s0 : (k6 == 4u ? s1 : s2)) + val;
-            s0 = (dc && k6 < 4u) ? t : s0;
-            s1 = (dc && k6 == 4u) ? t : s1;
-            s2 = (dc && k6 == 5u) ? t : s2;
-            r.dc_count += dc ? 1u : 0u;
-            const bool ac = good && !isdc && !iseob && size != 0u;
-            if (dc) coef[(uint64_t)blk * 64u] = (int16_t)t;      // the sum counts from this lane's start; pass 5 adds the base
-            if (ac) coef[(uint64_t)blk * 64u + idx] = (int16_t)val;
-            const uint32_t newk = isdc ? 1u : idx + 1u;
-            const bool block_end = good && (iseob || (!isdc && newk == 64u));
-            k = good ? (block_end ? 0u : newk) : k;
-            k6 = block_end ? (k6 == 5u ? 0u : k6 + 1u) : k6;
-            blk += block_end ? 1u : 0u;
-            tab = table_of(k, k6);
-            const bool finished = block_end && blk == blocks_per_frame;
-            const uint32_t why = bad ? 1u : (over ? 2u : (finished ? 3u : 0u));
-            stop = (alive && why) ? why : stop;
-            alive = alive && !why && p < limit;
-        }
-    }
-    // the state froze where the lane stopped
-    r.err = stop == 1u ? kStFormat : (stop == 2u ? kStOverrun : 0u);
-    r.err_blk = blk;
-    r.stop_p = stop == 1u ? p + 17u : p;
-    r.done = stop == 3u;
-    r.sum[0] = s0; r.sum[1] = s1; r.sum[2] = s2;
-    return r;
-}
-
 }  // namespace
 
-// Outputs of the records form (SyncOut::rec != nullptr), all per frame: its lines of rec (rec_line), seg_start[segs + 1][2]
-// {from, to} bounds of each MCU-row segment's records (SyncSinks; entries of segments the decoder never reached, and
-// the last one, hold the total twice), lane_tab[L] = {first block whose DC the lane decoded, DC base Y, Cb, Cr} (lanes right of the
+// Outputs of the synchronising kernels, all per frame: its lines of rec (rec_line), seg_start[segs + 1][2] {from, to}
+// bounds of each MCU-row segment's records (SyncSinks; entries of segments the decoder never reached, and the last one,
+// hold the total twice), lane_tab[L] = {first block whose DC the lane decoded, DC base Y, Cb, Cr} (lanes right of the
 // one that met the frame's end or first error: first block ~0), rec_count = total, or ~0 when the frame was handed to
 // the serial kernel, whose output is dense coefficient lines.
 struct SyncOut {
-    int16_t* coef;
     uint32_t* rec;
     const uint32_t* rec_line;
     uint32_t* seg_start;
@@ -563,145 +340,10 @@ struct SyncOut {
     uint32_t ok_in_blocks;   // nmcu_ok counts whole blocks instead of whole MCUs (SyncSinks)
 };
 
-// The dense form (coefficient lines: amvhip_huffman_decode_dev's output).
-// dynamic LDS: [ m1 4 KB | m2 8 KB | per wave: ring of kRingWords words per lane ]
-// With a list, the kernel decodes frames list[0 .. *list_count) (surplus waves do nothing).
-template <int L>
-__global__ __launch_bounds__(kWave* 16) void amv_huffman_sync_kernel(
-    const uint32_t* __restrict__ ws, const uint32_t* __restrict__ ws_bytes, uint32_t n,
-    const uint32_t* __restrict__ list, const uint32_t* __restrict__ list_count,
-    uint32_t blocks_per_frame, const uint32_t* __restrict__ ws_line,
-    const HuffDecodeImage* __restrict__ img, SyncOut out, int32_t* __restrict__ status,
-    uint32_t* __restrict__ nmcu_ok, uint32_t* __restrict__ queue, unsigned long long* __restrict__ stats) {
-    constexpr int kFrames = kWave / L;   // frames per wave
-    extern __shared__ __attribute__((aligned(16))) uint8_t s_mem[];
-    const uint16_t* m1 = reinterpret_cast<const uint16_t*>(s_mem);
-    const uint16_t* m2 = m1 + (4 << kLut1Bits);
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t slot = lane / L, sub = lane % L;
-
-    {   // tables, shared by the waves of the workgroup
-        const uint4* src = reinterpret_cast<const uint4*>(&img->m1[0][0]);
-        uint4* dst = reinterpret_cast<uint4*>(s_mem);
-        for (uint32_t i = threadIdx.x; i < kTableBytes / 16u; i += blockDim.x) dst[i] = src[i];
-    }
-    __syncthreads();   // the only workgroup-wide barrier; from here the waves are on their own
-    uint32_t* ring = reinterpret_cast<uint32_t*>(s_mem + kTableBytes) + wave * (kRingWords * kWave) + lane;
-    if (list) n = *list_count;
-    const uint32_t ntasks = (n + kFrames - 1) / kFrames;
-    // Tasks (kFrames frames each) are handed out through a counter: a wave that finishes early -- the
-    // number of synchronisation rounds varies a lot between frames -- takes the next one instead of
-    // idling until the slowest wave of the grid is done.  Every wave leaves once the counter passes ntasks.
-    for (;;) {
-    uint32_t task = 0;
-    if (lane == 0) task = atomicAdd(queue, 1u);
-    task = __shfl(task, 0);
-    if (task >= ntasks) return;
-
-    const bool timing = stats != nullptr && lane == 0;   // optional phase clock (amvhip_entropy_stats)
-    unsigned long long tc[6] = {0, 0, 0, 0, 0, 0};
-    if (timing) tc[0] = clock64();
-
-    const uint32_t idx = task * kFrames + slot;
-    const uint32_t frame = idx < n ? (list ? list[idx] : idx) : kNever;
-    const uint32_t total = frame != kNever ? ws_bytes[frame] : kNever;   // kNever: handed to the serial kernel
-    const bool live = total != kNever;
-    const uint32_t fsafe = live ? frame : 0u;
-    int16_t* const coef = out.coef + (uint64_t)fsafe * blocks_per_frame * 64u;
-    const uint32_t valid_bits = live ? total * 8u : 0u;
-    if (live) {   // the frame's coefficient lines start as zeros
-        uint4* z = reinterpret_cast<uint4*>(coef);
-        for (uint32_t i = sub; i < blocks_per_frame * 8u; i += L) z[i] = make_uint4(0, 0, 0, 0);
-    }
-    Stream win{ws + (uint64_t)ws_line[fsafe] * 4u, live ? ((total + 15u) >> 4) * 4u : 0u, ring, 0u, make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
-
-    // ---- 1/2. speculative walks until every lane's start state equals its neighbour's arrival
-    uint32_t S = ((valid_bits + L - 1) / L + 31u) & ~31u;   // bits per lane, a whole number of words
-    if (S < 64u) S = 64u;
-    // the last lane of a frame has no right neighbour to feed: it only runs in pass 4
-    const uint32_t limit = (!live || sub == L - 1) ? 0u : (sub + 1u) * S;
-    State entry{sub * S, 0u, 0u}, arrive = entry;
-    if (timing) tc[1] = clock64();
-    uint32_t my_blocks = walk_skip(win, m1, m2, arrive, limit);
-    if (timing) tc[2] = clock64();
-    uint32_t rounds = 0;
-    const uint64_t seg = L == 64 ? ~0ull : (((1ull << (L & 63)) - 1ull) << (slot * L));
-    for (int round = 0; round < L; ++round) {
-        State left;
-        left.p = __shfl_up(arrive.p, 1, L);
-        left.k = __shfl_up(arrive.k, 1, L);
-        left.k6 = __shfl_up(arrive.k6, 1, L);
-        const bool changed = live && sub != 0 && (left.p != entry.p || left.k != entry.k || left.k6 != entry.k6);
-        const uint64_t who = __ballot(changed);
-        if (!who) break;
-        if (who & seg) ++rounds;
-        if (changed) {
-            entry = left;
-            arrive = left;
-            my_blocks = walk_skip(win, m1, m2, arrive, limit);
-        }
-    }
-    if (timing) tc[3] = clock64();
-
-    // ---- 3. first block of every lane (the last lane has not walked: its count is 0, it is last)
-    uint32_t all_blocks;
-    const uint32_t blk0 = seg_excl_sum<L>(my_blocks, sub, all_blocks);
-
-    // ---- 4. the strict, writing pass.  Lanes left of the frame's end (or first error) are exact;
-    // whatever a lane to the right of it does is ignored below.
-    __builtin_amdgcn_s_waitcnt(0);   // the zeroing stores have landed before the sparse ones go out
-    WriteResult wr{0u, 0u, 0u, false, 0u, 0u, {0, 0, 0}};
-    if (live && blk0 < blocks_per_frame)
-        wr = walk_write(win, m1, m2, entry, sub == L - 1 ? kNever : limit, blk0, blocks_per_frame, coef);
-    if (timing) tc[4] = clock64();
-    const uint64_t stop_mask = __ballot(wr.done || wr.err != 0u) & seg;
-    uint32_t st = 0, good_blocks = blocks_per_frame;
-    if (stop_mask) {
-        const int stop_lane = __builtin_ctzll(stop_mask);   // leftmost = the true path
-        const uint32_t e = __shfl(wr.err, stop_lane);
-        const uint32_t eb = __shfl(wr.err_blk, stop_lane);
-        const uint32_t sp = __shfl(wr.stop_p, stop_lane);
-        st = e;
-        if (e) good_blocks = eb;
-        if (sp > valid_bits) st |= kStTruncated;
-    } else {
-        st = kStFormat; good_blocks = 0;   // unreachable: the last lane runs until the frame ends or fails
-    }
-
-    // ---- 5. DC prediction: the sums of the lanes to the left are a lane's base, which it adds to the DCs it stored (a
-    // lane reads back only its own stores -- same thread, ordered by the wait -- so no cache is in play).
-    uint32_t tot;
-    const int by = (int)seg_excl_sum<L>((uint32_t)wr.sum[0], sub, tot);
-    const int bu = (int)seg_excl_sum<L>((uint32_t)wr.sum[1], sub, tot);
-    const int bv = (int)seg_excl_sum<L>((uint32_t)wr.sum[2], sub, tot);
-    __builtin_amdgcn_s_waitcnt(0);
-    for (uint32_t j = 0; j < wr.dc_count; ++j) {
-        const uint32_t b = wr.dc_first + j, c6 = b % 6u;
-        const int base = c6 < 4u ? by : (c6 == 4u ? bu : bv);
-        int16_t* q = coef + (uint64_t)b * 64u;
-        *q = (int16_t)(*q + base);
-    }
-    if (timing) {
-        tc[5] = clock64();
-        for (int q = 0; q < 5; ++q) atomicAdd(&stats[4 + q], tc[q + 1] - tc[q]);
-        atomicAdd(&stats[9], 1ull);
-    }
-    if (live && sub == 0) {
-        if (stats) {   // optional: how hard the synchronisation worked (amvhip_entropy_stats)
-            atomicAdd(&stats[0], 1ull);
-            atomicAdd(&stats[1], (unsigned long long)rounds);
-            atomicMax(&stats[2], (unsigned long long)rounds);
-        }
-        status[frame] = (int32_t)st;
-        nmcu_ok[frame] = out.ok_in_blocks ? good_blocks : good_blocks / 6u;
-    }
-    }   // next task
-}
-
 // =============================================================================================
-// One lane per frame (a batch that fills the chip that way: no speculation, no lane table).  The symbol step of
-// walk_write spends most of its ~90 instructions on selects -- which table, which component's DC sum, is the lane
-// alive, did the block end, did a segment start -- and the kernel is bound by VALU issue.  Here the step is
+// One lane per frame (a batch that fills the chip that way: no speculation, no lane table).  A symbol step written
+// with selects -- which table, which component's DC sum, is the lane alive, did the block end, did a segment start --
+// spends most of its ~90 instructions on them, and a kernel of such steps is bound by VALU issue.  Here the step is
 // arithmetic on a state chosen for it, under half as many instructions:
 //   * bit position: t = bits consumed - 1.  The window's two words are read from the lane's ring at (t >> 5) (slot 16
 //     mirrors slot 0, so the pair is one ds_read2) and the next 32 bits are alignbit(hi, lo, ~t): no window registers
@@ -762,8 +404,8 @@ struct FastState {
 // LDS by byte address: the kernel's dynamic LDS is all the LDS it has, so it starts at 0 (checked on entry) and the
 // addresses the walk computes go to the instruction as they are
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
-__device__ __forceinline__ uint32_t lds_load(uint32_t a) { return *(const lds_u32*)(uintptr_t)a; }
-__device__ __forceinline__ void lds_store(uint32_t a, uint32_t v) { *(lds_u32*)(uintptr_t)a = v; }
+__device__ __forceinline__ uint32_t lds_get(uint32_t a) { return *(const lds_u32*)(uintptr_t)a; }
+__device__ __forceinline__ void lds_put(uint32_t a, uint32_t v) { *(lds_u32*)(uintptr_t)a = v; }
 // (x << 3) + y in one instruction (left alone the compiler forms the shift, an AND and an add)
 __device__ __forceinline__ uint32_t shl3_add(uint32_t x, uint32_t y) {
     uint32_t d;
@@ -820,16 +462,16 @@ __device__ __forceinline__ void fast_service_paced(Stream& s, uint32_t w, bool a
 // the next 32 bits
 __device__ __forceinline__ uint32_t fast_window(uint32_t ringb, uint32_t t) {
     const uint32_t ra = shl3_add(t & 0x1e0u, ringb);
-    return __builtin_amdgcn_alignbit(lds_load(ra), lds_load(ra + kSlot), ~t);
+    return __builtin_amdgcn_alignbit(lds_get(ra), lds_get(ra + kSlot), ~t);
 }
 
 // the entry they select: m1 at the region's start, m2 kFastM2Word words in, both read, OR-ed
 __device__ __forceinline__ uint32_t fast_lookup(const FastState& s, uint32_t v) {
     // chroma (j = 0, 1) -> + one region; AC -> + two
     const uint32_t toff = (((3u * kFastRegion) >> s.j) & kFastRegion) | (~s.dc & (2u * kFastRegion));
-    const uint32_t e1 = lds_load(((v >> 21) & 0x7fcu) | toff);
+    const uint32_t e1 = lds_get(((v >> 21) & 0x7fcu) | toff);
     const uint32_t x2 = max(v >> 16, kFastLongFirst - 1u);
-    const uint32_t e2 = lds_load((x2 << 2) + (toff + (kFastM2Word * 4u - 4u * (kFastLongFirst - 1u))));
+    const uint32_t e2 = lds_get((x2 << 2) + (toff + (kFastM2Word * 4u - 4u * (kFastLongFirst - 1u))));
     return e1 | e2;
 }
 
@@ -843,7 +485,7 @@ __device__ __forceinline__ void fast_stride(uint32_t ringb, uint32_t stageb, uin
     for (int it = 0; it < kStrideWrite; ++it) {
         // issued together, ahead of the table look-up: the component's DC sum (j = 1 Cb, j = 0 Cr, else Y) and the window
         const uint32_t ca = (((2u * kSlot) >> s.j) & (3u * kSlot)) | sumb;
-        const uint32_t sum = lds_load(ca);
+        const uint32_t sum = lds_get(ca);
         const uint32_t v = fast_window(ringb, s.t);
         __builtin_amdgcn_sched_barrier(0);   // (left alone, the scheduler sinks the sum's read behind the look-up and waits twice)
         uint32_t run = (uint32_t)((int32_t)s.togo6 >> 31);   // 0 once the frame's last block is done
@@ -862,9 +504,9 @@ __device__ __forceinline__ void fast_stride(uint32_t ringb, uint32_t stageb, uin
         uint32_t dcn = (uint32_t)__builtin_amdgcn_sbfe((int)kn, 6u, 1u);   // ~0: the block ends with this symbol
         asm("" : "+v"(dcn));   // (knowing where it comes from, the compiler builds kn & ~dcn from a shift, a compare and a select)
         // DC difference (:945-951) joins its component's sum (:1200-1221)
-        lds_store(ca, sum + (val & s.dc));
+        lds_put(ca, sum + (val & s.dc));
         const uint32_t rv = val + (sum & s.dc);
-        lds_store((s.rp8 & ((2u * kFlush - 1u) << 8)) | stageb, (rv << 16) | (s.togo6 & 0xfc0u) | (kn - 1u));
+        lds_put((s.rp8 & ((2u * kFlush - 1u) << 8)) | stageb, (rv << 16) | (s.togo6 & 0xfc0u) | (kn - 1u));
         s.rp8 += e & kFastEmit;
         s.k = kn & ~dcn;
         s.togo6 += kn & 64u;
@@ -961,7 +603,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
         for (uint32_t i = threadIdx.x; i < kFastTableBytes / 16u; i += blockDim.x) dst[i] = src[i];
     }
     __syncthreads();   // the only workgroup-wide barrier; from here the waves are on their own
-    // lds_load takes raw LDS addresses: the dynamic segment must begin at 0.  Should a toolchain ever put something in
+    // lds_get takes raw LDS addresses: the dynamic segment must begin at 0.  Should a toolchain ever put something in
     // front of it, the kernel decodes nothing and hands its frames to the serial kernel instead.
     const bool lds_at_zero = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)s_mem == 0u;
     const uint32_t stageb = kFastTableBytes + wave * fast_stage_bytes(kFlush) + lane * 4u;
@@ -996,7 +638,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
         Stream win{ws + (uint64_t)ws_line[fsafe] * 4u, live ? ((total + 15u) >> 4) * 4u : 0u, reinterpret_cast<uint32_t*>(s_mem + ringb), 0u,
                    make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
         fast_open(win);
-        for (uint32_t c = 0; c < 3u; ++c) lds_store(sumb + c * kSlot, 0u);
+        for (uint32_t c = 0; c < 3u; ++c) lds_put(sumb + c * kSlot, 0u);
 
         // a lane without a frame stands still from the start
         FastState s{0xffffffffu, 0u, 5u, live ? 0u - (blocks_per_frame << 6) : 0u, 0u, ~0u};
@@ -1098,8 +740,8 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
 }
 
 // =============================================================================================
-// Several lanes per frame, records form, in the same arithmetic (amv_huffman_sync_kernel<L, true>'s passes 1-5 with
-// fast_skip as the speculative walk and fast_stride as the strict one; the dense form keeps the kernel above).
+// Several lanes per frame, in the same arithmetic: passes 1-5 of the file's head, with fast_skip as the speculative
+// walk and fast_stride as the strict one.
 // A lane's share ends at bit `limit`: the strict walk looks at no symbol that starts there or later, so the lanes'
 // records partition the frame's; every lane's records start on a piece of kFlush of them (fillers behind its last).
 // dynamic LDS as amv_huffman_fast_kernel's.
@@ -1126,7 +768,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
         for (uint32_t i = threadIdx.x; i < kFastTableBytes / 16u; i += blockDim.x) dst[i] = src[i];
     }
     __syncthreads();   // the only workgroup-wide barrier; from here the waves are on their own
-    // lds_load takes raw LDS addresses: the dynamic segment must begin at 0.  Should a toolchain ever put something in
+    // lds_get takes raw LDS addresses: the dynamic segment must begin at 0.  Should a toolchain ever put something in
     // front of it, the kernel decodes nothing and hands its frames to the serial kernel instead.
     const bool lds_at_zero = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)s_mem == 0u;
     const uint32_t stageb = kFastTableBytes + wave * fast_stage_bytes(kFlush) + lane * 4u;
@@ -1194,7 +836,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
         // the last lane of a frame has no right neighbour to feed: its share is only walked in pass 4
         const bool walks = live && sub != L - 1;
         uint32_t my_blocks6 = 0u, my_recs8 = 0u, seeded = 0u, rounds = 0u;
-        lds_store(col_addr(lane, 19u), 0u);
+        lds_put(col_addr(lane, 19u), 0u);
         {   // round 0: every lane from its guess (lane 0: the exact state)
             FastState st{sub * S - 1u, 0u, 5u, 0u, 0u, ~0u};
             const uint32_t lim1 = walks ? (sub + 1u) * S - 1u : 0u;
@@ -1202,10 +844,10 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
             uint32_t b6, r8;
             fast_skip<skip_pace<L>()>(win, ringb, st, lim1, b6, r8);
             if (walks) {
-                lds_store(col_addr(lane, 0u), kGuess | (((st.t - lim1) | (st.k << 5) | (st.j << 11)) << 16));
-                lds_store(col_addr(lane, 1u), b6);
-                lds_store(col_addr(lane, 2u), r8);
-                lds_store(col_addr(lane, 19u), 1u);
+                lds_put(col_addr(lane, 0u), kGuess | (((st.t - lim1) | (st.k << 5) | (st.j << 11)) << 16));
+                lds_put(col_addr(lane, 1u), b6);
+                lds_put(col_addr(lane, 2u), r8);
+                lds_put(col_addr(lane, 19u), 1u);
             }
         }
         if (timing) tc[2] = clock64();
@@ -1216,12 +858,12 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
         for (int round = 0; round < L + 1; ++round) {
             wave_sync();
             // what the lane's own share and the share to its left have been walked from / arrived at, into registers
-            const uint32_t held = lds_load(col_addr(lane, 19u));
-            const uint32_t left_n = sub ? lds_load(col_addr(lane - 1u, 19u)) : 0u;
+            const uint32_t held = lds_get(col_addr(lane, 19u));
+            const uint32_t left_n = sub ? lds_get(col_addr(lane - 1u, 19u)) : 0u;
             uint32_t mine[kMemo], cand[kMemo];
 #pragma unroll
             for (uint32_t q = 0; q < kMemo; ++q) {
-                const uint32_t a = lds_load(col_addr(lane, 3u * q)), b = lds_load(col_addr(sub ? lane - 1u : lane, 3u * q));
+                const uint32_t a = lds_get(col_addr(lane, 3u * q)), b = lds_get(col_addr(sub ? lane - 1u : lane, 3u * q));
                 mine[q] = q < held ? a : kNever;                     // entry code | arrival code << 16
                 cand[q] = q < left_n ? b >> 16 : kNever;             // arrival codes at the end of the share before
             }
@@ -1265,7 +907,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
             // before that it has not walked from (newest first), then guesses with another position in the MCU
             uint32_t p = 0u;
             if (walks && front) {
-                lds_store(col_addr(lane, 15u), final_code);
+                lds_put(col_addr(lane, 15u), final_code);
                 p = 1u;
             } else if (walks && !settled) {
                 const uint32_t most = min(kMemo - min(held, kMemo), kPend);
@@ -1281,13 +923,13 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
                     if (!known && p < most) {
 #pragma unroll
                         for (uint32_t m = 0; m < kPend; ++m) if (m == p) taken[m] = c;
-                        lds_store(col_addr(lane, 15u + p), c);
+                        lds_put(col_addr(lane, 15u + p), c);
                         ++p;
                     }
                 }
                 while (seeded < 5u && p + 1u < most) {     // (one place stays free for what finality brings)
                     ++seeded;
-                    lds_store(col_addr(lane, 15u + p), (5u - seeded) << 11);
+                    lds_put(col_addr(lane, 15u + p), (5u - seeded) << 11);
                     ++p;
                 }
             }
@@ -1316,7 +958,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
             FastState st{0u, 0u, 5u, 0u, 0u, ~0u};
             uint32_t lim1 = 0u, code = 0u;
             if (work) {
-                code = lds_load(col_addr(col0 + owner, 15u + rank));
+                code = lds_get(col_addr(col0 + owner, 15u + rank));
                 lim1 = (owner + 1u) * S - 1u;
                 st.t = owner * S - 1u + (code & 31u);
                 st.k = (code >> 5) & 63u;
@@ -1328,26 +970,26 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
             if (work) {
                 const uint32_t arr = (st.t - lim1) | (st.k << 5) | (st.j << 11);
                 // the walk from a final start always lands in the memo: in its last place when the memo is full
-                uint32_t at = lds_load(col_addr(col0 + owner, 19u)) + rank;
+                uint32_t at = lds_get(col_addr(col0 + owner, 19u)) + rank;
                 if (rank == 0u && front) at = min(at, kMemo - 1u);
                 if (at < kMemo) {
-                    lds_store(col_addr(col0 + owner, 3u * at), code | (arr << 16));
-                    lds_store(col_addr(col0 + owner, 3u * at + 1u), b6);
-                    lds_store(col_addr(col0 + owner, 3u * at + 2u), r8);
+                    lds_put(col_addr(col0 + owner, 3u * at), code | (arr << 16));
+                    lds_put(col_addr(col0 + owner, 3u * at + 1u), b6);
+                    lds_put(col_addr(col0 + owner, 3u * at + 2u), r8);
                 }
             }
             wave_sync();
             if (p) {    // how many of this share's tasks found a lane: its own + the extras numbered below the idle lanes' count
                 const uint32_t done = 1u + min(extras, all_idle > ex_at ? all_idle - ex_at : 0u);
-                lds_store(col_addr(lane, 19u), min(held + done, kMemo));
+                lds_put(col_addr(lane, 19u), min(held + done, kMemo));
             }
         }
         // the final walk's counts, for EVERY lane that has one -- also when the loop ended on its bound with a frame of the
         // wave still open (that frame goes to the serial kernel below; the wave's other frames are settled, and their
         // block and record prefix sums need their counts all the same)
         if (walks && final_at != kNone) {
-            my_blocks6 = lds_load(col_addr(lane, 3u * final_at + 1u));
-            my_recs8 = lds_load(col_addr(lane, 3u * final_at + 2u));
+            my_blocks6 = lds_get(col_addr(lane, 3u * final_at + 1u));
+            my_recs8 = lds_get(col_addr(lane, 3u * final_at + 2u));
         }
         if (timing) tc[3] = clock64();
         // the state every lane starts pass 4 in: the bit offset inside the share's first word takes the code's five low bits --
@@ -1368,7 +1010,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
 
         // ---- 4. the strict, writing pass.  Lanes left of the frame's end (or first error) are exact; whatever a lane to
         // the right of it does is ignored below.
-        for (uint32_t c = 0; c < 3u; ++c) lds_store(sumb + c * kSlot, 0u);
+        for (uint32_t c = 0; c < 3u; ++c) lds_put(sumb + c * kSlot, 0u);
         FastState s = entry;
         s.togo6 = (blk0 - blocks_per_frame) << 6;
         s.rp8 = rec0 << 8;
@@ -1462,9 +1104,9 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
         // ---- 5. DC prediction: the sums of the lanes to the left are a lane's base; it goes into the frame's lane table
         // and the reader adds it
         uint32_t tot;
-        const uint32_t by = seg_excl_sum<L>(lds_load(sumb), sub, tot);
-        const uint32_t bu = seg_excl_sum<L>(lds_load(sumb + kSlot), sub, tot);
-        const uint32_t bv = seg_excl_sum<L>(lds_load(sumb + 2u * kSlot), sub, tot);
+        const uint32_t by = seg_excl_sum<L>(lds_get(sumb), sub, tot);
+        const uint32_t bu = seg_excl_sum<L>(lds_get(sumb + kSlot), sub, tot);
+        const uint32_t bv = seg_excl_sum<L>(lds_get(sumb + 2u * kSlot), sub, tot);
         if (live) {
             // lanes right of the one that met the end (or the first error) walked from states no decoder reaches
             const bool real = (int)lane <= stop_lane && blk0 < blocks_per_frame;
@@ -1510,36 +1152,6 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
 
 namespace {
 
-template <int L>
-void launch_sync(const uint32_t* ws, const uint32_t* ws_bytes, uint32_t n, const uint32_t* list,
-                 const uint32_t* list_count, const FrameGeom& g, const uint32_t* ws_line,
-                 const HuffDecodeImage* d_img, const SyncOut& out, int32_t* status, uint32_t* nmcu_ok,
-                 uint32_t* queue, unsigned long long* stats, uint32_t cus, hipStream_t s) {
-    constexpr uint32_t kMaxWaves = 10u;
-    constexpr uint32_t kPerWave = kRingWords * kWave * 4u;
-    // the attribute belongs to the device's copy of the function: once per device and instantiation
-    static std::atomic<uint64_t> raised{0};
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    const uint64_t bit = 1ull << (dev & 63);
-    if (!(raised.load(std::memory_order_relaxed) & bit)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(amv_huffman_sync_kernel<L>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kTableBytes + kMaxWaves * kPerWave));
-        raised.fetch_or(bit, std::memory_order_relaxed);
-    }
-    // Workgroups: as many as the chip holds (the rest of the tasks come from the queue); a batch that does not fill
-    // them gets smaller workgroups, so that its waves spread over all the compute units instead of filling a few.
-    const uint32_t groups = cus * 2u;
-    const uint32_t tasks = (n + (uint32_t)(kWave / L) - 1u) / (uint32_t)(kWave / L);
-    uint32_t waves = (tasks + groups - 1u) / groups;
-    if (waves < 4u) waves = 4u;
-    if (waves > kMaxWaves) waves = kMaxWaves;
-    uint32_t grid = (tasks + waves - 1u) / waves;
-    if (grid > groups) grid = groups;
-    hipLaunchKernelGGL((amv_huffman_sync_kernel<L>), dim3(grid), dim3(kWave * waves), kTableBytes + waves * kPerWave, s, ws,
-                       ws_bytes, n, list, list_count, g.blocks, ws_line, d_img, out, status, nmcu_ok, queue, stats);
-}
-
 template <uint32_t kFlush>
 void launch_fast(const uint32_t* ws, const uint32_t* ws_bytes, uint32_t n, const uint32_t* list,
                  const uint32_t* list_count, const FrameGeom& g, const uint32_t* ws_line,
@@ -1581,7 +1193,7 @@ void launch_sync2(const uint32_t* ws, const uint32_t* ws_bytes, uint32_t n, cons
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kFastTableBytes + kMaxWaves * fast_per_wave(8u)));
         raised.fetch_or(bit, std::memory_order_relaxed);
     }
-    // as launch_sync: as many workgroups as the chip holds, smaller ones for a batch that does not fill them
+    // as launch_fast: as many workgroups as the chip holds, smaller ones for a batch that does not fill them
     const uint32_t tasks = (n + (uint32_t)(kWave / L) - 1u) / (uint32_t)(kWave / L);
     uint32_t waves = (tasks + cus - 1u) / cus;
     if (waves < 4u) waves = 4u;
@@ -1603,7 +1215,7 @@ void launch_sync2(const uint32_t* ws, const uint32_t* ws_bytes, uint32_t n, cons
 // length and as many lanes as keep every task resident: 20 000: 0.67 with eight; 10 000: 0.49 with sixteen (0.52 / 0.63
 // with eight / thirty-two); 320x240: 32 000 frames 1.90 with eight (1.84 with sixteen), 8 000: 0.68 with sixteen,
 // 2 000: 0.32 with sixty-four.  `wanted` (a power of two up to 64) overrides.
-int huffman_sync_lanes(uint32_t n, uint32_t cus, int wanted, uint64_t pixels, bool records) {
+int huffman_sync_lanes(uint32_t n, uint32_t cus, int wanted, uint64_t pixels) {
     if (wanted == 1 || wanted == 2 || wanted == 4 || wanted == 8 || wanted == 16 || wanted == 32 || wanted == 64) return wanted;
     if (n >= cus * 230u) return 1;
     if (n >= cus * 150u) return 2;
@@ -1613,15 +1225,13 @@ int huffman_sync_lanes(uint32_t n, uint32_t cus, int wanted, uint64_t pixels, bo
     // 160x120, sixteen lanes / eight: 12 000 frames (3 000 tasks) 0.46 / 0.53, 14 000 (3 500 tasks) 0.58 / 0.56; 320x240:
     // 11 000 frames 0.85 / 0.99, 13 000 1.02 / 1.04, 14 000 1.11 / 1.03 -- so the table counts in generations of 13 waves per
     // unit (rounds 4 - 5 had counted ten, the workgroup the launch happened to get).
-    // (records: the records form, amv_huffman_sync2_kernel.  The dense form's kernel -- amvhip_huffman_decode_dev, nothing on the
-    // decode path -- holds ten waves per unit and was not swept: it keeps the table it had.)
-    const uint64_t resident = (uint64_t)cus * (records ? fast_waves(8u) : 10u);
+    const uint64_t resident = (uint64_t)cus * fast_waves(8u);
     // Short frames (160x120: 3.5 kB) beyond what eight lanes keep resident: two lanes.  Their launch stays one generation
     // deep up to 106 000 frames and lasts 0.80 ms from 10 000 frames to 30 000 (one task per SIMD, half a frame per lane), where
     // eight lanes in a second generation need 0.88 at 28 000 frames, 0.91 at 30 000 and 0.96 at 34 000 against 0.81 / 0.81 /
     // 0.96.  Long frames do not follow: 320x240, 32 000 frames 2.32 with two lanes against 1.86 with eight (a lane's fixed
     // cost of falling in step is a smaller part of a 14-kB frame's share, eight lanes stay efficient).
-    if (records && pixels <= 30000u && (uint64_t)n * 8u > resident * 64u) return 2;
+    if (pixels <= 30000u && (uint64_t)n * 8u > resident * 64u) return 2;
     int full = 8;                                  // chip full: 8 lanes up to 320x240 (32 000 frames: 1.90 ms against 1.84 with 16)
     while (full < 64 && (uint64_t)full * 25000u <= pixels) full *= 2;
     int fill = 8;                                  // small batch: as many lanes as keep every task resident ...
@@ -1684,29 +1294,17 @@ void launch_huffman_sync(const uint32_t* ws, const uint32_t* ws_bytes, uint32_t 
                          uint32_t* queue, unsigned long long* stats, uint32_t cus, hipStream_t s) {
     if (n == 0) return;
     const uint32_t per_row = (g.mcu_cols + kSegMcus - 1u) / kSegMcus;
-    SyncOut out{sinks.coef, sinks.rec, sinks.rec_line, sinks.seg_start, sinks.lane_tab, SegGeom{g.mcu_cols, per_row, per_row * g.mcu_rows},
+    SyncOut out{sinks.rec, sinks.rec_line, sinks.seg_start, sinks.lane_tab, SegGeom{g.mcu_cols, per_row, per_row * g.mcu_rows},
                 sinks.lanes, sinks.rec_count, sinks.retry_list, sinks.retry_count, sinks.ok_in_blocks};
 #define AMV_SYNC_ARGS ws, ws_bytes, n, list, list_count, g, ws_line, d_img, out, status, nmcu_ok, queue, stats, cus, s
-    if (sinks.rec) {
-        switch (lanes_per_frame) {
-            case 64: launch_sync2<64>(AMV_SYNC_ARGS); break;
-            case 32: launch_sync2<32>(AMV_SYNC_ARGS); break;
-            case 8: launch_sync2<8>(AMV_SYNC_ARGS); break;
-            case 4: launch_sync2<4>(AMV_SYNC_ARGS); break;
-            case 2: launch_sync2<2>(AMV_SYNC_ARGS); break;
-            case 1: launch_fast<8>(AMV_SYNC_ARGS); break;
-            default: launch_sync2<16>(AMV_SYNC_ARGS); break;
-        }
-    } else {
-        switch (lanes_per_frame) {
-            case 64: launch_sync<64>(AMV_SYNC_ARGS); break;
-            case 32: launch_sync<32>(AMV_SYNC_ARGS); break;
-            case 8: launch_sync<8>(AMV_SYNC_ARGS); break;
-            case 4: launch_sync<4>(AMV_SYNC_ARGS); break;
-            case 2: launch_sync<2>(AMV_SYNC_ARGS); break;
-            case 1: launch_sync<1>(AMV_SYNC_ARGS); break;
-            default: launch_sync<16>(AMV_SYNC_ARGS); break;
-        }
+    switch (lanes_per_frame) {
+        case 64: launch_sync2<64>(AMV_SYNC_ARGS); break;
+        case 32: launch_sync2<32>(AMV_SYNC_ARGS); break;
+        case 8: launch_sync2<8>(AMV_SYNC_ARGS); break;
+        case 4: launch_sync2<4>(AMV_SYNC_ARGS); break;
+        case 2: launch_sync2<2>(AMV_SYNC_ARGS); break;
+        case 1: launch_fast<8>(AMV_SYNC_ARGS); break;
+        default: launch_sync2<16>(AMV_SYNC_ARGS); break;
     }
 #undef AMV_SYNC_ARGS
 }

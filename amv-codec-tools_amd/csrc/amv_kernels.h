@@ -27,13 +27,13 @@ void launch_unstuff(const uint8_t* blob, uint64_t blob_bytes, const uint64_t* of
                     const uint32_t* ws_line, uint32_t* ws, uint32_t* ws_bytes, uint32_t* retry_list, uint32_t* retry_count,
                     hipStream_t s);
 // lanes per frame for a batch of n frames of `pixels` pixels on a device with `cus` compute units (amv_decode_sync.hip)
-int huffman_sync_lanes(uint32_t n, uint32_t cus, int wanted, uint64_t pixels, bool records);
+int huffman_sync_lanes(uint32_t n, uint32_t cus, int wanted, uint64_t pixels);
 // the statistics buffer of the synchronising entropy kernel (amvhip_entropy_stats / _trace): 16 words of counters, then
 // one line of eight 64-bit words per task (wave) for the first kTraceTasks tasks of a launch
 constexpr uint32_t kTraceBase = 16, kTraceTasks = 16384;
 constexpr size_t kStatsBytes = (size_t)(kTraceBase + 8u * kTraceTasks) * 8u;
-// Where the entropy stage puts its result.  rec == nullptr: dense coefficient lines in coef
-// ([n][blocks][64] int16).  Otherwise the records form, per frame: its lines of rec (one word per DC coefficient and
+// What the reconstruction reads.  rec == nullptr: the caller's dense coefficient lines in coef ([n][blocks][64] int16:
+// amvhip_reconstruct_dev).  Otherwise what the entropy stage wrote, per frame: its lines of rec (one word per DC coefficient and
 // per non-zero AC coefficient, stream order: bits 0-5 index in block (0 = DC), 6-11 (block - blocks per frame) modulo 64, bit 15 filler,
 // 16-31 value; a DC value counts from the decoding lane's first block), seg_start[segs + 1][2] = {from, to} for each
 // MCU-row segment of kSegMcus MCUs (what one wave of the reconstruction takes): the segment's first record is at or
@@ -89,6 +89,11 @@ struct FrameSel {
     uint32_t base;
     uint32_t round;   // items of this round; 0 = default launch
 };
+// records form -> dense lines coef[n][blocks][64] (amvhip_huffman_decode_dev): one wave per MCU-row segment, through the
+// reconstruction's reader (amv_block_load.h).  Frames whose rec_count is ~0 are left alone (the serial kernel writes them);
+// lines of blocks at or after a frame's first error are zeros.
+void launch_expand_records(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameGeom& g, int16_t* coef,
+                           hipStream_t s);
 // dequantise + IDCT + YCbCr->BGR + flipped store: one wave per MCU-row segment
 // sinks.rec == nullptr: every frame is dense in sinks.coef; otherwise per frame as rec_count says
 void launch_reconstruct(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameSel& sel, uint32_t items,

@@ -310,4 +310,44 @@ void launch_reconstruct(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_
     else launch_rows<kRowsPerGroup>(sinks, nmcu_ok, n, sel, items, g, flags, out, s);
 }
 
+// Records -> dense lines (amvhip_huffman_decode_dev, not on the decode path): stage A of the kernel above for one
+// (frame, MCU-row segment) per wave, then every lane with a block stores it as the block's 128-byte line.  The waves
+// walk a flat list of (frame, segment) pairs.
+__global__ __launch_bounds__(kWave * 4) void amv_expand_records_kernel(SyncSinks in, const uint32_t* __restrict__ nmcu_ok, uint32_t n,
+                                                                        FrameGeom g, uint32_t nseg, int16_t* __restrict__ coef) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_img[4][kSegImageBytes + 128];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t segs = g.mcu_rows * nseg;
+    const uint64_t pairs = (uint64_t)n * segs;
+    for (uint64_t p = (uint64_t)blockIdx.x * 4u + wave; p < pairs; p += (uint64_t)gridDim.x * 4u) {
+        const uint32_t f = (uint32_t)(p / segs), segidx = (uint32_t)(p % segs);
+        const uint32_t m0 = (segidx % nseg) * kSegMcus;
+        const uint32_t cnt = min((uint32_t)kSegMcus, g.mcu_cols - m0);
+        const uint32_t mcu0 = (segidx / nseg) * g.mcu_cols + m0;
+        const uint32_t ok = nmcu_ok[f];
+        uint32_t c[32];
+        bool skip;   // (a frame the serial kernel decodes: its lines are that kernel's)
+        if (load_segment_blocks(in, f, f, false, g, segidx, segs, mcu0, cnt, ok, lane, s_img[wave], c, skip)) {
+            const uint32_t blk = mcu0 * 6u + lane;
+            if (blk >= (in.ok_in_blocks ? ok : ok * 6u)) {   // at or after the first error: no records, but the DC base was added
+#pragma unroll
+                for (int i = 0; i < 32; ++i) c[i] = 0u;
+            }
+            uint4* d = reinterpret_cast<uint4*>(coef + ((uint64_t)f * g.blocks + blk) * 64u);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) d[i] = make_uint4(c[4 * i], c[4 * i + 1], c[4 * i + 2], c[4 * i + 3]);
+        }
+        seg_sync();   // every lane has read the image
+    }
+}
+
+void launch_expand_records(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameGeom& g, int16_t* coef,
+                           hipStream_t s) {
+    const uint32_t nseg = (g.mcu_cols + kSegMcus - 1) / kSegMcus;
+    const uint64_t groups = ((uint64_t)n * g.mcu_rows * nseg + 3u) / 4u;
+    if (groups == 0) return;
+    hipLaunchKernelGGL(amv_expand_records_kernel, dim3(groups < 65536u ? (uint32_t)groups : 65536u), dim3(kWave * 4), 0, s, sinks,
+                       nmcu_ok, n, g, nseg, coef);
+}
+
 }  // namespace amv

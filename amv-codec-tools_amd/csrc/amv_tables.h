@@ -100,7 +100,8 @@ static constexpr int16_t kSinQ14[65] = {
 static constexpr int kLut1Bits = 9;
 static constexpr int kLut2Bits = 7;
 static constexpr int kLut2Pages = 16;
-// m1/m2 are the same codes in the form the synchronising kernel wants (amv_decode_sync.hip):
+// m1/m2 are the same codes in the form of the select-based synchronising walks, which no kernel has any longer (fast[] below
+// replaced them; m1/m2 stay only so that fast[] keeps its offset in the image):
 // bits 0-4 code length + magnitude bits (0 = no such code), bits 5-10 how far the coefficient index
 // moves (run + 1; 1 for a DC symbol; 63 for end-of-block), bits 11-14 magnitude bits, m1 bit 15 "the
 // code is longer than 9 bits".  Long codes occupy the top prefixes of every table (at most the last 5 of

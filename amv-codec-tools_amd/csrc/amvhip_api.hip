@@ -154,7 +154,7 @@ void build_images(HuffDecodeImage& dec, HuffEncodeImage& enc) {
         }
     }
     if (pages > kLut2Pages) abort();  // static property of the K.3 tables (11 pages)
-    // the synchronising kernel's form of the same tables
+    // the select-based walks' form of the same tables (unread: amv_tables.h)
     auto merged = [](uint16_t e, int t) -> uint16_t {
         const uint32_t len = (e >> 8) & 31u, sym = e & 0xffu, size = sym & 15u;
         if (len == 0) return 0;
@@ -366,17 +366,16 @@ struct Fallback {
     uint32_t items;
 };
 
-// unstuffing + the synchronising kernel into `sinks` (dense when sinks.rec == nullptr, records otherwise); fb says
-// what is left for the serial kernel
-// lanes: lanes per frame of the synchronising kernel; heavy_lanes != 0 (records form, a batch that gets ONE lane per frame):
+// unstuffing + the synchronising kernel into the records of `sinks`; fb says what is left for the serial kernel
+// lanes: lanes per frame of the synchronising kernel; heavy_lanes != 0 (a batch that gets ONE lane per frame):
 // frames whose chunk is over twice the batch's mean get that many lanes instead -- a wave's 64 frames finish together, and one
 // noise frame among 63 quiet ones kept them all waiting for six times their own length (a stream with every 16th frame noise
 // spent 4.3 ms per 160 000 frames in the entropy kernel for 1.3 times the uniform stream's symbols).  The split is made on the
 // device (the lengths are there): two frame lists, two launches that take their frames from them.
 static int entropy_front(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
                          const uint32_t* d_lens, uint32_t n, const FrameGeom& g, SyncSinks sinks, int32_t* d_status,
-                         uint32_t* d_nmcu_ok, DevBuf& retry, hipStream_t st, Fallback& fb, int lanes, int heavy_lanes = 0,
-                         const LayoutSpec& rec_layout = LayoutSpec{0u, 0u, 0u, 0u, 0u, nullptr}) {
+                         uint32_t* d_nmcu_ok, DevBuf& retry, hipStream_t st, Fallback& fb, int lanes, int heavy_lanes,
+                         const LayoutSpec& rec_layout) {
     // Window per frame for the unstuffed scan in the global workspace: the frame's own chunk length + the zeroed tail of its
     // last 16-byte piece + a piece of slack, in 16-byte pieces laid out on the device (round 4; 5/16 byte per pixel for every
     // frame before: a chunk over 1.6x the usual size went to the serial kernel, the others used 60 % of their window).  The
@@ -385,7 +384,7 @@ static int entropy_front(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_byt
     uint64_t ws_lines = (blob_bytes + (uint64_t)n * 48u) / 16u + 4u;
     if (ws_lines > 0xffffffffull) ws_lines = 0xffffffffull;
     if (c->entropy_mode == AMVHIP_ENTROPY_SERIAL || g.blocks >= 16384u) {
-        if (sinks.rec) HIP_TRY(c, hipMemsetAsync(sinks.rec_count, 0xff, (size_t)n * 4, st));   // every frame dense
+        HIP_TRY(c, hipMemsetAsync(sinks.rec_count, 0xff, (size_t)n * 4, st));   // every frame dense
         fb = Fallback{nullptr, nullptr, n};
         c->last_split = false;
         return AMVHIP_OK;
@@ -410,8 +409,8 @@ static int entropy_front(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_byt
     }
     if (int r = check_launch(c, "unstuff")) return r;
     unsigned long long* stats = c->want_stats ? (unsigned long long*)c->stats.p : nullptr;
-    c->last_split = heavy_lanes && sinks.rec;
-    if (heavy_lanes && sinks.rec) {
+    c->last_split = heavy_lanes != 0;
+    if (heavy_lanes) {
         if (int r = ensure(c, c->split, ((size_t)n * 2 + 8) * 4)) return r;   // [heavy count, light count, 6 spare | heavy list n | light list n]
         uint32_t* split_count = (uint32_t*)c->split.p;
         uint32_t *heavy = split_count + 8, *light = heavy + n;
@@ -432,32 +431,6 @@ static int entropy_front(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_byt
     }
     fb = Fallback{retry_list, retry_count, n};
     return check_launch(c, "huffman_sync");
-}
-
-extern "C" int amvhip_huffman_decode_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes,
-                                         const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n,
-                                         uint32_t w, uint32_t h, int16_t* d_coef, int32_t* d_status,
-                                         uint32_t* d_nmcu_ok, void* stream) {
-    if (!c) return AMVHIP_ERR_ARG;
-    if (!size_ok(w, h) || (n && (!d_blob || !d_offs || !d_lens || !d_coef || !d_status || !d_nmcu_ok)))
-        return fail(c, AMVHIP_ERR_ARG, "huffman_decode: bad argument");
-    if (((uintptr_t)d_blob & 3u) || ((uintptr_t)d_coef & 15u)) return fail(c, AMVHIP_ERR_ARG, "huffman_decode: blob must be 4-byte, coef 16-byte aligned");
-    if (int r = use_device(c)) return r;
-    if (n == 0) return AMVHIP_OK;
-    std::lock_guard<std::mutex> lk(c->mu);
-    const FrameGeom g = make_geom(w, h);
-    hipStream_t st = (hipStream_t)stream;
-    SyncSinks sinks{d_coef, nullptr, 0u, nullptr, nullptr, 0u, nullptr, nullptr, nullptr};
-    Fallback fb;
-    if (int r = entropy_front(c, d_blob, blob_bytes, d_offs, d_lens, n, g, sinks, d_status, d_nmcu_ok, c->retry, st, fb,
-                              huffman_sync_lanes(n, c->cus, c->sync_lanes, (uint64_t)g.width * g.height, false)))
-        return r;
-    {   // the caller's array has a place for every frame: one launch, lines at the frames' own places
-        Timed t(c, AMVHIP_K_HUFFMAN_SERIAL, st);
-        launch_huffman(d_blob, blob_bytes, d_offs, d_lens, n, g, c->d_dec, d_coef, d_status, d_nmcu_ok, fb.list, fb.count, 0u,
-                       fb.items, false, false, st);
-    }
-    return check_launch(c, "huffman");
 }
 
 static int reconstruct_launch(amvhip_ctx* c, const SyncSinks& sinks, const uint32_t* d_nmcu_ok, uint32_t n, const FrameSel& sel,
@@ -501,11 +474,6 @@ extern "C" int amvhip_reconstruct_dev(amvhip_ctx* c, const int16_t* d_coef, cons
 // small is latency-bound -- three rounds cost the 10 000-frame stream 3 % of its step)
 static uint32_t dense_round(uint32_t n) { return n <= 16384u ? n : (n / 4u > 16384u ? (n + 3u) / 4u : 16384u); }
 
-// What one decode call hands from the entropy stage to the reconstruction (the context has two such sets).
-struct DecodeBufs {
-    DevBuf &nmcu, &retry, &rec, &rec_line, &seg_start, &lane_tab, &rec_count;
-};
-
 static int decode_args_ok(amvhip_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n, uint32_t w,
                           uint32_t h, uint32_t flags, const uint8_t* d_out, const int32_t* d_status) {
     if (!size_ok(w, h)) return fail(c, AMVHIP_ERR_ARG, "decode: bad size %ux%u", w, h);
@@ -517,12 +485,17 @@ static int decode_args_ok(amvhip_ctx* c, const uint8_t* d_blob, const uint64_t* 
     return AMVHIP_OK;
 }
 
-// The entropy stage goes to stream `front`, everything that writes d_out to `back` (the same stream, or two of the
-// context's own with `back` waiting for `front`).  Caller holds the lock.
-static int decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
-                       uint32_t n, uint32_t w, uint32_t h, uint32_t flags, uint8_t* d_out, int32_t* d_status, DecodeBufs b,
-                       hipStream_t front, hipStream_t back) {
-    const FrameGeom g = make_geom(w, h);
+// What one decode call hands from the entropy stage to the reconstruction (the context has two such sets).
+struct DecodeBufs {
+    DevBuf &nmcu, &retry, &rec, &rec_line, &seg_start, &lane_tab, &rec_count;
+};
+
+// The entropy stage of a decode call into the hand-over set b: sizes the record space, the segment bounds, the lane table
+// and the record counts, then runs entropy_front.  Statuses and nmcu_ok go to d_status / d_nmcu_ok (ok_in_blocks: nmcu_ok
+// counts whole blocks, AMVHIP_FLAG_FFMPEG_KEEP).  sinks: where the records are; its coef is left null.
+static int entropy_records(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
+                           uint32_t n, const FrameGeom& g, bool ok_in_blocks, int32_t* d_status, uint32_t* d_nmcu_ok, DecodeBufs b,
+                           hipStream_t st, SyncSinks& sinks, Fallback& fb) {
     // Between the two stages coefficients travel as records (one word per DC and per non-zero AC coefficient), every frame
     // in space of its own, sized from ITS chunk (round 4; one stride for all, from the batch's mean chunk, before: a heavy
     // frame in a light stream was silently decoded by the one-lane serial kernel).  A record costs at least 3 bits of scan,
@@ -540,12 +513,63 @@ static int decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes
         if (by_stream < cap_lines) cap_lines = by_stream;
         if (cap_lines > 0xffffffffull) cap_lines = 0xffffffffull;
     }
-    const uint32_t lanes = (uint32_t)huffman_sync_lanes(n, c->cus, c->sync_lanes, (uint64_t)g.width * g.height, true);
+    const uint32_t lanes = (uint32_t)huffman_sync_lanes(n, c->cus, c->sync_lanes, (uint64_t)g.width * g.height);
     // a batch that gets one lane per frame gives its heavy frames kHeavyLanes (entropy_front); AMVHIP_SPLIT=0: every frame one
     const uint32_t heavy_lanes = lanes == 1u && c->split_heavy ? c->heavy_lanes : 0u;
     const uint32_t tab_lanes = heavy_lanes ? heavy_lanes : lanes;       // a frame's row in lane_tab
     const uint32_t segs = ((g.mcu_cols + 9u) / 10u) * g.mcu_rows;
-    // dense lines for a round of fall-back frames: by count (above), and never more than 2 GB of them -- at 640x480 a
+    if (int r = ensure(c, b.rec, (size_t)cap_lines * 128 + 16)) return r;   // + what a 16-byte read of a frame's last records may overshoot
+    if (int r = ensure(c, b.rec_line, ((size_t)n + 1) * 4)) return r;
+    const LayoutSpec rec_layout{4u, add_rec, hi_rec, 5u, (uint32_t)cap_lines, (uint32_t*)b.rec_line.p};   // laid out by entropy_front's launch
+    if (int r = ensure(c, b.seg_start, (size_t)n * (segs + 1) * 8)) return r;
+    if (int r = ensure(c, b.lane_tab, (size_t)n * tab_lanes * 16)) return r;
+    if (int r = ensure(c, b.rec_count, (size_t)n * 4)) return r;
+    sinks = SyncSinks{nullptr, (uint32_t*)b.rec.p, (const uint32_t*)b.rec_line.p, (uint32_t*)b.seg_start.p, (uint32_t*)b.lane_tab.p, tab_lanes,
+                      (uint32_t*)b.rec_count.p, nullptr, nullptr};
+    sinks.ok_in_blocks = ok_in_blocks ? 1u : 0u;
+    c->last_decode_retry = &b.retry;
+    return entropy_front(c, d_blob, blob_bytes, d_offs, d_lens, n, g, sinks, d_status, d_nmcu_ok, b.retry, st, fb, (int)lanes, (int)heavy_lanes,
+                         rec_layout);
+}
+
+extern "C" int amvhip_huffman_decode_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes,
+                                         const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n,
+                                         uint32_t w, uint32_t h, int16_t* d_coef, int32_t* d_status,
+                                         uint32_t* d_nmcu_ok, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!size_ok(w, h) || (n && (!d_blob || !d_offs || !d_lens || !d_coef || !d_status || !d_nmcu_ok)))
+        return fail(c, AMVHIP_ERR_ARG, "huffman_decode: bad argument");
+    if (((uintptr_t)d_blob & 3u) || ((uintptr_t)d_coef & 15u)) return fail(c, AMVHIP_ERR_ARG, "huffman_decode: blob must be 4-byte, coef 16-byte aligned");
+    if (int r = use_device(c)) return r;
+    if (n == 0) return AMVHIP_OK;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const FrameGeom g = make_geom(w, h);
+    hipStream_t st = (hipStream_t)stream;
+    // the entropy stage of amvhip_decode_batch_dev, into its hand-over set; the records become the caller's lines
+    SyncSinks sinks;
+    Fallback fb;
+    if (int r = entropy_records(c, d_blob, blob_bytes, d_offs, d_lens, n, g, false, d_status, d_nmcu_ok,
+                                DecodeBufs{c->nmcu, c->retry, c->rec, c->rec_line, c->seg_start, c->lane_tab, c->rec_count}, st, sinks, fb))
+        return r;
+    if (fb.list) {   // (without a list every frame is the serial kernel's)
+        launch_expand_records(sinks, d_nmcu_ok, n, g, d_coef, st);
+        if (int r = check_launch(c, "expand_records")) return r;
+    }
+    {   // the caller's array has a place for every frame: one launch, lines at the frames' own places
+        Timed t(c, AMVHIP_K_HUFFMAN_SERIAL, st);
+        launch_huffman(d_blob, blob_bytes, d_offs, d_lens, n, g, c->d_dec, d_coef, d_status, d_nmcu_ok, fb.list, fb.count, 0u,
+                       fb.items, false, false, st);
+    }
+    return check_launch(c, "huffman");
+}
+
+// The entropy stage goes to stream `front`, everything that writes d_out to `back` (the same stream, or two of the
+// context's own with `back` waiting for `front`).  Caller holds the lock.
+static int decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
+                       uint32_t n, uint32_t w, uint32_t h, uint32_t flags, uint8_t* d_out, int32_t* d_status, DecodeBufs b,
+                       hipStream_t front, hipStream_t back) {
+    const FrameGeom g = make_geom(w, h);
+    // dense lines for a round of fall-back frames: by count (dense_round), and never more than 2 GB of them -- at 640x480 a
     // block line is 128 bytes x 7 200 blocks, and 16 384 frames of that would be 15 GB kept for rounds that usually find nothing
     uint32_t round = dense_round(n);
     {
@@ -555,21 +579,14 @@ static int decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes
     }
     if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
     if (int r = ensure(c, b.nmcu, (size_t)n * 4)) return r;
-    if (int r = ensure(c, b.rec, (size_t)cap_lines * 128 + 16)) return r;   // + what a 16-byte read of a frame's last records may overshoot
-    if (int r = ensure(c, b.rec_line, ((size_t)n + 1) * 4)) return r;
-    const LayoutSpec rec_layout{4u, add_rec, hi_rec, 5u, (uint32_t)cap_lines, (uint32_t*)b.rec_line.p};   // laid out by entropy_front's launch
-    if (int r = ensure(c, b.seg_start, (size_t)n * (segs + 1) * 8)) return r;
-    if (int r = ensure(c, b.lane_tab, (size_t)n * tab_lanes * 16)) return r;
-    if (int r = ensure(c, b.rec_count, (size_t)n * 4)) return r;
-    SyncSinks sinks{(int16_t*)c->coef.p, (uint32_t*)b.rec.p, (const uint32_t*)b.rec_line.p, (uint32_t*)b.seg_start.p, (uint32_t*)b.lane_tab.p, tab_lanes,
-                    (uint32_t*)b.rec_count.p, nullptr, nullptr};
-    sinks.ok_in_blocks = (flags & AMVHIP_FLAG_FFMPEG_KEEP) ? 1u : 0u;   // b.nmcu is the context's own array: whole blocks, not whole MCUs
     uint32_t* d_nmcu = (uint32_t*)b.nmcu.p;
-    c->last_decode_retry = &b.retry;
+    // AMVHIP_FLAG_FFMPEG_KEEP: b.nmcu is the context's own array, so it may count whole blocks, not whole MCUs
+    SyncSinks sinks;
     Fallback fb;
-    if (int r = entropy_front(c, d_blob, blob_bytes, d_offs, d_lens, n, g, sinks, d_status, d_nmcu, b.retry, front, fb, (int)lanes, (int)heavy_lanes,
-                              rec_layout))
+    if (int r = entropy_records(c, d_blob, blob_bytes, d_offs, d_lens, n, g, (flags & AMVHIP_FLAG_FFMPEG_KEEP) != 0, d_status, d_nmcu, b, front,
+                                sinks, fb))
         return r;
+    sinks.coef = (int16_t*)c->coef.p;
     if (back != front) {
         HIP_TRY(c, hipEventRecord(c->ev_front, front));
         HIP_TRY(c, hipStreamWaitEvent(back, c->ev_front, 0));
@@ -1418,7 +1435,7 @@ extern "C" uint32_t amvhip_jpeg_header(uint16_t height, uint16_t width, uint8_t*
 
 extern "C" const char* amvhip_kernel_name(int kernel) {
     switch (kernel) {
-        case AMVHIP_K_HUFFMAN: return "amv_huffman_fast_kernel|sync2|sync";   // whichever the batch got (huffman_sync_lanes; dense form: sync)
+        case AMVHIP_K_HUFFMAN: return "amv_huffman_fast_kernel|sync2|sync";   // whichever the batch got (huffman_sync_lanes); a key of bench lines and profiles, kept as it was
         case AMVHIP_K_UNSTUFF: return "amv_unstuff_kernel";
         case AMVHIP_K_HUFFMAN_SERIAL: return "amv_huffman_kernel";
         case AMVHIP_K_RECON: return "amv_reconstruct_kernel";

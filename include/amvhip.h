@@ -308,9 +308,11 @@ int amvhip_entropy_trace(amvhip_ctx *ctx, uint64_t *out, uint32_t tasks);
  * No analogue in the reference (its decoder takes one frame at a time, AMVDec.c:259). */
 int amvhip_decode_split_stats(amvhip_ctx *ctx, uint32_t out[2]);
 
-/* Stage access for parity tests: entropy stage only.  d_coef: n * nmcu*6*64 int16,
- * DC-predicted quantised coefficients in bitstream order (amvlib MCUBuffer,
- * AmvJpeg.c:1200-1223); d_nmcu_ok: MCUs decoded before the first error. */
+/* Stage access for parity tests: entropy stage only, the same kernels amvhip_decode_batch_dev runs.  d_coef: n * nmcu*6*64
+ * int16, DC-predicted quantised coefficients in bitstream order (amvlib MCUBuffer, AmvJpeg.c:1200-1223); d_nmcu_ok: MCUs
+ * decoded before the first error.  Every line of every frame is written.  Lines of MCUs before d_nmcu_ok[i] are the
+ * decoder's; lines at or after it are unspecified (frames that go through the serial kernel keep the failing block's
+ * partial values there, the others zeros).  Nothing reads them: amvhip_reconstruct_dev stops at d_nmcu_ok[i]. */
 int amvhip_huffman_decode_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes,
                               const uint64_t *d_offs, const uint32_t *d_lens, uint32_t n,
                               uint32_t width, uint32_t height,

@@ -177,6 +177,85 @@ def test_huffman_stage_matches_oracle(ctx, orc):
         assert (coef[i] == want).all(), i
 
 
+def test_huffman_stage_every_entropy_kernel(pkg, orc):
+    """The stage accessor runs the decode path's entropy kernels.  Contexts whose batches get the lane count of their
+    size, one lane per frame (the noise frames split off to several lanes each), 2, 16 and 64 lanes, and
+    AMVHIP_ENTROPY_SERIAL; a batch of clean frames, damaged ones (flipped bits, some cut short inside an MCU), noise frames
+    and frames the unstuffer hands to the serial kernel (a run of FF bytes past its look-back, as in
+    test_decode_fallback_rounds).  Statuses and nmcu_ok equal the oracle's, so do the lines of every MCU before nmcu_ok,
+    and a clean frame's lines everywhere."""
+    import os
+    import torch
+    w, h = 160, 120
+    rng = np.random.default_rng(2718)
+    clean = _synth_chunks(orc, 24, w, h, first=300)
+    chunks = list(clean)
+    for i, c in enumerate(clean[:18]):
+        b = bytearray(c)
+        for _ in range(3):
+            b[int(rng.integers(8, len(b) - 4))] ^= 1 << int(rng.integers(0, 8))
+        if i % 2:
+            b = b[: int(rng.integers(40, len(b) - 2))]
+        chunks.append(bytes(b))
+    noise = [orc.encode_frame(rng.integers(0, 256, (h, w, 3), dtype=np.uint8), w, h) for _ in range(3)]
+    chunks += noise
+    for i in range(9):
+        c = clean[i]
+        if i % 9 < 5:
+            cut = 10 + (i % 17)
+            c = c[:cut] + b"\xff" * 40 + c[cut:]
+        chunks.append(c)
+    order = rng.permutation(len(chunks))
+    chunks = [chunks[int(k)] for k in order]
+    is_clean = np.array([c in clean or c in noise for c in chunks])
+    n, nblk = len(chunks), orc.nmcu(w, h) * 6
+    want = [orc.decode_frame(c, w, h, 0, want_coef=True) for c in chunks]
+    want_st = np.array([x[1] for x in want], np.int32)
+    want_ok = np.array([x[2] for x in want], np.int32)
+    assert (want_st[~is_clean] != 0).sum() >= 10 and (want_st[is_clean] == 0).all()
+    blob, offs, lens, nbytes = _blob_of(chunks, 2)
+
+    keep = {k: os.environ.get(k) for k in ("AMVHIP_SYNC_LANES",)}
+    ctxs = {}
+    try:
+        for lanes in (None, "1", "2", "16", "64"):
+            if lanes is None:
+                os.environ.pop("AMVHIP_SYNC_LANES", None)
+            else:
+                os.environ["AMVHIP_SYNC_LANES"] = lanes
+            ctxs[lanes] = pkg.Context(0)
+    finally:
+        for k, v in keep.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+    try:
+        for key, c in [(k, c) for k, c in ctxs.items()] + [("serial", ctxs[None])]:
+            c.set_entropy_mode(pkg.ENTROPY_SERIAL if key == "serial" else pkg.ENTROPY_AUTO)
+            d_coef = torch.full((n, nblk, 64), 77, dtype=torch.int16, device="cuda:0")
+            d_st = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
+            d_ok = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
+            c.huffman_decode_dev(_t(blob), nbytes, _t(offs), _t(lens), n, w, h, d_coef, d_st, d_ok)
+            torch.cuda.synchronize()
+            c.set_entropy_mode(pkg.ENTROPY_AUTO)
+            coef, st, ok = d_coef.cpu().numpy(), d_st.cpu().numpy(), d_ok.cpu().numpy()
+            assert (st == want_st).all(), (key, st, want_st)
+            assert (ok == want_ok).all(), (key, ok, want_ok)
+            for i in range(n):
+                upto = int(want_ok[i]) * 6
+                assert (coef[i, :upto] == want[i][3][:upto]).all(), (key, i)
+                if is_clean[i]:
+                    assert (coef[i] == want[i][3]).all(), (key, i)
+            if key != "serial":
+                assert c.entropy_stats(False)["handed_to_serial"] >= 5, key
+            if key == "1":
+                assert c.decode_split_stats()["heavy"] >= len(noise), key
+    finally:
+        for c in ctxs.values():
+            c.close()
+
+
 def test_reconstruct_stage_matches_oracle(ctx, orc):
     """dequant + IDCT + colour from arbitrary coefficients, including values no encoder produces"""
     import torch
