@@ -1055,6 +1055,16 @@ static void build_enc(hufenc *he, const uint8_t bits[16], const uint8_t *vals)
     }
 }
 
+/* the code table the encoder writes with, as data: t = 0 DC luma, 1 DC chroma, 2 AC luma, 3 AC chroma; size[sym] = 0
+ * for a symbol the table does not hold */
+void amvo_huffman_codes(int t, uint8_t size[256], uint16_t code[256])
+{
+    hufenc he;
+    build_enc(&he, k_bits[t & 3], k_vals[t & 3]);
+    memcpy(size, he.size, sizeof he.size);
+    memcpy(code, he.code, sizeof he.code);
+}
+
 typedef struct { uint8_t *buf; size_t pos; uint32_t acc; int nacc; } bitwr;
 
 static void put_bits(bitwr *bw, int n, uint32_t v)

@@ -150,6 +150,9 @@ void amvo_quantize_block(const int16_t dct[64], int comp, uint32_t qbias, int16_
 int amvo_encode_frame(const uint8_t *src, uint32_t src_stride, uint32_t w, uint32_t h, int bgr,
                       uint32_t qbias, uint8_t *out, int16_t *coef_out);
 uint32_t amvo_encode_bound(uint32_t w, uint32_t h);
+/* the encoder's Huffman code of every symbol of table t (0 DC luma, 1 DC chroma, 2 AC luma, 3 AC chroma; ff_mjpeg_build_huffman_codes,
+ * mjpeg.c:129-147): code length in size[sym] (0: no such symbol), the code in the low bits of code[sym] */
+void amvo_huffman_codes(int t, uint8_t size[256], uint16_t code[256]);
 /* the same from planes: YUVJ420P as amv_encoder takes it (mjpegenc.c:493), and YUVJ422P by the product's rule (the two chroma
  * rows over a 4:2:0 sample averaged, rounding up -- amvo_yuv422_to_420; the reference's own 4:2:2 scan has eight blocks per
  * MCU, mjpegenc.c:437-450, which no AMV decoder reads).  out: amvo_encode_bound(w,h) bytes; returns the chunk's length. */

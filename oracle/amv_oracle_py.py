@@ -93,6 +93,7 @@ def lib():
             "amvo_quantize_block": (None, [_vp, _int, _u32, _vp]),
             "amvo_encode_frame": (_int, [_vp, _u32, _u32, _u32, _int, _u32, _vp, _vp]),
             "amvo_encode_bound": (_u32, [_u32, _u32]),
+            "amvo_huffman_codes": (None, [_int, _vp, _vp]),
             "amvo_encode_frame_yuv420": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp]),
             "amvo_encode_frame_yuv422": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _vp]),
             "amvo_yuv422_to_420": (None, [_vp, _u32, _u32, _u32, _vp, _u32]),
@@ -262,6 +263,13 @@ def encode_frame(pix, w, h, bgr=False, qbias=0, want_coef=False):
     if n < 0:
         raise ValueError("amvo_encode_frame rejected %dx%d" % (w, h))
     return (bytes(buf[:n]), coef) if want_coef else bytes(buf[:n])
+
+
+def huffman_codes(t):
+    """the encoder's code table t (0 DC luma, 1 DC chroma, 2 AC luma, 3 AC chroma) -> (size[256] uint8, code[256] uint16)"""
+    size, code = np.zeros(256, np.uint8), np.zeros(256, np.uint16)
+    lib().amvo_huffman_codes(t, size.ctypes.data, code.ctypes.data)
+    return size, code
 
 
 def encode_frame_yuv(y, cb, cr, w, h, qbias=0):

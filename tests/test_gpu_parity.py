@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from conftest import SEED
+import scan_builder
 from test_oracle_pin import AMVLIB_HASH, AMVLIB_HASH_FIXED_ZZ
 
 pytestmark = pytest.mark.gpu
@@ -2128,7 +2129,8 @@ def test_mixed_stream_keeps_the_parallel_kernels(pkg, orc):
     (amvhip_entropy_stats), and every byte and status equals the oracle's.  Both parallel entropy kernels: the
     speculative lanes a small batch gets and the one-lane-per-frame kernel of a chip-filling batch (AMVHIP_SYNC_LANES=1).
     A frame's record space is two words per byte of its chunk + two per block (amvhip_api.hip: `add_rec`, `hi_rec`), never
-    more than a frame with every coefficient non-zero could fill -- white noise stays on the parallel kernels too --
+    more than a frame with every coefficient non-zero could fill -- white noise stays on the parallel kernels too, a crafted
+    scan with every coefficient non-zero does not --
     and chunks that overlap in the blob (their lengths add up to more than the blob holds) are decoded all the same."""
     import os
     import torch
@@ -2141,6 +2143,8 @@ def test_mixed_stream_keeps_the_parallel_kernels(pkg, orc):
     assert min(len(c) for c in heavy) > 8 * max(len(c) for c in light[:4])
     chunks = [(heavy[(i // 16) % 3] if i % 16 == 15 else light[i % len(light)]) for i in range(640)]
     uniq = {c: orc.decode_frame(c, w, h) for c in set(chunks)}
+    dense = next(c for c in scan_builder.corpus() if c.name == "dense_all_ac")
+    assert dense.over and (dense.w, dense.h) == (w, h)
     want = np.stack([uniq[c][0] for c in chunks])
     wst = np.array([uniq[c][1] for c in chunks], np.int32)
     assert (wst == 0).all()
@@ -2161,12 +2165,17 @@ def test_mixed_stream_keeps_the_parallel_kernels(pkg, orc):
             got, st = _gpu_decode(c, chunks, w, h)
             assert (st == wst).all() and (got == want).all()
             assert c.entropy_stats(False)["handed_to_serial"] == 0
-            # the noisiest picture there is: more records than any frame is given -> the serial kernel, same bytes
+            # the noisiest picture there is (about 12 600 records in 20 000 slots) stays on the parallel kernels; a crafted scan with
+            # every coefficient non-zero (30 720 records, 2.7 per chunk byte) is more than its record space holds -> the serial
+            # kernel, and nothing of it lands in the frames around it
             loud = orc.encode_frame(rng.integers(0, 256, (h, w, 3)).astype(np.uint8), w, h)
-            mix = chunks[:40] + [loud] + chunks[40:80]
-            got, st = _gpu_decode(c, mix, w, h)
+            mix = chunks[:40] + [loud, dense.chunk] + chunks[40:80]
+            got, st = _gpu_decode(c, mix, w, h, pad_front=1)
+            assert c.entropy_stats(False)["handed_to_serial"] == 1
             ref, rst, _ = orc.decode_frame(loud, w, h)
-            assert (got[40] == ref).all() and st[40] == rst and (got[:40] == want[:40]).all() and (got[41:] == want[40:80]).all()
+            dref, drst, _ = orc.decode_frame(dense.chunk, w, h)
+            assert (got[40] == ref).all() and st[40] == rst and (got[:40] == want[:40]).all() and (got[42:] == want[40:80]).all()
+            assert (got[41] == dref).all() and st[41] == drst == 0
             # every frame the SAME chunk of the blob: the lengths add up to 300 times what the blob holds
             one = heavy[0]
             blob = np.frombuffer(one + b"\0" * 16, np.uint8).copy()

@@ -312,6 +312,8 @@ def test_huffman_tables_match_reference_build(orc):
         code = np.zeros(256, np.uint16)
         R.amvref_mjpeg_huffman_codes(t, size.ctypes.data, code.ctypes.data)
         assert int((size > 0).sum()) == n and size.max() <= 16
+        mine_size, mine_code = orc.huffman_codes(t)          # the oracle encoder's table, as data
+        assert (mine_size == size).all() and (mine_code[size > 0] == code[size > 0]).all(), t
         # Kraft sum of a complete-but-one prefix code (JPEG reserves the all-ones code)
         assert sum(2.0 ** -int(s) for s in size if s) == 1.0 - 2.0 ** -int(size.max())
 
