@@ -465,7 +465,8 @@ __device__ __forceinline__ uint32_t fast_window(uint32_t ringb, uint32_t t) {
     return __builtin_amdgcn_alignbit(lds_get(ra), lds_get(ra + kSlot), ~t);
 }
 
-// the entry they select: m1 at the region's start, m2 kFastM2Word words in, both read, OR-ed
+// the entry they select: the 9-bit-prefix half at the region's start, the long-code half kFastM2Word words in, both
+// read, OR-ed
 __device__ __forceinline__ uint32_t fast_lookup(const FastState& s, uint32_t v) {
     // chroma (j = 0, 1) -> + one region; AC -> + two
     const uint32_t toff = (((3u * kFastRegion) >> s.j) & kFastRegion) | (~s.dc & (2u * kFastRegion));

@@ -100,14 +100,6 @@ static constexpr int16_t kSinQ14[65] = {
 static constexpr int kLut1Bits = 9;
 static constexpr int kLut2Bits = 7;
 static constexpr int kLut2Pages = 16;
-// m1/m2 are the same codes in the form of the select-based synchronising walks, which no kernel has any longer (fast[] below
-// replaced them; m1/m2 stay only so that fast[] keeps its offset in the image):
-// bits 0-4 code length + magnitude bits (0 = no such code), bits 5-10 how far the coefficient index
-// moves (run + 1; 1 for a DC symbol; 63 for end-of-block), bits 11-14 magnitude bits, m1 bit 15 "the
-// code is longer than 9 bits".  Long codes occupy the top prefixes of every table (at most the last 5 of
-// the 512: they all begin with six one-bits), so m2 is indexed by the 10 bits behind those six.
-static constexpr int kLut2PagesPerTable = 5;
-static constexpr int kM2Bits = 10;
 // fast[t] is table t once more, for the one-lane-per-frame walk (amv_huffman_fast_kernel), as 32-bit entries laid out
 // so that a symbol step is arithmetic, not selects: words 0-511 are indexed by the next 9 bits; words 512-1536 by
 // max(next 16 bits, 0xfbff) - 0xfbff, i.e. word 512 (always 0) for every stream that does not begin with six one-bits
@@ -118,14 +110,12 @@ static constexpr int kM2Bits = 10;
 // index 1..63 and the sum stays clear of 65..79, an over-long run; 0 for "no such code"), byte 3 code length +
 // magnitude bits (1 for "no such code": a walk from a guessed start slips one bit there, the strict walk stops).
 static constexpr uint32_t kFastWords = 2048;          // per table: 8 KB, a power of two (the table is chosen by OR-ing address bits)
-static constexpr uint32_t kFastM2Word = 512;
+static constexpr uint32_t kFastM2Word = 512;          // the long-code half of a table starts here
 static constexpr uint32_t kFastLongFirst = 0xfc00u;   // 16-bit windows from here on begin with six one-bits
 static constexpr uint32_t kFastInvalid = 1u << 5, kFastEmit = 1u << 8, kFastEobAdvance = 192u;
 struct HuffDecodeImage {
     uint16_t l1[4][1 << kLut1Bits];
     uint16_t l2[kLut2Pages][1 << kLut2Bits];
-    uint16_t m1[4][1 << kLut1Bits];
-    uint16_t m2[4][1 << kM2Bits];
     uint32_t fast[4][kFastWords];
 };
 

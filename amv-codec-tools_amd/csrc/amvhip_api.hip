@@ -21,10 +21,22 @@ using namespace amv;
 
 namespace {
 
-// grow-only device buffer
+// grow-only device buffer (ensure), freed with its owner
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() {
+        if (p) (void)hipFree(p);
+    }
+};
+
+// What one decode call hands from the entropy stage to the reconstruction
+struct DecodeSet {
+    DevBuf nmcu, retry, rec, rec_line, seg_start, lane_tab, rec_count;
+    size_t cap() const { return nmcu.cap + retry.cap + rec.cap + rec_line.cap + seg_start.cap + lane_tab.cap + rec_count.cap; }
 };
 
 struct ProfRec {
@@ -37,13 +49,12 @@ struct ProfRec {
 struct amvhip_ctx {
     int device = 0;
     std::string err;
-    HuffDecodeImage* d_dec = nullptr;
-    HuffEncodeImage* d_enc = nullptr;
+    DevBuf d_dec, d_enc;   // HuffDecodeImage, HuffEncodeImage
     // workspace
-    DevBuf coef, status, nmcu, tmp, lens, offs, flag, map, start, retry, enc_retry, stats, ws, ws_line, layout, ws_bytes, rec, rec_line, seg_start, lane_tab, rec_count, scaled, trellis_ws, chain, split;
-    // amvhip_decode_submit_dev / _collect_dev: what the entropy stage hands to the reconstruction exists twice, so that
-    // the entropy stage of one batch can run (stream `front`) beside the reconstruction of the batch before (`back`)
-    struct DecodeSet { DevBuf nmcu, retry, rec, rec_line, seg_start, lane_tab, rec_count; } second;
+    DevBuf coef, tmp, flag, map, start, enc_retry, stats, ws, ws_line, layout, ws_bytes, scaled, trellis_ws, chain, split;
+    // set[0] serves every decode call but amvhip_decode_submit_dev, which takes the two in turn, so that the entropy stage
+    // of one batch can run (stream `front`) beside the reconstruction of the batch before (`back`)
+    DecodeSet set[2];
     hipStream_t front = nullptr, back = nullptr;
     hipEvent_t ev_in = nullptr, ev_front = nullptr, ev_done[2] = {nullptr, nullptr};
     uint64_t submitted = 0, collected = 0;
@@ -116,6 +127,13 @@ int ensure(amvhip_ctx* c, DevBuf& b, size_t bytes) {
     return AMVHIP_OK;
 }
 
+// grow b to at least `room` bytes and queue the copy of `bytes` from host memory into it on st
+int stage(amvhip_ctx* c, DevBuf& b, size_t room, const void* src, size_t bytes, hipStream_t st) {
+    if (int r = ensure(c, b, room)) return r;
+    HIP_TRY(c, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st));
+    return AMVHIP_OK;
+}
+
 // ---- table images ---------------------------------------------------------------------------
 
 const uint8_t* symbols_of(int t) {
@@ -154,28 +172,6 @@ void build_images(HuffDecodeImage& dec, HuffEncodeImage& enc) {
         }
     }
     if (pages > kLut2Pages) abort();  // static property of the K.3 tables (11 pages)
-    // the select-based walks' form of the same tables (unread: amv_tables.h)
-    auto merged = [](uint16_t e, int t) -> uint16_t {
-        const uint32_t len = (e >> 8) & 31u, sym = e & 0xffu, size = sym & 15u;
-        if (len == 0) return 0;
-        const uint32_t adv = t < 2 ? 1u : (sym == 0 ? 63u : (sym >> 4) + 1u);
-        return (uint16_t)((len + size) | (adv << 5) | (size << 11));
-    };
-    const int first = (1 << kLut1Bits) - kLut2PagesPerTable;
-    for (int t = 0; t < 4; ++t) {
-        for (int i = 0; i < (1 << kLut1Bits); ++i) {
-            const uint16_t e = dec.l1[t][i];
-            if (!(e & 0x8000u)) { dec.m1[t][i] = merged(e, t); continue; }
-            if (i < first) abort();   // static property of the K.3 tables: long codes live in the last 5 prefixes
-            dec.m1[t][i] = 0x8000u;
-        }
-        // m2: the 16-bit window 111111 xxxxxxxxxx -> entry of the code it starts with (0 where none does)
-        for (int x = 0; x < (1 << kM2Bits); ++x) {
-            const uint32_t w16 = 0xfc00u | (uint32_t)x;
-            const uint16_t e1 = dec.l1[t][w16 >> (16 - kLut1Bits)];
-            if (e1 & 0x8000u) dec.m2[t][x] = merged(dec.l2[e1 & 0xffu][(w16 >> (16 - kLut1Bits - kLut2Bits)) & ((1u << kLut2Bits) - 1u)], t);
-        }
-    }
     // the one-lane-per-frame walk's form (amv_tables.h)
     auto fast = [](uint16_t e, int t) -> uint32_t {
         const uint32_t len = (e >> 8) & 31u, sym = e & 0xffu, size = sym & 15u;
@@ -305,10 +301,10 @@ extern "C" int amvhip_create(amvhip_ctx** out, int device) {
             c->adpcm_sweeps = strcmp(e, "map") == 0 ? -1 : (atoi(e) < 0 ? 0 : (atoi(e) > 60 ? 60 : atoi(e)));
         }
     }
-    if (hipMalloc((void**)&c->d_dec, sizeof dec) != hipSuccess) return die(AMVHIP_ERR_NOMEM);
-    if (hipMalloc((void**)&c->d_enc, sizeof enc) != hipSuccess) return die(AMVHIP_ERR_NOMEM);
-    if (hipMemcpy(c->d_dec, &dec, sizeof dec, hipMemcpyHostToDevice) != hipSuccess) return die(AMVHIP_ERR_DEVICE);
-    if (hipMemcpy(c->d_enc, &enc, sizeof enc, hipMemcpyHostToDevice) != hipSuccess) return die(AMVHIP_ERR_DEVICE);
+    if (hipMalloc(&c->d_dec.p, sizeof dec) != hipSuccess) return die(AMVHIP_ERR_NOMEM);
+    if (hipMalloc(&c->d_enc.p, sizeof enc) != hipSuccess) return die(AMVHIP_ERR_NOMEM);
+    if (hipMemcpy(c->d_dec.p, &dec, sizeof dec, hipMemcpyHostToDevice) != hipSuccess) return die(AMVHIP_ERR_DEVICE);
+    if (hipMemcpy(c->d_enc.p, &enc, sizeof enc, hipMemcpyHostToDevice) != hipSuccess) return die(AMVHIP_ERR_DEVICE);
     *out = c;
     return AMVHIP_OK;
 }
@@ -322,19 +318,11 @@ extern "C" void amvhip_destroy(amvhip_ctx* c) {
     if (c->dstream) { (void)hipStreamSynchronize(c->dstream); (void)hipStreamDestroy(c->dstream); }
     for (hipEvent_t e : {c->ev_decoded, c->ev_copied[0], c->ev_copied[1]})
         if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&c->v_out[0], &c->v_out[1], &c->v_status[0], &c->v_status[1]})
-        if (b->p) (void)hipFree(b->p);
     for (hipStream_t q : {c->front, c->back})
         if (q) { (void)hipStreamSynchronize(q); (void)hipStreamDestroy(q); }
     for (hipEvent_t e : {c->ev_in, c->ev_front, c->ev_done[0], c->ev_done[1]})
         if (e) (void)hipEventDestroy(e);
-    for (DevBuf* b : {&c->coef, &c->status, &c->nmcu, &c->tmp, &c->lens, &c->offs, &c->flag, &c->map,
-                      &c->start, &c->retry, &c->enc_retry, &c->stats, &c->ws, &c->ws_line, &c->layout, &c->ws_bytes, &c->rec, &c->rec_line, &c->seg_start, &c->lane_tab, &c->rec_count, &c->scaled, &c->trellis_ws, &c->chain, &c->split, &c->h_in, &c->h_offs, &c->h_lens, &c->h_out, &c->h_status, &c->h_aux, &c->a_in, &c->a_tab, &c->a_out,
-                      &c->second.nmcu, &c->second.retry, &c->second.rec, &c->second.rec_line, &c->second.seg_start, &c->second.lane_tab, &c->second.rec_count})
-        if (b->p) (void)hipFree(b->p);
-    if (c->d_dec) (void)hipFree(c->d_dec);
-    if (c->d_enc) (void)hipFree(c->d_enc);
-    delete c;
+    delete c;   // (every stream is drained: the buffers go with the context)
 }
 
 extern "C" const char* amvhip_last_error(const amvhip_ctx* c) { return c ? c->err.c_str() : "null context"; }
@@ -409,6 +397,7 @@ static int entropy_front(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_byt
     }
     if (int r = check_launch(c, "unstuff")) return r;
     unsigned long long* stats = c->want_stats ? (unsigned long long*)c->stats.p : nullptr;
+    const HuffDecodeImage* dec = (const HuffDecodeImage*)c->d_dec.p;
     c->last_split = heavy_lanes != 0;
     if (heavy_lanes) {
         if (int r = ensure(c, c->split, ((size_t)n * 2 + 8) * 4)) return r;   // [heavy count, light count, 6 spare | heavy list n | light list n]
@@ -421,13 +410,13 @@ static int entropy_front(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_byt
         // the heavy frames first: their launch is a few waves deep and as long as its slowest frame's chain, the light
         // frames' launch behind it fills the chip
         launch_huffman_sync((const uint32_t*)c->ws.p, (const uint32_t*)c->ws_bytes.p, n, heavy, split_count, g, (const uint32_t*)c->ws_line.p,
-                            heavy_lanes, c->d_dec, sinks, d_status, d_nmcu_ok, retry_count + 2, stats, c->cus, st);
+                            heavy_lanes, dec, sinks, d_status, d_nmcu_ok, retry_count + 2, stats, c->cus, st);
         launch_huffman_sync((const uint32_t*)c->ws.p, (const uint32_t*)c->ws_bytes.p, n, light, split_count + 1, g, (const uint32_t*)c->ws_line.p,
-                            lanes, c->d_dec, sinks, d_status, d_nmcu_ok, retry_count + 1, stats, c->cus, st);
+                            lanes, dec, sinks, d_status, d_nmcu_ok, retry_count + 1, stats, c->cus, st);
     } else {
         Timed t(c, AMVHIP_K_HUFFMAN, st);
         launch_huffman_sync((const uint32_t*)c->ws.p, (const uint32_t*)c->ws_bytes.p, n, nullptr, nullptr, g, (const uint32_t*)c->ws_line.p,
-                            lanes, c->d_dec, sinks, d_status, d_nmcu_ok, retry_count + 1, stats, c->cus, st);
+                            lanes, dec, sinks, d_status, d_nmcu_ok, retry_count + 1, stats, c->cus, st);
     }
     fb = Fallback{retry_list, retry_count, n};
     return check_launch(c, "huffman_sync");
@@ -469,10 +458,16 @@ extern "C" int amvhip_reconstruct_dev(amvhip_ctx* c, const int16_t* d_coef, cons
     return reconstruct_launch(c, sinks, d_nmcu_ok, n, FrameSel{nullptr, nullptr, 0u, 0u}, n, g, flags, d_out, (hipStream_t)stream);
 }
 
-// dense coefficient lines the context keeps for frames that go through the serial kernel: a round's worth
-// (one round up to 16 384 frames: every round is a pair of launches that usually find nothing to do, and a batch that
-// small is latency-bound -- three rounds cost the 10 000-frame stream 3 % of its step)
-static uint32_t dense_round(uint32_t n) { return n <= 16384u ? n : (n / 4u > 16384u ? (n + 3u) / 4u : 16384u); }
+// Frames per round of a fall-back route (the context keeps a round's worth of dense coefficient lines): the whole batch
+// up to `most` frames, beyond `parts` times that a `parts`-th of it, else `most`.  Never more than 2 GB of lines, though,
+// nor fewer than 64 frames: at 640x480 a block line is 128 bytes x 7 200 blocks, and 16 384 frames of that would be 15 GB
+// kept for rounds that usually find nothing.
+static uint32_t fallback_round(uint32_t n, const FrameGeom& g, uint32_t most, uint32_t parts) {
+    uint32_t round = n <= most ? n : (n / parts > most ? (n + parts - 1u) / parts : most);
+    const uint64_t by_bytes = (2ull << 30) / ((uint64_t)g.blocks * 128u);
+    if (round > by_bytes) round = by_bytes > 64u ? (uint32_t)by_bytes : 64u;
+    return round < n ? round : n;
+}
 
 static int decode_args_ok(amvhip_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n, uint32_t w,
                           uint32_t h, uint32_t flags, const uint8_t* d_out, const int32_t* d_status) {
@@ -485,16 +480,11 @@ static int decode_args_ok(amvhip_ctx* c, const uint8_t* d_blob, const uint64_t* 
     return AMVHIP_OK;
 }
 
-// What one decode call hands from the entropy stage to the reconstruction (the context has two such sets).
-struct DecodeBufs {
-    DevBuf &nmcu, &retry, &rec, &rec_line, &seg_start, &lane_tab, &rec_count;
-};
-
 // The entropy stage of a decode call into the hand-over set b: sizes the record space, the segment bounds, the lane table
 // and the record counts, then runs entropy_front.  Statuses and nmcu_ok go to d_status / d_nmcu_ok (ok_in_blocks: nmcu_ok
 // counts whole blocks, AMVHIP_FLAG_FFMPEG_KEEP).  sinks: where the records are; its coef is left null.
 static int entropy_records(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
-                           uint32_t n, const FrameGeom& g, bool ok_in_blocks, int32_t* d_status, uint32_t* d_nmcu_ok, DecodeBufs b,
+                           uint32_t n, const FrameGeom& g, bool ok_in_blocks, int32_t* d_status, uint32_t* d_nmcu_ok, DecodeSet& b,
                            hipStream_t st, SyncSinks& sinks, Fallback& fb) {
     // Between the two stages coefficients travel as records (one word per DC and per non-zero AC coefficient), every frame
     // in space of its own, sized from ITS chunk (round 4; one stride for all, from the batch's mean chunk, before: a heavy
@@ -548,8 +538,7 @@ extern "C" int amvhip_huffman_decode_dev(amvhip_ctx* c, const uint8_t* d_blob, u
     // the entropy stage of amvhip_decode_batch_dev, into its hand-over set; the records become the caller's lines
     SyncSinks sinks;
     Fallback fb;
-    if (int r = entropy_records(c, d_blob, blob_bytes, d_offs, d_lens, n, g, false, d_status, d_nmcu_ok,
-                                DecodeBufs{c->nmcu, c->retry, c->rec, c->rec_line, c->seg_start, c->lane_tab, c->rec_count}, st, sinks, fb))
+    if (int r = entropy_records(c, d_blob, blob_bytes, d_offs, d_lens, n, g, false, d_status, d_nmcu_ok, c->set[0], st, sinks, fb))
         return r;
     if (fb.list) {   // (without a list every frame is the serial kernel's)
         launch_expand_records(sinks, d_nmcu_ok, n, g, d_coef, st);
@@ -557,8 +546,8 @@ extern "C" int amvhip_huffman_decode_dev(amvhip_ctx* c, const uint8_t* d_blob, u
     }
     {   // the caller's array has a place for every frame: one launch, lines at the frames' own places
         Timed t(c, AMVHIP_K_HUFFMAN_SERIAL, st);
-        launch_huffman(d_blob, blob_bytes, d_offs, d_lens, n, g, c->d_dec, d_coef, d_status, d_nmcu_ok, fb.list, fb.count, 0u,
-                       fb.items, false, false, st);
+        launch_huffman(d_blob, blob_bytes, d_offs, d_lens, n, g, (const HuffDecodeImage*)c->d_dec.p, d_coef, d_status, d_nmcu_ok, fb.list,
+                       fb.count, 0u, fb.items, false, false, st);
     }
     return check_launch(c, "huffman");
 }
@@ -566,17 +555,12 @@ extern "C" int amvhip_huffman_decode_dev(amvhip_ctx* c, const uint8_t* d_blob, u
 // The entropy stage goes to stream `front`, everything that writes d_out to `back` (the same stream, or two of the
 // context's own with `back` waiting for `front`).  Caller holds the lock.
 static int decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
-                       uint32_t n, uint32_t w, uint32_t h, uint32_t flags, uint8_t* d_out, int32_t* d_status, DecodeBufs b,
+                       uint32_t n, uint32_t w, uint32_t h, uint32_t flags, uint8_t* d_out, int32_t* d_status, DecodeSet& b,
                        hipStream_t front, hipStream_t back) {
     const FrameGeom g = make_geom(w, h);
-    // dense lines for a round of fall-back frames: by count (dense_round), and never more than 2 GB of them -- at 640x480 a
-    // block line is 128 bytes x 7 200 blocks, and 16 384 frames of that would be 15 GB kept for rounds that usually find nothing
-    uint32_t round = dense_round(n);
-    {
-        const uint64_t by_bytes = (2ull << 30) / ((uint64_t)g.blocks * 128u);
-        if (round > by_bytes) round = by_bytes > 64u ? (uint32_t)by_bytes : 64u;
-        if (round > n) round = n;
-    }
+    // (rounds of up to 16 384 frames: every round is a pair of launches that usually find nothing to do, and a batch that
+    // small is latency-bound -- three rounds cost the 10 000-frame stream 3 % of its step)
+    const uint32_t round = fallback_round(n, g, 16384u, 4u);
     if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
     if (int r = ensure(c, b.nmcu, (size_t)n * 4)) return r;
     uint32_t* d_nmcu = (uint32_t*)b.nmcu.p;
@@ -601,15 +585,13 @@ static int decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes
         const uint32_t items = fb.items - base < round ? fb.items - base : round;
         {
             Timed t(c, AMVHIP_K_HUFFMAN_SERIAL, st);
-            launch_huffman(d_blob, blob_bytes, d_offs, d_lens, n, g, c->d_dec, sinks.coef, d_status, d_nmcu, fb.list, fb.count, base,
-                           items, true, sinks.ok_in_blocks != 0u, st);
+            launch_huffman(d_blob, blob_bytes, d_offs, d_lens, n, g, (const HuffDecodeImage*)c->d_dec.p, sinks.coef, d_status, d_nmcu, fb.list,
+                           fb.count, base, items, true, sinks.ok_in_blocks != 0u, st);
         }
         if (int r = check_launch(c, "huffman")) return r;
         if (int r = reconstruct_launch(c, sinks, d_nmcu, n, FrameSel{fb.list, fb.count, base, items}, items, g, flags, d_out, st)) return r;
     }
-    c->ws_bytes_per_frame = (double)(c->ws.cap + c->coef.cap + c->ws_bytes.cap + c->ws_line.cap + c->rec.cap + c->rec_line.cap + c->second.rec_line.cap + c->seg_start.cap + c->lane_tab.cap +
-                                     c->rec_count.cap + c->nmcu.cap + c->retry.cap + c->second.rec.cap + c->second.seg_start.cap +
-                                     c->second.lane_tab.cap + c->second.rec_count.cap + c->second.nmcu.cap + c->second.retry.cap) / n;
+    c->ws_bytes_per_frame = (double)(c->ws.cap + c->coef.cap + c->ws_bytes.cap + c->ws_line.cap + c->set[0].cap() + c->set[1].cap()) / n;
     return AMVHIP_OK;
 }
 
@@ -622,8 +604,7 @@ extern "C" int amvhip_decode_batch_dev(amvhip_ctx* c, const uint8_t* d_blob, uin
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
-    return decode_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, flags, d_out, d_status,
-                       DecodeBufs{c->nmcu, c->retry, c->rec, c->rec_line, c->seg_start, c->lane_tab, c->rec_count}, (hipStream_t)stream,
+    return decode_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, flags, d_out, d_status, c->set[0], (hipStream_t)stream,
                        (hipStream_t)stream);
 }
 
@@ -659,10 +640,7 @@ extern "C" int amvhip_decode_submit_dev(amvhip_ctx* c, const uint8_t* d_blob, ui
     // ahead of the batch before this one -- whose entropy stage `front` has already gone through -- but not of `front`)
     if (c->submitted >= 2) HIP_TRY(c, hipStreamWaitEvent(c->front, c->ev_done[which], 0));
     if (n != 0) {
-        DecodeBufs first{c->nmcu, c->retry, c->rec, c->rec_line, c->seg_start, c->lane_tab, c->rec_count};
-        DecodeBufs second{c->second.nmcu, c->second.retry, c->second.rec, c->second.rec_line, c->second.seg_start, c->second.lane_tab, c->second.rec_count};
-        if (int r = decode_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, flags, d_out, d_status, which ? second : first, c->front,
-                                c->back))
+        if (int r = decode_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, flags, d_out, d_status, c->set[which], c->front, c->back))
             return r;
     } else {   // nothing to decode: `back` still has to pass the point where the inputs are ready
         HIP_TRY(c, hipEventRecord(c->ev_front, c->front));
@@ -699,9 +677,6 @@ extern "C" int amvhip_decode_batch_async(amvhip_ctx* c, const uint8_t* blob, uin
     // the staging buffers belong to the context: one host-buffer call at a time grows and fills them (hmu orders the
     // host-buffer entry points among themselves; mu, taken inside the _dev calls, orders the kernels' workspace)
     std::lock_guard<std::mutex> hlk(c->hmu);
-    if (int r = ensure(c, c->h_in, blob_bytes + 16)) return r;
-    if (int r = ensure(c, c->h_offs, (size_t)n * 8)) return r;
-    if (int r = ensure(c, c->h_lens, (size_t)n * 4)) return r;
     if (!c->dstream) {
         HIP_TRY(c, hipStreamCreateWithFlags(&c->dstream, hipStreamNonBlocking));
         for (hipEvent_t* e : {&c->ev_decoded, &c->ev_copied[0], &c->ev_copied[1]}) HIP_TRY(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
@@ -712,9 +687,9 @@ extern "C" int amvhip_decode_batch_async(amvhip_ctx* c, const uint8_t* blob, uin
     if (int r = ensure(c, d_st, (size_t)n * 4)) return r;
     // the copy that last read this staging buffer (the call before the last one) must be done before the kernels write it
     if (c->async_calls >= 2) HIP_TRY(c, hipStreamWaitEvent(st, c->ev_copied[which], 0));
-    HIP_TRY(c, hipMemcpyAsync(c->h_in.p, blob, blob_bytes, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->h_offs.p, offs, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->h_lens.p, lens, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    if (int r = stage(c, c->h_in, blob_bytes + 16, blob, blob_bytes, st)) return r;
+    if (int r = stage(c, c->h_offs, (size_t)n * 8, offs, (size_t)n * 8, st)) return r;
+    if (int r = stage(c, c->h_lens, (size_t)n * 4, lens, (size_t)n * 4, st)) return r;
     // AMVHIP_FLAG_FFMPEG_KEEP: what no block covers stays as the CALLER had it -- the caller's frames go up first
     if (flags & AMVHIP_FLAG_FFMPEG_KEEP) HIP_TRY(c, hipMemcpyAsync(d_frames.p, out, fb * n, hipMemcpyHostToDevice, st));
     if (int r = amvhip_decode_batch_dev(c, (const uint8_t*)c->h_in.p, blob_bytes, (const uint64_t*)c->h_offs.p,
@@ -788,9 +763,6 @@ extern "C" int amvhip_encode_coefs_dev(amvhip_ctx* c, const uint8_t* d_pix, uint
     return check_launch(c, "forward");
 }
 
-// dense coefficient lines the context keeps for frames that go through the two-stage route: a round's worth
-static uint32_t encode_round(uint32_t n) { return n <= 1024u ? n : (n / 2u > 1024u ? (n + 1u) / 2u : 1024u); }
-
 // Pixels -> chunks for n frames, RGB (yuv == nullptr) or planar YUVJ420P (the context is locked).  The one-kernel
 // encoder takes the batch; what it hands back -- and the whole batch in AMVHIP_ENTROPY_SERIAL mode -- goes through
 // amv_forward_kernel + amv_pack_kernel a round of dense lines at a time (with a list the count is on the device: the
@@ -799,12 +771,8 @@ static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride,
                        const FrameGeom& g, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
                        hipStream_t stream) {
     const uint32_t bound = amvhip_encode_bound(g.width, g.height);
-    uint32_t round = encode_round(n);
-    {   // (never more than 2 GB of dense coefficient lines, as in decode_core)
-        const uint64_t by_bytes = (2ull << 30) / ((uint64_t)g.blocks * 128u);
-        if (round > by_bytes) round = by_bytes > 64u ? (uint32_t)by_bytes : 64u;
-        if (round > n) round = n;
-    }
+    const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
+    const uint32_t round = fallback_round(n, g, 1024u, 2u);
     if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
     if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
     if (int r = ensure(c, c->flag, 16)) return r;
@@ -815,7 +783,7 @@ static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride,
     const bool fused = c->entropy_mode != AMVHIP_ENTROPY_SERIAL;
     if (fused) {
         Timed t(c, AMVHIP_K_PACK, stream);
-        launch_encode_frames(d_pix, pix_stride, is_bgr, yuv, n, g, qbias, c->d_enc, (uint8_t*)c->tmp.p, bound, d_lens, retry_list,
+        launch_encode_frames(d_pix, pix_stride, is_bgr, yuv, n, g, qbias, book, (uint8_t*)c->tmp.p, bound, d_lens, retry_list,
                              retry_count, stream);
     }
     if (int r = check_launch(c, "encode_frames")) return r;
@@ -829,7 +797,7 @@ static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride,
         }
         {
             Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
-            launch_pack((const int16_t*)c->coef.p, n, sel, items, g, c->d_enc, (uint8_t*)c->tmp.p, bound, d_lens, stream);
+            launch_pack((const int16_t*)c->coef.p, n, sel, items, g, book, (uint8_t*)c->tmp.p, bound, d_lens, stream);
         }
         if (int r = check_launch(c, "forward + pack")) return r;
     }
@@ -912,11 +880,10 @@ extern "C" int amvhip_encode_batch(amvhip_ctx* c, const uint8_t* pix, uint32_t p
     if (int r = host_stream(c, &hs)) return r;
     const size_t in_bytes = (size_t)pix_stride * h * n;
     std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
-    if (int r = ensure(c, c->h_in, in_bytes)) return r;
+    if (int r = stage(c, c->h_in, in_bytes, pix, in_bytes, hs)) return r;
     if (int r = ensure(c, c->h_out, blob_cap + 16)) return r;
     if (int r = ensure(c, c->h_offs, (size_t)n * 8)) return r;
     if (int r = ensure(c, c->h_lens, (size_t)n * 4)) return r;
-    HIP_TRY(c, hipMemcpyAsync(c->h_in.p, pix, in_bytes, hipMemcpyHostToDevice, hs));
     if (int r = amvhip_encode_batch_dev(c, (const uint8_t*)c->h_in.p, pix_stride, is_bgr, n, w, h, qbias,
                                         (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p,
                                         (uint32_t*)c->h_lens.p, hs))
@@ -1139,19 +1106,17 @@ extern "C" int amvhip_adpcm_decode_batch_async(amvhip_ctx* c, const uint8_t* blo
     // audio staging sits behind the video staging of the same stream: separate buffers, so that a video batch and the
     // audio batch that travels with it can both be in flight
     std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
-    if (int r = ensure(c, c->a_in, blob_bytes + 16)) return r;
+    if (int r = stage(c, c->a_in, blob_bytes + 16, blob, blob_bytes, st)) return r;
     if (int r = ensure(c, c->a_tab, (size_t)n * 28)) return r;
-    if (int r = ensure(c, c->a_out, pcm_samples * 2)) return r;
+    if (int r = stage(c, c->a_out, pcm_samples * 2, pcm, pcm_samples * 2, st)) return r;   // keep untouched gaps
     uint8_t* tab = (uint8_t*)c->a_tab.p;
     uint64_t* d_offs = (uint64_t*)tab;
     uint64_t* d_pcm_offs = (uint64_t*)(tab + (size_t)n * 8);
     int32_t* d_fin = (int32_t*)(tab + (size_t)n * 16);
     uint32_t* d_lens = (uint32_t*)(tab + (size_t)n * 24);
-    HIP_TRY(c, hipMemcpyAsync(c->a_in.p, blob, blob_bytes, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(d_offs, offs, (size_t)n * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(d_lens, lens, (size_t)n * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(c, hipMemcpyAsync(d_pcm_offs, pcm_offs, (size_t)n * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(c, hipMemcpyAsync(c->a_out.p, pcm, pcm_samples * 2, hipMemcpyHostToDevice, st));  // keep untouched gaps
     if (int r = amvhip_adpcm_decode_batch_dev(c, (const uint8_t*)c->a_in.p, blob_bytes, d_offs, d_lens, n, (int16_t*)c->a_out.p,
                                               d_pcm_offs, d_fin, st))
         return r;
@@ -1182,17 +1147,12 @@ extern "C" int amvhip_adpcm_encode_batch(amvhip_ctx* c, const int16_t* pcm, uint
     hipStream_t hs;
     if (int r = host_stream(c, &hs)) return r;
     std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
-    if (int r = ensure(c, c->h_in, pcm_samples * 2 + 16)) return r;
-    if (int r = ensure(c, c->h_offs, (size_t)n * 8)) return r;
-    if (int r = ensure(c, c->h_lens, (size_t)n * 4)) return r;
-    if (int r = ensure(c, c->h_out, blob_bytes)) return r;
-    if (int r = ensure(c, c->h_aux, (size_t)n * 8)) return r;
+    if (int r = stage(c, c->h_in, pcm_samples * 2 + 16, pcm, pcm_samples * 2, hs)) return r;
+    if (int r = stage(c, c->h_offs, (size_t)n * 8, offs, (size_t)n * 8, hs)) return r;
+    if (int r = stage(c, c->h_lens, (size_t)n * 4, nsamp, (size_t)n * 4, hs)) return r;
+    if (int r = stage(c, c->h_out, blob_bytes, blob, blob_bytes, hs)) return r;
+    if (int r = stage(c, c->h_aux, (size_t)n * 8, pcm_offs, (size_t)n * 8, hs)) return r;
     if (int r = ensure(c, c->h_status, (size_t)n * 4)) return r;
-    HIP_TRY(c, hipMemcpyAsync(c->h_in.p, pcm, pcm_samples * 2, hipMemcpyHostToDevice, hs));
-    HIP_TRY(c, hipMemcpyAsync(c->h_aux.p, pcm_offs, (size_t)n * 8, hipMemcpyHostToDevice, hs));
-    HIP_TRY(c, hipMemcpyAsync(c->h_lens.p, nsamp, (size_t)n * 4, hipMemcpyHostToDevice, hs));
-    HIP_TRY(c, hipMemcpyAsync(c->h_offs.p, offs, (size_t)n * 8, hipMemcpyHostToDevice, hs));
-    HIP_TRY(c, hipMemcpyAsync(c->h_out.p, blob, blob_bytes, hipMemcpyHostToDevice, hs));
     if (step_in) HIP_TRY(c, hipMemcpyAsync(c->h_status.p, step_in, (size_t)n * 4, hipMemcpyHostToDevice, hs));
     if (int r = amvhip_adpcm_encode_batch_dev(c, (const int16_t*)c->h_in.p, (const uint64_t*)c->h_aux.p,
                                               (const uint32_t*)c->h_lens.p, n,
@@ -1252,15 +1212,13 @@ static int adpcm_encode_frame_impl(amvhip_ctx* c, const int16_t* samples, uint32
     if (int r = host_stream(c, &hs)) return r;
     // staging: [pcm | chunk | scratch pcm] + small tables {pcm_off, chunk_off, nsamp, len, step, final[2]}
     std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
-    if (int r = ensure(c, c->h_in, (size_t)nsamp * 2 + 16)) return r;
-    if (int r = ensure(c, c->h_out, (size_t)len + 16 + (size_t)nsamp * 2 + 16)) return r;
-    if (int r = ensure(c, c->h_aux, 64)) return r;
     struct { uint64_t pcm_off, chunk_off; uint32_t nsamp, len; int32_t step; int32_t final_state[2]; } tab = {0, 0, nsamp, len, *step_index, {0, 0}};
+    if (int r = stage(c, c->h_in, (size_t)nsamp * 2 + 16, samples, (size_t)nsamp * 2, hs)) return r;
+    if (int r = ensure(c, c->h_out, (size_t)len + 16 + (size_t)nsamp * 2 + 16)) return r;
+    if (int r = stage(c, c->h_aux, 64, &tab, sizeof tab, hs)) return r;
     uint8_t* aux = (uint8_t*)c->h_aux.p;
     uint8_t* d_chunk = (uint8_t*)c->h_out.p;
     int16_t* d_scratch = (int16_t*)(d_chunk + ((len + 15u) & ~15u));
-    HIP_TRY(c, hipMemcpyAsync(c->h_in.p, samples, (size_t)nsamp * 2, hipMemcpyHostToDevice, hs));
-    HIP_TRY(c, hipMemcpyAsync(aux, &tab, sizeof tab, hipMemcpyHostToDevice, hs));
     if (trellis) {
         if (int r = amvhip_adpcm_encode_trellis_batch_dev(c, (const int16_t*)c->h_in.p, (const uint64_t*)aux, (const uint32_t*)(aux + 16), 1,
                                                           (const int32_t*)(aux + 24), trellis, d_chunk, (const uint64_t*)(aux + 8), nullptr, hs))
@@ -1294,11 +1252,9 @@ extern "C" int amvhip_adpcm_wav_encode_frame(amvhip_ctx* c, const int16_t* sampl
     if (int r = host_stream(c, &hs)) return r;
     const size_t ns = (size_t)1 + 8 * (size_t)groups;
     std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
-    if (int r = ensure(c, c->h_in, ns * 2)) return r;
+    if (int r = stage(c, c->h_in, ns * 2, samples, ns * 2, hs)) return r;
     if (int r = ensure(c, c->h_out, 4 + 4 * (size_t)groups)) return r;
-    if (int r = ensure(c, c->h_status, 8)) return r;
-    HIP_TRY(c, hipMemcpyAsync(c->h_in.p, samples, ns * 2, hipMemcpyHostToDevice, hs));
-    HIP_TRY(c, hipMemcpyAsync(c->h_status.p, state, 8, hipMemcpyHostToDevice, hs));
+    if (int r = stage(c, c->h_status, 8, state, 8, hs)) return r;
     launch_adpcm_wav_encode((const int16_t*)c->h_in.p, groups, (int32_t*)c->h_status.p, (uint8_t*)c->h_out.p, hs);
     if (int r = check_launch(c, "adpcm_wav_encode")) return r;
     HIP_TRY(c, hipMemcpyAsync(frame, c->h_out.p, 4 + 4 * (size_t)groups, hipMemcpyDeviceToHost, hs));
