@@ -19,6 +19,8 @@ FLAG_FFMPEG = 2
 FLAG_FFMPEG_KEEP = 4
 QBIAS_AMV, QBIAS_MJPEG = 0, 128
 K_HUFFMAN, K_RECON, K_FDCT, K_PACK, K_ADPCM_DEC, K_ADPCM_ENC, K_SYNTH, K_HUFFMAN_SERIAL, K_UNSTUFF, K_PACK_SERIAL, K_COMPACT = range(11)
+K_AUDIO_RESAMPLE = 11
+AUDIO_RATE_MIN, AUDIO_RATE_MAX = 1000, 192000
 ENTROPY_AUTO, ENTROPY_SERIAL = 0, 1
 
 _vp, _u8p = ctypes.c_void_p, ctypes.c_void_p
@@ -111,6 +113,12 @@ SYMBOLS = {
     "amvhip_encode_yuv422_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp]),
     "amvhip_resample_yuv420_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
     "amvhip_encode_yuv420_scaled_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_audio_resample_out_samples": (_u64, [_u32, _u32, _u64]),
+    "amvhip_audio_resample_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _vp]),
+    "amvhip_audio_resample_batch": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _u32, _u32]),
+    "amvhip_audio_resample_init": (_vp, [_vp, _int, _int, _int, _int]),
+    "amvhip_audio_resample": (_int, [_vp, _vp, _vp, _int]),
+    "amvhip_audio_resample_close": (None, [_vp]),
     "amvhip_encode_coefs_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _vp, _vp]),
     "amvhip_adpcm_decode_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "amvhip_adpcm_encode_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
@@ -293,6 +301,19 @@ class Context:
                                                                   _ptr(step_in), _ptr(blob), _ptr(offs), stream),
                            "adpcm_encode_batch_dev")
 
+    def audio_resample_out_samples(self, in_rate, out_rate, in_samples):
+        return audio_resample_out_samples(in_rate, out_rate, in_samples)
+
+    def audio_resample_batch_dev(self, pcm, pcm_offs, nsamp, n, in_channels, in_rate, out, out_offs, out_channels, out_rate,
+                                 stream=None):
+        return self._check(self.lib.amvhip_audio_resample_batch_dev(self.h, _ptr(pcm), _ptr(pcm_offs), _ptr(nsamp), n,
+                                                                    in_channels, in_rate, _ptr(out), _ptr(out_offs),
+                                                                    out_channels, out_rate, stream), "audio_resample_batch_dev")
+
+    def audio_resampler(self, output_channels, input_channels, output_rate, input_rate):
+        """the streaming form (amvhip_audio_resample_init): an AudioResampler bound to this context"""
+        return AudioResampler(self, output_channels, input_channels, output_rate, input_rate)
+
     def synth_frames_dev(self, seed, first, n, w, h, rgb, stream=None):
         return self._check(self.lib.amvhip_synth_frames_dev(self.h, seed, first, n, w, h, _ptr(rgb), stream), "synth_frames_dev")
 
@@ -317,6 +338,12 @@ class Context:
         return self._check(self.lib.amvhip_adpcm_encode_batch(self.h, _ptr(pcm), pcm_samples, _ptr(pcm_offs), _ptr(nsamp),
                                                               n, _ptr(step_in), _ptr(blob), blob_bytes, _ptr(offs)),
                            "adpcm_encode_batch")
+
+    def audio_resample_batch(self, pcm, pcm_samples, pcm_offs, nsamp, n, in_channels, in_rate, out, out_samples, out_offs,
+                             out_channels, out_rate):
+        return self._check(self.lib.amvhip_audio_resample_batch(self.h, _ptr(pcm), pcm_samples, _ptr(pcm_offs), _ptr(nsamp), n,
+                                                                in_channels, in_rate, _ptr(out), out_samples, _ptr(out_offs),
+                                                                out_channels, out_rate), "audio_resample_batch")
 
     def set_entropy_mode(self, mode):
         return self._check(self.lib.amvhip_set_entropy_mode(self.h, mode), "set_entropy_mode")
@@ -367,3 +394,35 @@ class Context:
 
     def kernel_name(self, kernel):
         return self.lib.amvhip_kernel_name(kernel).decode()
+
+
+def audio_resample_out_samples(in_rate, out_rate, in_samples):
+    """frames one audio_resample call makes of in_samples frames (host arithmetic, no device)"""
+    return load_library().amvhip_audio_resample_out_samples(in_rate, out_rate, in_samples)
+
+
+class AudioResampler:
+    """amvhip_audio_resample_init / _resample / _close: the reference's audio_resample, one packet per call"""
+
+    def __init__(self, ctx, output_channels, input_channels, output_rate, input_rate):
+        self.ctx, self.out_ch, self.in_ch = ctx, output_channels, input_channels
+        self.ratio = ctypes.c_float(ctypes.c_float(output_rate).value / ctypes.c_float(input_rate).value).value
+        self.h = ctx.lib.amvhip_audio_resample_init(ctx.h, output_channels, input_channels, output_rate, input_rate)
+        if not self.h:
+            raise AmvHipError("amvhip_audio_resample_init failed: %s" % ctx.lib.amvhip_last_error(ctx.h).decode())
+
+    def resample(self, pcm):
+        """one packet (numpy int16, interleaved input channels) -> its output (numpy int16, interleaved output channels)"""
+        import numpy as np
+        pcm = np.ascontiguousarray(pcm, np.int16)
+        nb = pcm.size // self.in_ch
+        out = np.zeros((int(4 * nb * self.ratio) + 18) * self.out_ch, np.int16)    # the reference's lenout bound (+2: float vs double)
+        got = self.ctx._check(self.ctx.lib.amvhip_audio_resample(self.h, out.ctypes.data, pcm.ctypes.data, nb), "audio_resample")
+        return out[:got * self.out_ch]
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.lib.amvhip_audio_resample_close(self.h)
+            self.h = None
+
+    __del__ = close

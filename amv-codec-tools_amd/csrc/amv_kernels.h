@@ -154,6 +154,35 @@ struct ResampleFilters {    // img_resample_full_init (:425-472): 16 phases x 4 
 };
 void launch_resample(const ResamplePlanes& src, const ResamplePlanes& dst, const ResampleFilters& f, uint32_t n, hipStream_t s);
 
+// ---- audio resample (amv_audio_resample.hip): audio_resample of libavcodec/resample.c over av_resample (resample2.c) --
+constexpr uint32_t kAudioPhases = 1024;                       // 1 << phase_shift (resample.c:165)
+constexpr uint32_t kAudioSpan = 4096;                         // input frames of one workgroup's LDS span (per channel)
+// Outputs one av_resample call makes on src_size frames from position `base` (index) and `frac0` before its break
+// (:266-267): I_k = base + floor((frac0 + k * D) / out_rate), D = in_rate * 1024, exists while I_k < 0 or
+// (I_k >> 10) + fl <= src_size.  Host and device use this one function.
+__host__ __device__ inline uint64_t audio_out_count(uint64_t src_size, int64_t base, uint64_t frac0, uint64_t D, uint32_t out_rate,
+                                                    uint32_t fl) {
+    const int64_t lim = src_size + 1 > fl ? (int64_t)(src_size + 1 - fl) * (int64_t)kAudioPhases : 0;
+    const int64_t m = lim - base;
+    if (m <= 0) return 0;
+    return ((uint64_t)m * out_rate - frac0 + D - 1) / D;
+}
+struct AudioResampleArgs {
+    const int16_t* pcm;           // interleaved in_ch; stream i at pcm + pcm_offs[i], nsamp[i] frames
+    const uint64_t* pcm_offs;
+    const uint64_t* nsamp;
+    int16_t* out;                 // interleaved out_ch; stream i at out + out_offs[i]
+    const uint64_t* out_offs;
+    const int16_t* bank;          // 1024 rows of fl_pad int16 (fl taps, then zeros), 16-byte aligned
+    uint32_t* tiles;              // workspace: n + 1 words
+    uint32_t n, in_ch, out_ch, out_rate, fl, fl_pad, tile;   // tile: outputs per workgroup tile (<= 256)
+    uint64_t D;                   // in_rate * 1024
+    int64_t base;                 // index before the first output (batch: -1024 * ((fl - 1) / 2))
+    uint64_t frac0, cap;          // frac before the first output; most outputs per stream (lenout of :194)
+};
+uint32_t audio_resample_tile(uint32_t in_rate, uint32_t out_rate, uint32_t fl_pad);
+void launch_audio_resample(const AudioResampleArgs& a, uint32_t blocks, hipStream_t s);
+
 // ---- ADPCM --------------------------------------------------------------------------------
 void launch_adpcm_decode(const uint8_t* blob, uint64_t blob_bytes, const uint64_t* offs,
                          const uint32_t* lens, uint32_t n, int16_t* pcm, const uint64_t* pcm_offs,

@@ -10,6 +10,7 @@
 #include <math.h>
 #include <string.h>
 
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -52,6 +53,9 @@ struct amvhip_ctx {
     DevBuf d_dec, d_enc;   // HuffDecodeImage, HuffEncodeImage
     // workspace
     DevBuf coef, tmp, flag, map, start, enc_retry, stats, ws, ws_line, layout, ws_bytes, scaled, trellis_ws, chain, split;
+    // audio resampler: filter banks by (in_rate << 32 | out_rate), uploaded once and kept; the tile counts of the last call
+    std::map<uint64_t, DevBuf> audio_banks;
+    DevBuf audio_tiles;
     // set[0] serves every decode call but amvhip_decode_submit_dev, which takes the two in turn, so that the entropy stage
     // of one batch can run (stream `front`) beside the reconstruction of the batch before (`back`)
     DecodeSet set[2];
@@ -73,7 +77,7 @@ struct amvhip_ctx {
     bool adpcm_settle = true;        // "nosettle": the chain stops after its launched sweeps (test knob: its check must notice)
     uint32_t chain_n = 0;            // chunks of the last chained ADPCM encode (where its counters are in `chain`)
     // host-pointer staging (one in-order stream of the context's own carries every host-buffer entry point)
-    DevBuf h_in, h_offs, h_lens, h_out, h_status, h_aux, a_in, a_tab, a_out;
+    DevBuf h_in, h_offs, h_lens, h_out, h_status, h_aux, a_in, a_tab, a_out, r_in, r_tab, r_out;
     hipStream_t hstream = nullptr;
     // amvhip_decode_batch_async: decoded frames go back to the host on a stream of their own, out of two staging buffers used
     // in turn, so that the copy of one call runs beside the upload and the kernels of the next (a window of the amvlib reader
@@ -1013,6 +1017,268 @@ extern "C" int amvhip_encode_yuv420_scaled_batch_dev(amvhip_ctx* c, const uint8_
 }
 
 // =============================================================================================
+// audio resample
+// =============================================================================================
+
+namespace {
+
+bool audio_args_ok(uint32_t in_ch, uint32_t in_rate, uint32_t out_ch, uint32_t out_rate) {
+    return in_ch >= 1 && in_ch <= 2 && out_ch >= 1 && out_ch <= 2 && in_rate >= AMVHIP_AUDIO_RATE_MIN &&
+           in_rate <= AMVHIP_AUDIO_RATE_MAX && out_rate >= AMVHIP_AUDIO_RATE_MIN && out_rate <= AMVHIP_AUDIO_RATE_MAX;
+}
+
+// av_resample_init (resample2.c:183-190) as audio_resample_init calls it (resample.c:165): 16 taps, cutoff 0.8
+uint32_t audio_filter_length(uint32_t in_rate, uint32_t out_rate) {
+    const double f = out_rate * 0.8 / in_rate, factor = f > 1.0 ? 1.0 : f;
+    const int fl = (int)ceil(16 / factor);
+    return fl > 1 ? (uint32_t)fl : 1u;
+}
+
+int64_t audio_index0(uint32_t fl) { return -(int64_t)kAudioPhases * ((fl - 1) / 2); }
+
+double kaiser_bessel(double x) {   // bessel() of resample2.c:74-85
+    double v = 1, t = 1;
+    x = x * x / 4;
+    for (int i = 1; i < 50; i++) {
+        t *= x / (i * i);
+        v += t;
+    }
+    return v;
+}
+
+// av_build_filter(filter, factor, fl, 1024, 1 << 15, 9) -- resample2.c:93-139, the Kaiser sibling of build_resample_filter:
+// same double / float operations in the same order; rows padded with zero taps to fl_pad
+void build_audio_bank(std::vector<int16_t>& bank, uint32_t in_rate, uint32_t out_rate, uint32_t fl, uint32_t fl_pad) {
+    const double f = out_rate * 0.8 / in_rate;
+    const double factor = f > 1.0 ? 1.0 : f;
+    const int center = ((int)fl - 1) / 2;
+    std::vector<double> tab(fl);
+    bank.assign((size_t)kAudioPhases * fl_pad, 0);
+    for (int ph = 0; ph < (int)kAudioPhases; ph++) {
+        double norm = 0;
+        for (int i = 0; i < (int)fl; i++) {
+            const double x = M_PI * ((double)(i - center) - (double)ph / (int)kAudioPhases) * factor;
+            double y = x == 0 ? 1.0 : sin(x) / x;
+            const double w = 2.0 * x / (factor * (int)fl * M_PI);
+            y *= kaiser_bessel(9 * sqrt(1 - w * w > 0 ? 1 - w * w : 0));
+            tab[i] = y;
+            norm += y;
+        }
+        for (int i = 0; i < (int)fl; i++) {
+            const long v = lrintf((float)(tab[i] * (1 << 15) / norm));
+            bank[(size_t)ph * fl_pad + i] = (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v));
+        }
+    }
+}
+
+struct AudioPlan {
+    uint32_t fl, fl_pad, tile;
+    uint64_t D;
+};
+
+AudioPlan audio_plan(uint32_t in_rate, uint32_t out_rate) {
+    AudioPlan p;
+    p.fl = audio_filter_length(in_rate, out_rate);
+    p.fl_pad = (p.fl + 7u) & ~7u;
+    p.tile = audio_resample_tile(in_rate, out_rate, p.fl_pad);
+    p.D = (uint64_t)in_rate * kAudioPhases;
+    return p;
+}
+
+// the bank of (in_rate, out_rate): built and uploaded on first use, then kept for the context's life.  Caller holds c->mu.
+int audio_bank(amvhip_ctx* c, uint32_t in_rate, uint32_t out_rate, const AudioPlan& p, const int16_t** out) {
+    DevBuf& b = c->audio_banks[(uint64_t)in_rate << 32 | out_rate];
+    if (!b.p) {
+        std::vector<int16_t> h;
+        build_audio_bank(h, in_rate, out_rate, p.fl, p.fl_pad);
+        if (int r = ensure(c, b, h.size() * 2)) return r;
+        HIP_TRY(c, hipMemcpy(b.p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+    }
+    *out = (const int16_t*)b.p;
+    return AMVHIP_OK;
+}
+
+// the launch every form shares; caller holds c->mu
+int audio_resample_core(amvhip_ctx* c, const int16_t* d_pcm, const uint64_t* d_pcm_offs, const uint64_t* d_nsamp, uint32_t n,
+                        uint32_t in_ch, uint32_t in_rate, int16_t* d_out, const uint64_t* d_out_offs, uint32_t out_ch,
+                        uint32_t out_rate, int64_t base, uint64_t frac0, uint64_t cap, hipStream_t st) {
+    const AudioPlan p = audio_plan(in_rate, out_rate);
+    AudioResampleArgs a{};
+    if (int r = audio_bank(c, in_rate, out_rate, p, &a.bank)) return r;
+    if (int r = ensure(c, c->audio_tiles, ((size_t)n + 1) * 4)) return r;
+    a.pcm = d_pcm;
+    a.pcm_offs = d_pcm_offs;
+    a.nsamp = d_nsamp;
+    a.out = d_out;
+    a.out_offs = d_out_offs;
+    a.tiles = (uint32_t*)c->audio_tiles.p;
+    a.n = n;
+    a.in_ch = in_ch;
+    a.out_ch = out_ch;
+    a.out_rate = out_rate;
+    a.fl = p.fl;
+    a.fl_pad = p.fl_pad;
+    a.tile = p.tile;
+    a.D = p.D;
+    a.base = base;
+    a.frac0 = frac0;
+    a.cap = cap;
+    Timed t(c, AMVHIP_K_AUDIO_RESAMPLE, st);
+    launch_audio_resample(a, c->cus * 8u, st);
+    return check_launch(c, "audio_resample");
+}
+
+}  // namespace
+
+extern "C" uint64_t amvhip_audio_resample_out_samples(uint32_t in_rate, uint32_t out_rate, uint64_t in_samples) {
+    if (!audio_args_ok(1, in_rate, 1, out_rate) || in_samples == 0 || (in_samples >> 32)) return 0;
+    const AudioPlan p = audio_plan(in_rate, out_rate);
+    return audio_out_count(in_samples, audio_index0(p.fl), 0, p.D, out_rate, p.fl);
+}
+
+extern "C" int amvhip_audio_resample_batch_dev(amvhip_ctx* c, const int16_t* d_pcm, const uint64_t* d_pcm_offs, const uint64_t* d_nsamp,
+                                               uint32_t n, uint32_t in_channels, uint32_t in_rate, int16_t* d_out,
+                                               const uint64_t* d_out_offs, uint32_t out_channels, uint32_t out_rate, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!audio_args_ok(in_channels, in_rate, out_channels, out_rate))
+        return fail(c, AMVHIP_ERR_ARG, "audio_resample: channels 1 or 2 in and out, rates %d .. %d", AMVHIP_AUDIO_RATE_MIN,
+                    AMVHIP_AUDIO_RATE_MAX);
+    if (n && (!d_pcm || !d_pcm_offs || !d_nsamp || !d_out || !d_out_offs)) return fail(c, AMVHIP_ERR_ARG, "audio_resample: null argument");
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const AudioPlan p = audio_plan(in_rate, out_rate);
+    return audio_resample_core(c, d_pcm, d_pcm_offs, d_nsamp, n, in_channels, in_rate, d_out, d_out_offs, out_channels, out_rate,
+                               audio_index0(p.fl), 0, ~0ull, (hipStream_t)stream);
+}
+
+extern "C" int amvhip_audio_resample_batch(amvhip_ctx* c, const int16_t* pcm, uint64_t pcm_samples, const uint64_t* pcm_offs,
+                                           const uint64_t* nsamp, uint32_t n, uint32_t in_channels, uint32_t in_rate, int16_t* out,
+                                           uint64_t out_samples, const uint64_t* out_offs, uint32_t out_channels, uint32_t out_rate) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!audio_args_ok(in_channels, in_rate, out_channels, out_rate))
+        return fail(c, AMVHIP_ERR_ARG, "audio_resample: channels 1 or 2 in and out, rates %d .. %d", AMVHIP_AUDIO_RATE_MIN,
+                    AMVHIP_AUDIO_RATE_MAX);
+    if (n && (!pcm || !pcm_offs || !nsamp || !out || !out_offs)) return fail(c, AMVHIP_ERR_ARG, "audio_resample: null argument");
+    if (n == 0) return AMVHIP_OK;
+    for (uint32_t i = 0; i < n; ++i) {
+        if ((nsamp[i] >> 32) || pcm_offs[i] > pcm_samples || nsamp[i] * in_channels > pcm_samples - pcm_offs[i])
+            return fail(c, AMVHIP_ERR_ARG, "audio_resample: stream %u reads past pcm", i);
+        const uint64_t m = amvhip_audio_resample_out_samples(in_rate, out_rate, nsamp[i]) * out_channels;
+        if (out_offs[i] > out_samples || m > out_samples - out_offs[i])
+            return fail(c, AMVHIP_ERR_SPACE, "audio_resample: out too small for stream %u", i);
+    }
+    if (int r = use_device(c)) return r;
+    hipStream_t hs;
+    if (int r = host_stream(c, &hs)) return r;
+    std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
+    if (int r = stage(c, c->r_in, pcm_samples * 2 + 16, pcm, pcm_samples * 2, hs)) return r;
+    if (int r = stage(c, c->r_out, out_samples * 2 + 16, out, out_samples * 2, hs)) return r;   // keep untouched gaps
+    if (int r = ensure(c, c->r_tab, (size_t)n * 24)) return r;
+    uint64_t* tab = (uint64_t*)c->r_tab.p;
+    HIP_TRY(c, hipMemcpyAsync(tab, pcm_offs, (size_t)n * 8, hipMemcpyHostToDevice, hs));
+    HIP_TRY(c, hipMemcpyAsync(tab + n, nsamp, (size_t)n * 8, hipMemcpyHostToDevice, hs));
+    HIP_TRY(c, hipMemcpyAsync(tab + 2 * (size_t)n, out_offs, (size_t)n * 8, hipMemcpyHostToDevice, hs));
+    if (int r = amvhip_audio_resample_batch_dev(c, (const int16_t*)c->r_in.p, tab, tab + n, n, in_channels, in_rate, (int16_t*)c->r_out.p,
+                                                tab + 2 * (size_t)n, out_channels, out_rate, hs))
+        return r;
+    HIP_TRY(c, hipMemcpyAsync(out, c->r_out.p, out_samples * 2, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(c, hipStreamSynchronize(hs));
+    return AMVHIP_OK;
+}
+
+// The streaming form: audio_resample_init / audio_resample / audio_resample_close of resample.c, the calls ffmpeg.c:1639-1641
+// and :502 make.  The host keeps what ReSampleContext keeps -- index and frac of the AVResampleContext and the unconsumed
+// tail `temp` (:186-226) -- and runs every packet through the batch kernel as one stream: the tail and the packet, from the
+// kept position, at most lenout (:194) outputs.  The tail is kept as input frames as they came (2 -> 1 mixes down on the
+// device; a frame (l, r) mixes to the value the reference keeps), so nothing is computed here but positions.
+struct amvhip_audio_resampler {
+    amvhip_ctx* c = nullptr;
+    uint32_t in_ch = 0, out_ch = 0, in_rate = 0, out_rate = 0;
+    float ratio = 0;
+    int64_t index = 0;
+    uint64_t frac = 0;
+    std::vector<int16_t> temp;   // unconsumed input frames, interleaved in_ch
+};
+
+extern "C" amvhip_audio_resampler* amvhip_audio_resample_init(amvhip_ctx* c, int output_channels, int input_channels, int output_rate,
+                                                              int input_rate) {
+    if (!c) return nullptr;
+    if (output_channels < 1 || input_channels < 1 || output_rate < 0 || input_rate < 0 ||
+        !audio_args_ok((uint32_t)input_channels, (uint32_t)input_rate, (uint32_t)output_channels, (uint32_t)output_rate)) {
+        fail(c, AMVHIP_ERR_ARG, "audio_resample_init: channels 1 or 2 in and out (no 5.1), rates %d .. %d", AMVHIP_AUDIO_RATE_MIN,
+             AMVHIP_AUDIO_RATE_MAX);
+        return nullptr;
+    }
+    if (use_device(c)) return nullptr;
+    const AudioPlan p = audio_plan((uint32_t)input_rate, (uint32_t)output_rate);
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        const int16_t* bank;
+        if (audio_bank(c, (uint32_t)input_rate, (uint32_t)output_rate, p, &bank)) return nullptr;
+    }
+    amvhip_audio_resampler* r = new amvhip_audio_resampler;
+    r->c = c;
+    r->in_ch = (uint32_t)input_channels;
+    r->out_ch = (uint32_t)output_channels;
+    r->in_rate = (uint32_t)input_rate;
+    r->out_rate = (uint32_t)output_rate;
+    r->ratio = (float)output_rate / (float)input_rate;   // s->ratio (:146)
+    r->index = audio_index0(p.fl);                       // c->index of av_resample_init (:201)
+    return r;
+}
+
+extern "C" int amvhip_audio_resample(amvhip_audio_resampler* r, short* output, short* input, int nb_samples) {
+    if (!r) return AMVHIP_ERR_ARG;
+    amvhip_ctx* c = r->c;
+    if (nb_samples < 0 || nb_samples > (1 << 28) || !output || (nb_samples && !input))
+        return fail(c, AMVHIP_ERR_ARG, "audio_resample: bad argument");
+    const AudioPlan p = audio_plan(r->in_rate, r->out_rate);
+    const int lenout = (int)(4 * nb_samples * r->ratio) + 16;                      // :194
+    const size_t have = r->temp.size(), add = (size_t)nb_samples * r->in_ch;
+    const uint64_t src = (have + add) / r->in_ch;                                   // nb_samples += s->temp_len (:218)
+    if (src == 0) return 0;
+    uint64_t count = audio_out_count(src, r->index, r->frac, p.D, r->out_rate, p.fl);
+    if (count > (uint64_t)lenout) count = (uint64_t)lenout;
+    if (count) {
+        if (int e = use_device(c)) return e;
+        hipStream_t hs;
+        if (int e = host_stream(c, &hs)) return e;
+        std::lock_guard<std::mutex> hlk(c->hmu);
+        if (int e = ensure(c, c->r_in, (have + add) * 2 + 16)) return e;
+        if (int e = ensure(c, c->r_out, count * r->out_ch * 2 + 16)) return e;
+        if (int e = ensure(c, c->r_tab, 24)) return e;
+        const uint64_t tab[3] = {0, src, 0};   // pcm offset, frames, out offset of the one stream
+        if (have) HIP_TRY(c, hipMemcpyAsync(c->r_in.p, r->temp.data(), have * 2, hipMemcpyHostToDevice, hs));
+        if (add) HIP_TRY(c, hipMemcpyAsync((int16_t*)c->r_in.p + have, input, add * 2, hipMemcpyHostToDevice, hs));
+        HIP_TRY(c, hipMemcpyAsync(c->r_tab.p, tab, sizeof tab, hipMemcpyHostToDevice, hs));
+        {
+            std::lock_guard<std::mutex> lk(c->mu);
+            const uint64_t* d_tab = (const uint64_t*)c->r_tab.p;
+            if (int e = audio_resample_core(c, (const int16_t*)c->r_in.p, d_tab, d_tab + 1, 1, r->in_ch, r->in_rate, (int16_t*)c->r_out.p,
+                                            d_tab + 2, r->out_ch, r->out_rate, r->index, r->frac, count, hs))
+                return e;
+        }
+        HIP_TRY(c, hipMemcpyAsync(output, c->r_out.p, count * r->out_ch * 2, hipMemcpyDeviceToHost, hs));
+        HIP_TRY(c, hipStreamSynchronize(hs));
+    }
+    // the state av_resample leaves (:288-293, :307-316) and the new tail (:222-225)
+    const uint64_t total = r->frac + count * p.D;
+    int64_t index = r->index + (int64_t)(total / r->out_rate);
+    r->frac = total % r->out_rate;
+    const uint64_t consumed = index > 0 ? (uint64_t)index >> 10 : 0;
+    if (index >= 0) index &= kAudioPhases - 1;
+    r->index = index;
+    std::vector<int16_t> rest;
+    rest.reserve(have + add - consumed * r->in_ch);
+    for (uint64_t i = consumed * r->in_ch; i < have + add; ++i) rest.push_back(i < have ? r->temp[i] : input[i - have]);
+    r->temp.swap(rest);
+    return (int)count;
+}
+
+extern "C" void amvhip_audio_resample_close(amvhip_audio_resampler* r) { delete r; }
+
+// =============================================================================================
 // ADPCM
 // =============================================================================================
 
@@ -1402,6 +1668,7 @@ extern "C" const char* amvhip_kernel_name(int kernel) {
         case AMVHIP_K_ADPCM_DEC: return "amv_adpcm_decode_kernel";
         case AMVHIP_K_ADPCM_ENC: return "amv_adpcm_guess_kernel+amv_adpcm_sweep_kernel*+front+settle+check (+map, chain, encode_mapped when the chain does not settle)";
         case AMVHIP_K_SYNTH: return "amv_synth_frames_kernel";
+        case AMVHIP_K_AUDIO_RESAMPLE: return "amv_audio_tiles_kernel+amv_audio_resample_kernel";
         default: return "";
     }
 }

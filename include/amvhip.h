@@ -396,6 +396,46 @@ int amvhip_encode_yuv420_scaled_batch_dev(amvhip_ctx *ctx, const uint8_t *d_y, c
                                           uint64_t c_frame_stride, uint32_t src_width, uint32_t src_height, uint32_t n,
                                           uint32_t width, uint32_t height, uint32_t qbias, uint8_t *d_blob,
                                           uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens, void *stream);
+/*
+ * The audio resampler in front of the ADPCM encoder: audio_resample (libavcodec/resample.c:129-242) over av_resample
+ * (resample2.c:182-324), what ffmpeg.c:1639-1641 / :502 run for `-ac 1 -ar 22050` (AMVmuxer/Makefile:16).  16-tap (at
+ * 0.8 of the lower rate's Nyquist: 40 taps at 44.1 kHz -> 22.05 kHz, 44 at 48 kHz, 88 at 96 kHz), 1024-phase, Kaiser-windowed
+ * polyphase filter in int16 with 32-bit wrapping sums, bit-exact with the reference.  Channels: 1 or 2 in, 1 or 2 out
+ * (2 -> 1 mixes down (l + r) >> 1 first, 1 -> 2 duplicates; the reference's 5.1 output is not offered); rates
+ * AMVHIP_AUDIO_RATE_MIN .. AMVHIP_AUDIO_RATE_MAX (AMVHIP_ERR_ARG beyond).  Samples int16, channels interleaved; offsets in
+ * int16 elements, lengths in frames (one sample per channel).
+ *
+ * amvhip_audio_resample_out_samples  frames one audio_resample call makes of in_samples frames (host arithmetic, no device):
+ *                                    the filter needs its whole span, so the last ~fl/2 input frames make no output and
+ *                                    nothing flushes them (ffmpeg.c never does).  0 outside the rate range, for 0 frames and
+ *                                    for 2^32 frames or more.
+ * amvhip_audio_resample_batch_dev    n independent streams of one format; stream i = d_nsamp[i] frames at d_pcm + d_pcm_offs[i],
+ *                                    its output (out_samples(d_nsamp[i]) frames) at d_out + d_out_offs[i]: equal to one
+ *                                    audio_resample call on the whole stream.  Asynchronous on `stream`.
+ * amvhip_audio_resample_batch        the same with host buffers (H2D, kernels, D2H, synchronous); pcm_samples / out_samples are
+ *                                    the sizes in int16 of the whole arrays the offsets index into.
+ * amvhip_audio_resample_init / amvhip_audio_resample / amvhip_audio_resample_close
+ *                                    the reference's streaming calls with their argument order (output first): every packet of
+ *                                    nb_samples frames goes to the device and returns the reference's count, the unconsumed tail
+ *                                    and the filter position kept between calls (also the reference's lenout cap of
+ *                                    4 * nb_samples * ratio + 16 outputs per call).  init: NULL for bad arguments (input or output
+ *                                    channels beyond 2, as resample.c:134-138 refuses) or without a device; resample: the count,
+ *                                    or a negative AMVHIP_ERR_*.
+ */
+#define AMVHIP_AUDIO_RATE_MIN 1000
+#define AMVHIP_AUDIO_RATE_MAX 192000
+uint64_t amvhip_audio_resample_out_samples(uint32_t in_rate, uint32_t out_rate, uint64_t in_samples);
+int amvhip_audio_resample_batch_dev(amvhip_ctx *ctx, const int16_t *d_pcm, const uint64_t *d_pcm_offs, const uint64_t *d_nsamp,
+                                    uint32_t n, uint32_t in_channels, uint32_t in_rate, int16_t *d_out,
+                                    const uint64_t *d_out_offs, uint32_t out_channels, uint32_t out_rate, void *stream);
+int amvhip_audio_resample_batch(amvhip_ctx *ctx, const int16_t *pcm, uint64_t pcm_samples, const uint64_t *pcm_offs,
+                                const uint64_t *nsamp, uint32_t n, uint32_t in_channels, uint32_t in_rate, int16_t *out,
+                                uint64_t out_samples, const uint64_t *out_offs, uint32_t out_channels, uint32_t out_rate);
+typedef struct amvhip_audio_resampler amvhip_audio_resampler;
+amvhip_audio_resampler *amvhip_audio_resample_init(amvhip_ctx *ctx, int output_channels, int input_channels, int output_rate,
+                                                   int input_rate);
+int amvhip_audio_resample(amvhip_audio_resampler *r, short *output, short *input, int nb_samples);
+void amvhip_audio_resample_close(amvhip_audio_resampler *r);
 /* Stage access: quantised coefficients (zig-zag order, not predicted), n*nmcu*6*64 int16 */
 int amvhip_encode_coefs_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr,
                             uint32_t n, uint32_t width, uint32_t height, uint32_t qbias,
@@ -507,6 +547,7 @@ int amvhip_mux_close(amvhip_muxer *m);
 #define AMVHIP_K_UNSTUFF 8
 #define AMVHIP_K_PACK_SERIAL 9
 #define AMVHIP_K_COMPACT 10   /* amv_scan_kernel + amv_gather_kernel, timed as one */
+#define AMVHIP_K_AUDIO_RESAMPLE 11   /* amv_audio_tiles_kernel + amv_audio_resample_kernel, timed as one */
 #define AMVHIP_K_COUNT 12
 void amvhip_prof_enable(amvhip_ctx *ctx, int on);
 void amvhip_prof_reset(amvhip_ctx *ctx);
