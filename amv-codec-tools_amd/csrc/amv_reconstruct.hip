@@ -36,7 +36,13 @@ constexpr int kRowsPerGroup = 4;   // (five where fours leave too many slots idl
 
 // 8-point inverse DCT of AmvJpeg.c: idctrow (:1082-1128) when kColumn == false, idctcol
 // (:1130-1175, without its final clamp) when true.  The reference's all-AC-zero shortcuts
-// (:1087-1092, :1134-1140) are exact special cases of this arithmetic and are not branched on.
+// (:1087-1092, :1134-1140) are not branched on.  They are special cases of this arithmetic only while the general
+// formula does not leave 32 bits where the shortcut stays inside them: the row shortcut's 8 * dc is
+// (dc * 2048 + 128) >> 8 for -2^20 <= dc < 2^20, the column shortcut's (x + 32) >> 6 is (x * 256 + 8192) >> 14 for
+// -2^23 <= x <= 2^23 - 33.  Every coefficient block a scan can carry stays inside both (DC any int16, |AC| <= 1023:
+// a row's first element is at most 32768 * 9 or 1023 * 61, a row-0 result at most 3.9 M), and so does every block whose
+// |AC * step| <= 100 000 ("What the stage accessor promises"); beyond that -- through amvhip_reconstruct_dev
+// only -- the kernel wraps where the reference's shortcut does not, and the pixels of such a block differ.
 // The products are written per input (W1*a4 + W7*a5 instead of W7*(a4+a5) + (W1-W7)*a4): the same numbers
 // modulo 2^32, which is what the reference's int arithmetic computes, but every factor is an INPUT of the
 // pass and those always fit 24 bits -- a quantised coefficient times a step in the row pass, a value

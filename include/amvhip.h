@@ -318,7 +318,16 @@ int amvhip_huffman_decode_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t b
                               uint32_t width, uint32_t height,
                               int16_t *d_coef, int32_t *d_status, uint32_t *d_nmcu_ok, void *stream);
 /* Stage access: dequantise + IDCT + colour + store from coefficients
- * (IQtIZzBlock/Fast_IDCT/GetYUV/StoreBuffer, AmvJpeg.c:1010-1059,754-840). */
+ * (IQtIZzBlock/Fast_IDCT/GetYUV/StoreBuffer, AmvJpeg.c:1010-1059,754-840).
+ * For which coefficients the frame is the reference's, byte for byte:
+ *   - AMVHIP_FLAG_FFMPEG: every int16 value at every place (the reference's int16 stores wrap, and so do the kernel's);
+ *   - the amvlib modes (flags 0, AMVHIP_FLAG_ZIGZAG_FIXED): the DC any int16 and every AC coefficient c at scan position s
+ *     with |c * step[s]| <= 100 000 (step: the amvlib quantiser tables, AmvJpeg.c:30-61).  That holds everything a scan
+ *     can carry (|AC| <= 1023, steps <= 61), so everything amvhip_huffman_decode_dev hands out.  Beyond it the reference's
+ *     all-AC-zero IDCT shortcuts (AmvJpeg.c:1087-1092, 1134-1140) keep 32-bit values where the kernel's general formula
+ *     wraps, and the pixels of such a BLOCK (its 8x8 luma samples, or the 16x16 pixels under a chroma block) may differ
+ *     from the reference's.  Every byte of the frame is written all the same, every pixel is a clamped 0..255 value, and
+ *     no other block, frame or byte outside the frame's rows is affected. */
 int amvhip_reconstruct_dev(amvhip_ctx *ctx, const int16_t *d_coef, const uint32_t *d_nmcu_ok,
                            uint32_t n, uint32_t width, uint32_t height, uint32_t flags,
                            uint8_t *d_out, void *stream);
