@@ -3,8 +3,8 @@
 // A wave owns an MCU-row segment of `cnt` MCUs (<= 10, i.e. <= 60 blocks).  Lane b ends up with block b's 64
 // coefficients (scan order, int16 pairs in 32 dwords): from its dense 128-byte line, or -- records form -- after
 // the wave has scattered the segment's (block, index, value) records into a zeroed LDS image of the blocks (16-byte
-// granules XOR-swizzled by block so that the per-lane 128-byte reads do not collide on banks) and added the DC base
-// of the entropy lane that decoded the block (SyncSinks::lane_tab).
+// granules XOR-swizzled by the record's block field so that the per-lane 128-byte reads do not collide on banks) and
+// added the DC base of the entropy lane that decoded the block (SyncSinks::lane_tab).
 #pragma once
 #include <cstdlib>
 
@@ -15,6 +15,10 @@ namespace amv {
 
 constexpr uint32_t kSegImageBytes = 60u * 128u;   // the LDS image of a segment's <= 60 blocks; 128 spare bytes follow it
 constexpr uint32_t kDummyRecordWord = 0x8000u;   // bit 15: a filler no block owns (amv_decode_sync.hip's kDummyRecord)
+// the scatter's numbers (tests/test_scatter_model.py restates the arithmetic on them)
+constexpr uint32_t kScatterSwizzleMask = 0x38u;     // (word >> 3) & this: the block field's low three bits over the index's granule bits
+constexpr uint32_t kScatterFieldShift = 6u;         // the block field's place in the word
+constexpr uint32_t kScatterAddressMask = 0x11ffeu;  // doubled word: byte offset (1-6), block in segment (7-12), filler (16)
 
 // A segment belongs to one wave and so does its LDS: what one lane wrote another lane of the same wave may read once
 // the wave has passed this point (a wave's LDS operations are served in order; the fence keeps the compiler from
@@ -41,6 +45,8 @@ __device__ __forceinline__ bool select_frame(const FrameSel& sel, uint32_t n, ui
 
 // dense_only: a round launch -- the frame's lines are in slot `slot` whatever rec_count says.  A default launch over
 // records leaves frames that went to the serial kernel alone: skip = true (for the whole workgroup), nothing loaded.
+// f, slot, segidx, mcu0, cnt and ok are the WAVE's: the same in every lane (a wave owns one segment).  The scatter keeps
+// what it derives from them in scalar registers; a caller whose values come from threadIdx loses nothing but those.
 __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, uint32_t f, uint32_t slot, bool dense_only,
                                                     const FrameGeom& g, uint32_t segidx,
                                                     uint32_t nsegs, uint32_t mcu0, uint32_t cnt, uint32_t ok, uint32_t lane,
@@ -86,27 +92,40 @@ __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, uint32_
         uint4* img16 = reinterpret_cast<uint4*>(s_img);
         for (uint32_t i = lane; i < nb * 8u; i += kWave) img16[i] = make_uint4(0, 0, 0, 0);
         seg_sync();
-        // Scatter, without a branch per record: the word shifted left by one holds 2 * index in bits 1-6, the block field
-        // in bits 7-12 and the filler flag in bit 16.  Adding (64 - first block) << 7 turns the field into the block's
-        // number in the segment (modulo 64, carry into bit 13); with bit 16 kept, one unsigned compare against
-        // "blocks decoded << 7" rejects fillers and other segments' blocks alike, and a record past the range's end
-        // compares against 0.  A rejected record goes to the lane's spare slot behind the image.
-        const uint32_t first7 = (64u - ((mcu0 * 6u - g.blocks) & 63u)) << 7;   // the block field counts from the frame's end
+        // Scatter, without a branch per record.  A word is index | block field << 6 | filler << 15 | value << 16, the
+        // field counting from the frame's end modulo 64.  The index's granule bits (3-5) are XOR-ed with the field's low
+        // three bits first -- the reader's swizzle, taken from the field as it stands, so the lane of block b reads with
+        // (b + first block's field) & 7 -- and then ONE add-and-shift puts the segment's first block at 0 and doubles the
+        // whole: byte offset in bits 1-6, block in segment in bits 7-12 (modulo 64, the carry lands in bit 13), filler in
+        // bit 16.  Masked to those, one unsigned compare against "blocks decoded << 7" rejects fillers and other
+        // segments' blocks alike.  A rejected record goes to the lane's spare slot behind the image.  The value is stored
+        // from the word's high half as it lies.  Words past the range's end are made fillers beforehand, in the one
+        // piece that holds the end (a test per record cost two instructions in every slot).
+        const uint32_t field0 = (mcu0 * 6u - g.blocks) & 63u;               // the block field of the segment's first block
+        const uint32_t first6 = (uint32_t)__builtin_amdgcn_readfirstlane((int)((64u - field0) << kScatterFieldShift));   // (wave-uniform by contract)
         const uint32_t ok7 = blocks_ok_here << 7;
         const uint32_t spare = kSegImageBytes + lane * 2u;
         for (uint32_t base = 0;;) {
 #pragma unroll
             for (uint32_t j = 0; j < kAhead; ++j) {
                 if (base + j * 4u * kWave >= nrec) break;                   // (wave-uniform) nothing of this piece is in range
-                const int32_t left = (int32_t)(nrec - base - j * 4u * kWave) - (int32_t)(lane * 4u);   // records from this lane's first on
+                if (base + (j + 1u) * 4u * kWave > nrec) {                  // (wave-uniform) the range ends inside this piece
+                    const int32_t left = (int32_t)(nrec - base - j * 4u * kWave) - (int32_t)(lane * 4u);   // records from this lane's first on
+#pragma unroll
+                    for (uint32_t e = 0; e < 4u; ++e)
+                        if (left <= (int32_t)e) q[j].w[e] = kDummyRecordWord;
+                }
 #pragma unroll
                 for (uint32_t e = 0; e < 4u; ++e) {
-                    const uint32_t u = q[j].w[e] << 1;
-                    const uint32_t t = u + first7;
-                    const uint32_t b7 = t & 0x11f80u;                                    // block in segment << 7, filler flag
-                    const uint32_t at = b7 | ((u & 0x7eu) ^ ((t >> 3) & 0x70u));         // 16-byte granule XOR block, as the reader expects
-                    const bool take = b7 < (left > (int32_t)e ? ok7 : 0u);
-                    *reinterpret_cast<int16_t*>(s_img + (take ? at : spare)) = (int16_t)(q[j].w[e] >> 16);
+                    const uint32_t w = q[j].w[e];
+                    // t = ((w ^ ((w >> 3) & 0x38)) + first6) << 1.  Written as the instruction because hipcc 7.2 splits
+                    // first6 into -(field0 << 6) and 64 << 6 and adds twice (eight instructions a slot instead of seven);
+                    // to see whether a compiler still needs it: put the C expression here and count the vector
+                    // instructions between two ds_write_b16_d16_hi of amv_reconstruct_kernel<false, 4> in the disassembly.
+                    uint32_t t;
+                    asm("v_add_lshl_u32 %0, %1, %2, 1" : "=v"(t) : "v"(w ^ ((w >> 3) & kScatterSwizzleMask)), "s"(first6));
+                    const uint32_t at = t & kScatterAddressMask;
+                    *reinterpret_cast<int16_t*>(s_img + (at < ok7 ? at : spare)) = (int16_t)(w >> 16);
                 }
             }
             base += kAhead * 4u * kWave;
@@ -144,9 +163,10 @@ __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, uint32_
     if (lane >= nb) return false;
     if (records) {
         const uint4* src = reinterpret_cast<const uint4*>(s_img) + lane * 8u;
+        const uint32_t swz = (lane + mcu0 * 6u - g.blocks) & 7u;   // the low bits of this block's field: the scatter's swizzle
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const uint4 q = src[(uint32_t)i ^ (lane & 7u)];
+            const uint4 q = src[(uint32_t)i ^ swz];
             c[4 * i] = q.x; c[4 * i + 1] = q.y; c[4 * i + 2] = q.z; c[4 * i + 3] = q.w;
         }
         c[0] = (c[0] & 0xffff0000u) | ((c[0] + (uint32_t)dc_base) & 0xffffu);   // int16 arithmetic, as the predictors wrap

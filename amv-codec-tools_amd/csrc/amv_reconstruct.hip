@@ -56,15 +56,20 @@ __device__ __forceinline__ int mad24(int x, int w, int c) {
     return d;
 }
 
-template <bool kColumn>
+// The column pass takes its v0 and v4 -- results of rows 0 and 4 -- as 256 * v0 + 8192 and 256 * v4.  ((s >> 8) << 8 is
+// s & ~255 for every 32-bit s, and 8192 is a multiple of 256, so (((s + 128) >> 8) << 8) + 8192 is (s + 128 + 8192) & ~255.)
+// Those two rows therefore leave the row pass masked instead of shifted (kRow0 with the column's bias on top of the
+// row's, kRow4 without), and the column pass neither shifts them up again nor adds: the same numbers modulo 2^32.
+enum RowKind { kRowPlain, kRow0, kRow4 };
+
+template <bool kColumn, RowKind kKind = kRowPlain>
 __device__ __forceinline__ void idct8(int& v0, int& v1, int& v2, int& v3, int& v4, int& v5, int& v6, int& v7) {
     constexpr int W1 = 2841, W2 = 2676, W3 = 2408, W5 = 1609, W6 = 1108, W7 = 565;
-    constexpr int kUp = kColumn ? 256 : 2048;    // <<8 / <<11
-    constexpr int kBias = kColumn ? 8192 : 128;
+    constexpr int kBias = kKind == kRow0 ? 128 + 8192 : 128;
     constexpr int kRound = kColumn ? 4 : 0;
     constexpr int kDown = kColumn ? 3 : 0;
     constexpr int kOut = kColumn ? 14 : 8;
-    int a0 = v0 * kUp + kBias, a1 = v4 * kUp;
+    int a0 = kColumn ? v0 : v0 * 2048 + kBias, a1 = kColumn ? v4 : v4 * 2048;   // (<<11; the column's <<8 is done)
     const int i2 = v6, i3 = v2, i4 = v1, i5 = v7, i6 = v5, i7 = v3;
     int t;
     int a4 = mad24(i4, W1, mad24(i5, W7, kRound)) >> kDown;     // W7*(x4+x5) + (W1-W7)*x4
@@ -85,14 +90,19 @@ __device__ __forceinline__ void idct8(int& v0, int& v1, int& v2, int& v3, int& v
     a0 -= a2;
     a2 = (181 * (a4 + a5) + 128) >> 8;
     a4 = (181 * (a4 - a5) + 128) >> 8;
-    v0 = (a7 + a1) >> kOut;
-    v1 = (a3 + a2) >> kOut;
-    v2 = (a0 + a4) >> kOut;
-    v3 = (t + a6) >> kOut;
-    v4 = (t - a6) >> kOut;
-    v5 = (a0 - a4) >> kOut;
-    v6 = (a3 - a2) >> kOut;
-    v7 = (a7 - a1) >> kOut;
+    v0 = a7 + a1;
+    v1 = a3 + a2;
+    v2 = a0 + a4;
+    v3 = t + a6;
+    v4 = t - a6;
+    v5 = a0 - a4;
+    v6 = a3 - a2;
+    v7 = a7 - a1;
+    if (kKind == kRowPlain) {
+        v0 >>= kOut; v1 >>= kOut; v2 >>= kOut; v3 >>= kOut; v4 >>= kOut; v5 >>= kOut; v6 >>= kOut; v7 >>= kOut;
+    } else {
+        v0 &= ~255; v1 &= ~255; v2 &= ~255; v3 &= ~255; v4 &= ~255; v5 &= ~255; v6 &= ~255; v7 &= ~255;
+    }
 }
 
 // the quantiser steps, scan order, four to a dword: [0] luma, [1] chroma.  A lane reads its component's sixteen dwords
@@ -140,7 +150,8 @@ __global__ __launch_bounds__(kWave * kRows) void amv_reconstruct_kernel(
     // 7 680 bytes (+ the scatter's spare slots): first the records' image of the 60 blocks (128 bytes each), then the three planes
     __shared__ __attribute__((aligned(16))) int16_t s_all[kRows][16 * kPitchY + 2 * 8 * kPitchC + 64];
     static_assert((16 * kPitchY + 2 * 8 * kPitchC) * 2 == kSegImageBytes, "the planes reuse the image");
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // (the wave's number as a scalar: what follows from it -- its MCU row, its LDS, the scatter's constants -- stays out of the vector registers)
+    const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t nseg = pm.nseg;
     uint32_t item0, row_group, seg;
     if (!locate_piece(pm, blockIdx.x, item0, row_group, seg)) return;
@@ -186,8 +197,11 @@ __global__ __launch_bounds__(kWave * kRows) void amv_reconstruct_kernel(
         if (!(flags & kFlagZigzagFixed))     // amvlib's table reads scan position 37 at natural (3,4)
             v[kAmvlibQuirkNatural] = coef_at(c, kAmvlibQuirkScan) * (int)((qw[kAmvlibQuirkScan >> 2] >> (8 * (kAmvlibQuirkScan & 3))) & 255u);
 #pragma unroll
-        for (int r = 0; r < 8; ++r)
-            idct8<false>(v[8 * r], v[8 * r + 1], v[8 * r + 2], v[8 * r + 3], v[8 * r + 4], v[8 * r + 5], v[8 * r + 6], v[8 * r + 7]);
+        for (int r = 0; r < 8; ++r) {
+            if (r == 0) idct8<false, kRow0>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+            else if (r == 4) idct8<false, kRow4>(v[32], v[33], v[34], v[35], v[36], v[37], v[38], v[39]);
+            else idct8<false>(v[8 * r], v[8 * r + 1], v[8 * r + 2], v[8 * r + 3], v[8 * r + 4], v[8 * r + 5], v[8 * r + 6], v[8 * r + 7]);
+        }
 #pragma unroll
         for (int col = 0; col < 8; ++col)
             idct8<true>(v[col], v[8 + col], v[16 + col], v[24 + col], v[32 + col], v[40 + col], v[48 + col], v[56 + col]);
