@@ -20,6 +20,10 @@ FLAG_FFMPEG_KEEP = 4
 QBIAS_AMV, QBIAS_MJPEG = 0, 128
 K_HUFFMAN, K_RECON, K_FDCT, K_PACK, K_ADPCM_DEC, K_ADPCM_ENC, K_SYNTH, K_HUFFMAN_SERIAL, K_UNSTUFF, K_PACK_SERIAL, K_COMPACT = range(11)
 K_AUDIO_RESAMPLE = 11
+K_PIXFMT = 12
+(PIX_YUV420P, PIX_YUVJ420P, PIX_YUV422P, PIX_YUVJ422P, PIX_YUV444P, PIX_YUVJ444P, PIX_YUYV422, PIX_UYVY422, PIX_RGB24, PIX_BGR24,
+ PIX_RGB32, PIX_RGB565, PIX_RGB555, PIX_GRAY8) = range(14)
+PIX_COUNT = 14
 AUDIO_RATE_MIN, AUDIO_RATE_MAX = 1000, 192000
 ENTROPY_AUTO, ENTROPY_SERIAL = 0, 1
 
@@ -113,6 +117,13 @@ SYMBOLS = {
     "amvhip_encode_yuv422_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp]),
     "amvhip_resample_yuv420_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
     "amvhip_encode_yuv420_scaled_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_img_convert_supported": (_int, [_int, _int, _u32, _u32]),
+    "amvhip_pix_frame_bytes": (_u64, [_int, _u32, _u32]),
+    "amvhip_img_convert_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
+    "amvhip_img_convert": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32]),
+    "amvhip_sws_scale_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
+    "amvhip_encode_fmt_scaled_batch_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_decode_fmt_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
     "amvhip_audio_resample_out_samples": (_u64, [_u32, _u32, _u64]),
     "amvhip_audio_resample_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _vp]),
     "amvhip_audio_resample_batch": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _u32, _u32]),
@@ -300,6 +311,35 @@ class Context:
         return self._check(self.lib.amvhip_adpcm_encode_batch_dev(self.h, _ptr(pcm), _ptr(pcm_offs), _ptr(nsamp), n,
                                                                   _ptr(step_in), _ptr(blob), _ptr(offs), stream),
                            "adpcm_encode_batch_dev")
+
+    # pixel formats.  A picture is (planes, stride, c_stride, frame_stride, c_frame_stride) with planes a sequence of up to
+    # three tensors / arrays / addresses (packed formats and GRAY8: one)
+    @staticmethod
+    def _pic(pic):
+        planes, stride, c_stride, frame, c_frame = pic
+        planes = list(planes) + [None] * (3 - len(planes))
+        return [_ptr(planes[0]), _ptr(planes[1]), _ptr(planes[2]), stride, c_stride, frame, c_frame]
+
+    def img_convert_dev(self, src_fmt, src, dst_fmt, dst, w, h, n, stream=None):
+        return self._check(self.lib.amvhip_img_convert_dev(self.h, src_fmt, *self._pic(src), dst_fmt, *self._pic(dst), w, h, n, stream),
+                           "img_convert_dev")
+
+    def img_convert(self, src_fmt, src, dst_fmt, dst, w, h, n):
+        return self._check(self.lib.amvhip_img_convert(self.h, src_fmt, *self._pic(src), dst_fmt, *self._pic(dst), w, h, n), "img_convert")
+
+    def sws_scale_dev(self, src_fmt, src, src_w, src_h, dst_fmt, dst, dst_w, dst_h, n, stream=None):
+        return self._check(self.lib.amvhip_sws_scale_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, dst_fmt, *self._pic(dst),
+                                                         dst_w, dst_h, n, stream), "sws_scale_dev")
+
+    def encode_fmt_scaled_batch_dev(self, src_fmt, src, src_w, src_h, n, w, h, qbias, blob, blob_cap, offs, lens, stream=None):
+        return self._check(self.lib.amvhip_encode_fmt_scaled_batch_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n, w, h, qbias,
+                                                                       _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), stream),
+                           "encode_fmt_scaled_batch_dev")
+
+    def decode_fmt_batch_dev(self, blob, blob_bytes, offs, lens, n, w, h, flags, dst_fmt, out, out_stride, status, stream=None):
+        return self._check(self.lib.amvhip_decode_fmt_batch_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, flags,
+                                                                dst_fmt, _ptr(out), out_stride, _ptr(status), stream),
+                           "decode_fmt_batch_dev")
 
     def audio_resample_out_samples(self, in_rate, out_rate, in_samples):
         return audio_resample_out_samples(in_rate, out_rate, in_samples)

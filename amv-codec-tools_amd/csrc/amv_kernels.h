@@ -152,7 +152,48 @@ struct ResampleFilters {    // img_resample_full_init (:425-472): 16 phases x 4 
     int16_t h[64], v[64];
     int h_incr, v_incr;
 };
-void launch_resample(const ResamplePlanes& src, const ResamplePlanes& dst, const ResampleFilters& f, uint32_t n, hipStream_t s);
+// to_jpeg: the bytes leave through y_ccir_to_jpeg / c_ccir_to_jpeg (the shim's last img_convert, YUV420P -> YUVJ420P, folded
+// into the store); false: the plain routine, as it always was
+void launch_resample(const ResamplePlanes& src, const ResamplePlanes& dst, const ResampleFilters& f, uint32_t n, hipStream_t s,
+                     bool to_jpeg = false);
+
+// ---- pixel formats (amv_pixfmt.hip): img_convert of libavcodec/imgconvert.c ----------------------------------------
+// SCALEBITS = 10 fixed point of colorspace.h:30-32
+constexpr int pix_fix(double x) { return (int)(x * 1024 + 0.5); }
+// one of the four range tables of imgconvert.c:1216-1233 as min(max((v * mul + add) >> 10, lo), 255); identity: {1024, 0, 0}
+struct PixRange { int mul, add, lo; };
+constexpr PixRange kPixRangeNone{1024, 0, 0};
+constexpr PixRange kPixYCcirToJpeg{pix_fix(255.0 / 219.0), 512 - 16 * pix_fix(255.0 / 219.0), 0};                         // colorspace.h:69-70
+constexpr PixRange kPixYJpegToCcir{pix_fix(219.0 / 255.0), 512 + (16 << 10), 0};                                         // :72-73
+constexpr PixRange kPixCCcirToJpeg{pix_fix(127.0 / 112.0), 512 + (128 << 10) - 128 * pix_fix(127.0 / 112.0), 0};         // :75-76
+constexpr PixRange kPixCJpegToCcir{pix_fix(112.0 / 127.0), 512 + (128 << 10) - 128 * pix_fix(112.0 / 127.0), 16};        // :79-84
+enum : uint32_t { kPixCopy = 0, kPixShrink12 = 1, kPixShrink22 = 2 };
+struct PixPlaneJob {        // one destination plane of w x h samples; frame i at src + i*sframe, dst + i*dframe
+    const uint8_t* src;
+    uint8_t* dst;
+    uint32_t sstride, dstride;
+    uint64_t sframe, dframe;
+    uint32_t w, h, resize;
+    PixRange range;
+};
+struct PixPlaneJobs { PixPlaneJob j[3]; uint32_t count; };
+struct PixPicture {         // planes (packed formats and GRAY8: plane 0 only), row and frame pitches in bytes
+    uint8_t* p[3];
+    uint32_t stride[3];
+    uint64_t frame[3];
+};
+struct PixRgbIn { int y[3], yadd, u[3], v[3]; };          // weights of the bytes at +0, +1, +2 of a pixel
+struct PixRgbOut {                                        // component at byte +0 / +1 / +2 (16-bit: red / green / blue)
+    int ymul, yoff, c0[2], c1[2], c2[2];                  // {weight of cb - 128, weight of cr - 128}
+    uint32_t rshift, gdrop;                               // 16-bit formats: 11, 2 (5-6-5) or 10, 3 (5-5-5)
+};
+void launch_pix_planes(const PixPlaneJobs& jobs, uint32_t n, hipStream_t s);
+void launch_pix_packed_in(const PixPicture& src, const PixPicture& dst, uint32_t w, uint32_t h, bool uyvy, uint32_t n, hipStream_t s);
+void launch_pix_packed_out(const PixPicture& src, const PixPicture& dst, uint32_t w, uint32_t h, bool uyvy, uint32_t n, hipStream_t s);
+void launch_pix_rgb_in(const PixPicture& src, const PixPicture& dst, uint32_t w, uint32_t h, uint32_t bpp, const PixRgbIn& k, uint32_t n,
+                       hipStream_t s);
+void launch_pix_rgb_out(const PixPicture& src, const PixPicture& dst, uint32_t w, uint32_t h, uint32_t bpp, const PixRgbOut& k, uint32_t n,
+                        hipStream_t s);
 
 // ---- audio resample (amv_audio_resample.hip): audio_resample of libavcodec/resample.c over av_resample (resample2.c) --
 constexpr uint32_t kAudioPhases = 1024;                       // 1 << phase_shift (resample.c:165)

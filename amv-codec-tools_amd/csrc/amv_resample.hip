@@ -23,6 +23,9 @@ __device__ __forceinline__ int phase_of(int pos) { return (pos >> (kPosBits - kP
 __device__ __forceinline__ int clip8(int sum) { return min(max(sum >> kFilterBits, 0), 255); }
 }  // namespace
 
+// kJpeg: the shim's closing img_convert YUV420P -> YUVJ420P (imgresample.c:671-680, the range tables of imgconvert.c:1216-1233)
+// applied to the byte where it is stored, so that the range step is no pass of its own
+template <bool kJpeg>
 __global__ __launch_bounds__(256) void amv_resample_kernel(ResamplePlanes src, ResamplePlanes dst, ResampleFilters f, uint32_t n) {
     __shared__ int16_t s_f[128];
     if (threadIdx.x < 128) s_f[threadIdx.x] = threadIdx.x < 64 ? f.h[threadIdx.x] : f.v[threadIdx.x - 64];
@@ -54,13 +57,19 @@ __global__ __launch_bounds__(256) void amv_resample_kernel(ResamplePlanes src, R
         const int h = row[sx[0]] * hf[0] + row[sx[1]] * hf[1] + row[sx[2]] * hf[2] + row[sx[3]] * hf[3];
         sum += clip8(h) * vf[j];
     }
-    out[(uint64_t)y * ostride + x] = (uint8_t)clip8(sum);
+    int v = clip8(sum);
+    if (kJpeg) {
+        const PixRange r = plane ? kPixCCcirToJpeg : kPixYCcirToJpeg;
+        v = min(max((v * r.mul + r.add) >> 10, 0), 255);
+    }
+    out[(uint64_t)y * ostride + x] = (uint8_t)v;
 }
 
-void launch_resample(const ResamplePlanes& src, const ResamplePlanes& dst, const ResampleFilters& f, uint32_t n, hipStream_t s) {
+void launch_resample(const ResamplePlanes& src, const ResamplePlanes& dst, const ResampleFilters& f, uint32_t n, hipStream_t s, bool to_jpeg) {
     if (n == 0) return;
     const uint32_t px = dst.width * dst.height;
-    hipLaunchKernelGGL(amv_resample_kernel, dim3((px + 255u) / 256u, 3, n), dim3(256), 0, s, src, dst, f, n);
+    if (to_jpeg) hipLaunchKernelGGL(amv_resample_kernel<true>, dim3((px + 255u) / 256u, 3, n), dim3(256), 0, s, src, dst, f, n);
+    else hipLaunchKernelGGL(amv_resample_kernel<false>, dim3((px + 255u) / 256u, 3, n), dim3(256), 0, s, src, dst, f, n);
 }
 
 }  // namespace amv

@@ -399,12 +399,125 @@ int amvhip_resample_yuv420_dev(amvhip_ctx *ctx, const uint8_t *d_src_y, const ui
                                uint8_t *d_dst_y, uint8_t *d_dst_cb, uint8_t *d_dst_cr,
                                uint32_t dst_y_stride, uint32_t dst_c_stride, uint64_t dst_y_frame_stride,
                                uint64_t dst_c_frame_stride, uint32_t dst_width, uint32_t dst_height, uint32_t n, void *stream);
-/* rescale to width x height, then encode: one call for ffmpeg.c's sws_scale + avcodec_encode_video pair (:757-814) */
+/* rescale to width x height, then encode: one call for ffmpeg.c's sws_scale + avcodec_encode_video pair (:757-814).  Of the
+ * shim this is the case without a conversion on either side: the bytes of the YUV420P source go rescaled to the encoder as
+ * they are.  amvhip_encode_fmt_scaled_batch_dev runs the whole shim, the conversions in front and the range step behind. */
 int amvhip_encode_yuv420_scaled_batch_dev(amvhip_ctx *ctx, const uint8_t *d_y, const uint8_t *d_cb, const uint8_t *d_cr,
                                           uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride,
                                           uint64_t c_frame_stride, uint32_t src_width, uint32_t src_height, uint32_t n,
                                           uint32_t width, uint32_t height, uint32_t qbias, uint8_t *d_blob,
                                           uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens, void *stream);
+/*
+ * Pixel formats on both sides of the codec: img_convert (libavcodec/imgconvert.c:2329-2571) for the formats that meet the
+ * AMV codec, as the sws_scale shim (imgresample.c:599-690) runs it in front of img_resample (a decoder's format ->
+ * YUV420P, :619-643) and behind it (YUV420P -> the encoder's YUVJ420P, :671-680), and as `ffmpeg -i x.amv -pix_fmt ...`
+ * runs it behind the AMV decoder.  Byte for byte the reference's arithmetic: the 10-bit FIX() constants of
+ * colorspace.h:30-109, the cm clamp, the 2x2 sums and shifts of imgconvert_template.h, the four 256-entry range tables
+ * (imgconvert.c:1216-1233) applied to the destination.
+ *
+ * AMVHIP_PIX_RGB32 is the reference's native-endian 32-bit word (a << 24 | r << 16 | g << 8 | b): B G R A in memory here;
+ * RGB565 / RGB555 are native 16-bit words.  Planar formats use three planes, every other format plane 0 alone (pass NULL,
+ * 0, 0 for the rest).  A picture is handed over flat, as in amvhip_resample_yuv420_dev: plane pointers, the row pitch of
+ * plane 0 and of the chroma planes, the frame pitch of plane 0 and of the chroma planes (bytes); frame i's planes start
+ * i frame pitches on.  Plane pointers must be 4-byte aligned.  No byte beyond a row's bytes and no row beyond the
+ * picture's height is written: pictures may be strided.  Cropping (av_picture_crop, ffmpeg.c:730-738) is pointer and size
+ * arithmetic the caller does on planar sources.  Padding (av_picture_pad) and the -r frame duplication / dropping of
+ * ffmpeg.c:705-728 are not offered.
+ *
+ * A (src, dst) pair is supported when the reference reaches it in ONE step -- a routine of convert_table
+ * (imgconvert.c:1940-2190), the planar route (:2415-2513: luma copied, chroma through ff_img_copy_plane / shrink12 /
+ * ff_shrink22, then the range tables) or the gray route (:2399-2413):
+ *   towards the encoder   YUVJ420P, YUV422P, YUVJ422P, YUV444P, YUVJ444P -> YUV420P and -> YUVJ420P;  YUV420P -> YUVJ420P;
+ *                         YUYV422, UYVY422, RGB24, BGR24, RGB32 -> YUV420P;  RGB24 -> YUVJ420P (the routine the encoder
+ *                         fuses: this entry followed by amvhip_encode_yuv420_batch_dev equals amvhip_encode_batch_dev)
+ *   from the decoder      YUVJ420P, YUV420P -> RGB24, BGR24, RGB32, RGB565, RGB555, GRAY8;  YUVJ420P -> YUV420P;
+ *                         YUV420P -> YUYV422, UYVY422
+ * Every other pair -- the same format twice; anything the reference reaches only through an intermediate picture
+ * (:2514-2571), such as YUYV422 / UYVY422 / BGR24 / RGB32 -> YUVJ420P, YUVJ420P -> YUYV422 / UYVY422, RGB <-> RGB, any
+ * source that is RGB565 / RGB555 / GRAY8, any 4:2:2 or 4:4:4 destination -- returns AMVHIP_ERR_ARG
+ * (amvhip_img_convert_supported tells, for a picture size, without a context or a device: 1 = the pair is offered at that size).
+ * Sizes: the routes into 4:2:0 from another sampling or from a packed / RGB format, and YUV420P -> YUYV422 / UYVY422, want
+ * even width and height (AMVHIP_ERR_ARG otherwise, as the encoder demands).  The routes out of 4:2:0 planes into RGB / GRAY8
+ * and between the two 4:2:0 formats take every size the decoder takes: chroma planes (w + 1) / 2 x (h + 1) / 2, the last
+ * column and row serving one pixel (the routines' tail code).  Between the two 4:2:0 formats the whole chroma planes are
+ * converted; the reference's planar route stops at w >> 1 x h >> 1 and leaves an odd picture's last chroma column and row
+ * as the destination had them.
+ *
+ * amvhip_img_convert_dev   n frames, device-resident, asynchronous on `stream`
+ * amvhip_img_convert       the same with host buffers (rows staged tight, converted, copied back row by row; synchronous)
+ * amvhip_pix_frame_bytes   bytes of one frame whose planes lie back to back with rows `stride` apart (chroma rows
+ *                          (stride + 1) / 2 apart, or `stride` for 4:4:4): the layout amvhip_decode_fmt_batch_dev writes
+ */
+#define AMVHIP_PIX_YUV420P 0
+#define AMVHIP_PIX_YUVJ420P 1
+#define AMVHIP_PIX_YUV422P 2
+#define AMVHIP_PIX_YUVJ422P 3
+#define AMVHIP_PIX_YUV444P 4
+#define AMVHIP_PIX_YUVJ444P 5
+#define AMVHIP_PIX_YUYV422 6
+#define AMVHIP_PIX_UYVY422 7
+#define AMVHIP_PIX_RGB24 8
+#define AMVHIP_PIX_BGR24 9
+#define AMVHIP_PIX_RGB32 10
+#define AMVHIP_PIX_RGB565 11
+#define AMVHIP_PIX_RGB555 12
+#define AMVHIP_PIX_GRAY8 13
+#define AMVHIP_PIX_COUNT 14
+int amvhip_img_convert_supported(int src_fmt, int dst_fmt, uint32_t width, uint32_t height);
+uint64_t amvhip_pix_frame_bytes(int fmt, uint32_t stride, uint32_t height);
+int amvhip_img_convert_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1, const uint8_t *d_src2,
+                           uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                           int dst_fmt, uint8_t *d_dst0, uint8_t *d_dst1, uint8_t *d_dst2,
+                           uint32_t dst_stride, uint32_t dst_c_stride, uint64_t dst_frame_stride, uint64_t dst_c_frame_stride,
+                           uint32_t width, uint32_t height, uint32_t n, void *stream);
+int amvhip_img_convert(amvhip_ctx *ctx, int src_fmt, const uint8_t *src0, const uint8_t *src1, const uint8_t *src2,
+                       uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                       int dst_fmt, uint8_t *dst0, uint8_t *dst1, uint8_t *dst2,
+                       uint32_t dst_stride, uint32_t dst_c_stride, uint64_t dst_frame_stride, uint64_t dst_c_frame_stride,
+                       uint32_t width, uint32_t height, uint32_t n);
+/*
+ * The shim as one call: sws_scale (imgresample.c:599-690).  Sizes differ: img_convert to YUV420P when the source is not
+ * YUV420P (:619-643), img_resample (amvhip_resample_yuv420_dev's kernel), img_convert to dst_fmt when that is not YUV420P
+ * (:671-680; towards YUVJ420P the range tables are applied where the rescaler stores its bytes).  Sizes equal: one
+ * img_convert, or a plane copy when the formats are equal too (av_picture_copy, :681-684).  Each conversion must be a
+ * supported pair at its size (AMVHIP_ERR_ARG otherwise); a rescaled picture is at least 2 x 2.  The pictures in between
+ * live in the context's workspace, grown on demand.  An odd destination size behind the rescaler: img_resample writes
+ * (w >> 1) x (h >> 1) chroma samples.  Into YUV420P / YUVJ420P the last chroma column and row of the caller's planes are
+ * then left as they were (undefined in the reference too); towards the RGB formats the routine reads
+ * those samples, which the reference leaves undefined and which are 128 here: the picture's last column and row come out
+ * without colour (GRAY8 reads no chroma; YUYV422 / UYVY422 want even sizes).
+ */
+int amvhip_sws_scale_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1, const uint8_t *d_src2,
+                         uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                         uint32_t src_width, uint32_t src_height,
+                         int dst_fmt, uint8_t *d_dst0, uint8_t *d_dst1, uint8_t *d_dst2,
+                         uint32_t dst_stride, uint32_t dst_c_stride, uint64_t dst_frame_stride, uint64_t dst_c_frame_stride,
+                         uint32_t dst_width, uint32_t dst_height, uint32_t n, void *stream);
+/*
+ * Front end + encoder in one call: ffmpeg.c:757-814 for any supported source -- the shim to YUVJ420P at width x height, then
+ * the encoder (arguments as amvhip_encode_yuv420_scaled_batch_dev).  At another size the range step is part of the
+ * rescaler's store, not a pass over memory.  At the target size RGB24 and BGR24 (frames back to back) take
+ * amvhip_encode_batch_dev's path and YUVJ420P takes amvhip_encode_yuv420_batch_dev's, byte for byte; the other sources
+ * need a one-step route to YUVJ420P there.
+ */
+int amvhip_encode_fmt_scaled_batch_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1, const uint8_t *d_src2,
+                                       uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride,
+                                       uint64_t src_c_frame_stride, uint32_t src_width, uint32_t src_height, uint32_t n,
+                                       uint32_t width, uint32_t height, uint32_t qbias, uint8_t *d_blob, uint64_t blob_cap,
+                                       uint64_t *d_offs, uint32_t *d_lens, void *stream);
+/*
+ * Decoder + back end in one call: the patched FFmpeg's amv decoder (AMVHIP_FLAG_FFMPEG, required: AMVHIP_ERR_ARG without)
+ * into workspace planes, then img_convert YUVJ420P -> dst_fmt (yuvj420p_to_*, imgconvert.c:1977-1993; the planar route for
+ * YUV420P; the gray route for GRAY8): what `ffmpeg -i x.amv [-pix_fmt rgb24|bgr24|rgb32|rgb565] out` hands its next stage
+ * (README:10-18).  Other arguments as amvhip_decode_batch_dev.  d_out: n frames of amvhip_pix_frame_bytes(dst_fmt,
+ * out_stride, height) bytes, rows out_stride apart (for YUV420P: the Y plane, then Cb and Cr with rows (out_stride + 1) / 2
+ * apart); bytes between a row's end and out_stride stay as they were.  AMVHIP_FLAG_FFMPEG_KEEP is refused (the caller's
+ * buffer is not in plane form); damaged frames convert what the plain compat mode leaves, zeros behind the failing MCU.
+ */
+int amvhip_decode_fmt_batch_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes,
+                                const uint64_t *d_offs, const uint32_t *d_lens, uint32_t n,
+                                uint32_t width, uint32_t height, uint32_t flags, int dst_fmt,
+                                uint8_t *d_out, uint32_t out_stride, int32_t *d_status, void *stream);
 /*
  * The audio resampler in front of the ADPCM encoder: audio_resample (libavcodec/resample.c:129-242) over av_resample
  * (resample2.c:182-324), what ffmpeg.c:1639-1641 / :502 run for `-ac 1 -ar 22050` (AMVmuxer/Makefile:16).  16-tap (at
@@ -557,7 +670,8 @@ int amvhip_mux_close(amvhip_muxer *m);
 #define AMVHIP_K_PACK_SERIAL 9
 #define AMVHIP_K_COMPACT 10   /* amv_scan_kernel + amv_gather_kernel, timed as one */
 #define AMVHIP_K_AUDIO_RESAMPLE 11   /* amv_audio_tiles_kernel + amv_audio_resample_kernel, timed as one */
-#define AMVHIP_K_COUNT 12
+#define AMVHIP_K_PIXFMT 12   /* the amv_pix_*_kernel family (amvhip_img_convert_dev and the entries built on it) */
+#define AMVHIP_K_COUNT 13
 void amvhip_prof_enable(amvhip_ctx *ctx, int on);
 void amvhip_prof_reset(amvhip_ctx *ctx);
 int amvhip_prof_read(amvhip_ctx *ctx, int kernel, uint64_t *launches, double *total_ms);
