@@ -121,7 +121,7 @@ __global__ __launch_bounds__(kWave) void amv_huffman_kernel(
 
     // Work items base .. : with a list (frames the synchronising kernel handed back) item p is frame list[p],
     // p < *list_count; without one, item p is frame p, p < n.  by_slot: the coefficient lines of item p go to slot
-    // p - base of a workspace that holds one round of items (amvhip_api.hip), else to the frame's own place.
+    // p - base of a workspace that holds one round of items (amvhip_decode.hip), else to the frame's own place.
     const uint32_t lane = threadIdx.x;
     const uint32_t f0 = base + blockIdx.x * kWave;
     const bool ok_in_blocks = (by_slot & 2u) != 0u;   // AMVHIP_FLAG_FFMPEG_KEEP: nmcu_ok counts whole blocks (amv_kernels.h)

@@ -1145,7 +1145,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
             } else {
                 status[frame] = (int32_t)st;
                 nmcu_ok[frame] = out.ok_in_blocks ? good_blocks : good_blocks / 6u;
-                out.rec_count[frame] = rec_total | ((uint32_t)(L - 1) << 24);   // (a frame holds < 2^21 records: amvhip_api.hip)
+                out.rec_count[frame] = rec_total | ((uint32_t)(L - 1) << 24);   // (a frame holds < 2^21 records: amv_host_plan.h)
             }
         }
     }   // next task

@@ -1,0 +1,289 @@
+// amv_host_plan.h -- the host side's arithmetic: table images, buffer sizes, filter banks, pixel-format routes.
+//
+// Plain C++ that no device call enters, so that a CPU program can walk it (tests/c/host_plan_test.cc).  The files of
+// the C ABI take the sizes and the tables they hand to the kernels from here.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <vector>
+
+#include "../../include/amvhip.h"
+#include "amv_tables.h"
+
+namespace amv {
+
+inline int size_ok(uint32_t w, uint32_t h) { return w > 0 && h > 0 && w <= AMVHIP_MAX_DIM && h <= AMVHIP_MAX_DIM; }
+
+// ---- table images ---------------------------------------------------------------------------
+
+inline const uint8_t* symbols_of(int t) {
+    return t < 2 ? kHuffDcSymbols : (t == 2 ? kHuffAcLumaSymbols : kHuffAcChromaSymbols);
+}
+
+// canonical code assignment of JPEG Annex C (what AmvJpeg.c:1454-1481 and mjpeg.c:129-147 both
+// derive): codes of each length are consecutive, and the first code of length l+1 is
+// (last code of length l + 1) << 1
+inline void build_images(HuffDecodeImage& dec, HuffEncodeImage& enc) {
+    memset(&dec, 0, sizeof dec);
+    memset(&enc, 0, sizeof enc);
+    int pages = 0;
+    for (int t = 0; t < 4; ++t) {
+        const uint8_t* syms = symbols_of(t);
+        uint32_t code = 0;
+        int k = 0;
+        for (int len = 1; len <= 16; ++len) {
+            for (int j = 0; j < kHuffCount[t][len - 1]; ++j, ++code) {
+                const uint32_t sym = syms[k++];
+                enc.code[t][sym] = code | ((uint32_t)len << 16);
+                const uint16_t entry = (uint16_t)(sym | ((uint32_t)len << 8));
+                if (len <= kLut1Bits) {
+                    const uint32_t lo = code << (kLut1Bits - len);
+                    for (uint32_t x = 0; x < (1u << (kLut1Bits - len)); ++x) dec.l1[t][lo + x] = entry;
+                } else {
+                    const int rest = len - kLut1Bits;  // 1..7
+                    const uint32_t prefix = code >> rest;
+                    if (!(dec.l1[t][prefix] & 0x8000u)) dec.l1[t][prefix] = (uint16_t)(0x8000u | (uint32_t)pages++);
+                    const uint32_t page = dec.l1[t][prefix] & 0xffu;
+                    const uint32_t lo = (code & ((1u << rest) - 1u)) << (kLut2Bits - rest);
+                    for (uint32_t x = 0; x < (1u << (kLut2Bits - rest)); ++x) dec.l2[page][lo + x] = entry;
+                }
+            }
+            code <<= 1;
+        }
+    }
+    if (pages > kLut2Pages) abort();  // static property of the K.3 tables (11 pages)
+    // the one-lane-per-frame walk's form (amv_tables.h)
+    auto fast = [](uint16_t e, int t) -> uint32_t {
+        const uint32_t len = (e >> 8) & 31u, sym = e & 0xffu, size = sym & 15u;
+        if (len == 0) return kFastInvalid | (1u << 24);   // one bit used, no advance: what a guessed start does with it
+        const bool dc = t < 2;
+        const uint32_t adv = dc ? 1u : (sym == 0 ? kFastEobAdvance : (sym >> 4) + 1u);
+        return size | ((dc || size) ? kFastEmit : 0u) | (adv << 16) | ((len + size) << 24);
+    };
+    for (int t = 0; t < 4; ++t) {
+        for (int i = 0; i < (1 << kLut1Bits); ++i) {
+            const uint16_t e = dec.l1[t][i];
+            dec.fast[t][i] = (e & 0x8000u) ? 0u : fast(e, t);
+        }
+        for (uint32_t w16 = kFastLongFirst; w16 < 0x10000u; ++w16) {
+            const uint16_t e1 = dec.l1[t][w16 >> (16 - kLut1Bits)];
+            if (e1 & 0x8000u)
+                dec.fast[t][kFastM2Word + 1u + (w16 - kFastLongFirst)] =
+                    fast(dec.l2[e1 & 0xffu][(w16 >> (16 - kLut1Bits - kLut2Bits)) & ((1u << kLut2Bits) - 1u)], t);
+        }
+    }
+}
+
+// ---- video decode: what the entropy stage of n frames in blob_bytes of chunks is given -------------------------------
+
+struct EntropyPlan {
+    uint64_t ws_lines;    // 16-byte pieces of the unstuffed scans' workspace
+    uint32_t hi_rec;      // most record words a frame gets
+    uint32_t add_rec;     // record words a frame gets on top of two per byte of its chunk
+    uint64_t cap_lines;   // 128-byte lines of the record space
+    uint32_t segs;        // MCU-row segments per frame
+};
+
+inline EntropyPlan entropy_plan(uint32_t n, uint64_t blob_bytes, const FrameGeom& g) {
+    EntropyPlan p;
+    // Window per frame for the unstuffed scan in the global workspace: the frame's own chunk length + the zeroed tail of its
+    // last 16-byte piece + a piece of slack, in 16-byte pieces laid out on the device (round 4; 5/16 byte per pixel for every
+    // frame before: a chunk over 1.6x the usual size went to the serial kernel, the others used 60 % of their window).  The
+    // total is bounded by what the chunks occupy; chunks that overlap in the blob make the layout run out, and the frames
+    // past its end take the serial kernel.
+    p.ws_lines = (blob_bytes + (uint64_t)n * 48u) / 16u + 4u;
+    if (p.ws_lines > 0xffffffffull) p.ws_lines = 0xffffffffull;
+    // Between the two stages coefficients travel as records (one word per DC and per non-zero AC coefficient), every frame
+    // in space of its own, sized from ITS chunk (round 4; one stride for all, from the batch's mean chunk, before: a heavy
+    // frame in a light stream was silently decoded by the one-lane serial kernel).  A record costs at least 3 bits of scan,
+    // in practice ~6, and every block has a DC symbol and (nearly always) an end-of-block symbol, which take a slot each in
+    // the one-lane kernel's stride-aligned form: 2 words per byte of chunk + 2 per block + a stride's slack (never more than a
+    // frame with every coefficient non-zero could fill; a frame denser than 2 records per byte goes to the serial kernel), in
+    // whole 128-byte lines.  The space is laid out on
+    // the device (the lengths are there); its total is bounded here by what the chunks occupy (chunks that overlap make the
+    // sum larger than that: the layout saturates and the frames past the end are handed to the serial kernel).
+    p.hi_rec = (g.blocks * 66u + 95u) & ~31u;   // every coefficient of every block non-zero, an end-of-block slot each
+    p.add_rec = g.blocks * 2u + 64u;
+    p.cap_lines = (uint64_t)n * (p.hi_rec / 32u);
+    const uint64_t by_stream = (2u * blob_bytes + (uint64_t)n * (p.add_rec + 31u)) / 32u + 1u;
+    if (by_stream < p.cap_lines) p.cap_lines = by_stream;
+    if (p.cap_lines > 0xffffffffull) p.cap_lines = 0xffffffffull;
+    p.segs = ((g.mcu_cols + 9u) / 10u) * g.mcu_rows;
+    return p;
+}
+
+// Frames per round of a fall-back route (the context keeps a round's worth of dense coefficient lines): the whole batch
+// up to `most` frames, beyond `parts` times that a `parts`-th of it, else `most`.  Never more than 2 GB of lines, though,
+// nor fewer than 64 frames: at 640x480 a block line is 128 bytes x 7 200 blocks, and 16 384 frames of that would be 15 GB
+// kept for rounds that usually find nothing.
+inline uint32_t fallback_round(uint32_t n, const FrameGeom& g, uint32_t most, uint32_t parts) {
+    uint32_t round = n <= most ? n : (n / parts > most ? (n + parts - 1u) / parts : most);
+    const uint64_t by_bytes = (2ull << 30) / ((uint64_t)g.blocks * 128u);
+    if (round > by_bytes) round = by_bytes > 64u ? (uint32_t)by_bytes : 64u;
+    return round < n ? round : n;
+}
+
+// ---- picture rescale --------------------------------------------------------------------------
+
+// av_build_filter(filter, factor, NB_TAPS = 4, NB_PHASES = 16, 1 << FILTER_BITS, type 0) -- libavcodec/resample2.c:93-140
+// as img_resample_full_init calls it (imgresample.c:468-471): cubic, first-order derivative -0.5, every phase
+// normalised to 256; host arithmetic in double / float exactly as there.
+inline void build_resample_filter(int16_t* filter, uint32_t out_size, uint32_t in_size) {
+    double factor = (float)out_size / (float)in_size;
+    if (factor > 1.0) factor = 1.0;                          // upsampling only interpolates
+    for (int ph = 0; ph < 16; ++ph) {
+        double tab[4], norm = 0;
+        for (int i = 0; i < 4; ++i) {
+            const float d = -0.5f;
+            const double x = fabs(((double)(i - 1) - (double)ph / 16) * factor);
+            const double y = x < 1.0 ? 1 - 3 * x * x + 2 * x * x * x + d * (-x * x + x * x * x)
+                                     : d * (-4 + 8 * x - 5 * x * x + x * x * x);
+            tab[i] = y;
+            norm += y;
+        }
+        for (int i = 0; i < 4; ++i) {
+            const long v = lrintf((float)(tab[i] * 256 / norm));
+            filter[ph * 4 + i] = (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v));
+        }
+    }
+}
+
+// the 16.16 step through the source per destination sample (imgresample.c:465-466)
+inline int resample_incr(uint32_t src_size, uint32_t dst_size) { return (int)(((uint64_t)src_size << 16) / dst_size); }
+
+// ---- pixel formats: the routes of img_convert ---------------------------------------------------------
+
+enum PixRoute { kRouteNone = 0, kRoutePlanes, kRouteGray, kRoutePackedIn, kRoutePackedOut, kRouteRgbIn, kRouteRgbOut };
+
+inline bool pix_planar_yuv(int f) { return f >= AMVHIP_PIX_YUV420P && f <= AMVHIP_PIX_YUVJ444P; }
+inline bool pix_jpeg(int f) { return f == AMVHIP_PIX_YUVJ420P || f == AMVHIP_PIX_YUVJ422P || f == AMVHIP_PIX_YUVJ444P; }
+inline bool pix_420(int f) { return f == AMVHIP_PIX_YUV420P || f == AMVHIP_PIX_YUVJ420P; }
+inline bool pix_444(int f) { return f == AMVHIP_PIX_YUV444P || f == AMVHIP_PIX_YUVJ444P; }
+inline uint32_t pix_bpp(int f) {   // bytes per pixel of plane 0
+    switch (f) {
+        case AMVHIP_PIX_YUYV422: case AMVHIP_PIX_UYVY422: case AMVHIP_PIX_RGB565: case AMVHIP_PIX_RGB555: return 2;
+        case AMVHIP_PIX_RGB24: case AMVHIP_PIX_BGR24: return 3;
+        case AMVHIP_PIX_RGB32: return 4;
+        default: return 1;
+    }
+}
+
+// the routes the reference reaches in one step: a routine of convert_table (imgconvert.c:1940-2190), the planar route
+// (:2415-2513) or the gray route (:2399-2413)
+inline PixRoute pix_route(int src, int dst) {
+    if (src < 0 || src >= AMVHIP_PIX_COUNT || dst < 0 || dst >= AMVHIP_PIX_COUNT || src == dst) return kRouteNone;
+    if (pix_planar_yuv(src) && pix_420(dst)) return kRoutePlanes;
+    if (pix_420(src) && dst == AMVHIP_PIX_GRAY8) return kRouteGray;
+    if ((src == AMVHIP_PIX_YUYV422 || src == AMVHIP_PIX_UYVY422) && dst == AMVHIP_PIX_YUV420P) return kRoutePackedIn;
+    if (src == AMVHIP_PIX_YUV420P && (dst == AMVHIP_PIX_YUYV422 || dst == AMVHIP_PIX_UYVY422)) return kRoutePackedOut;
+    if ((src == AMVHIP_PIX_RGB24 || src == AMVHIP_PIX_BGR24 || src == AMVHIP_PIX_RGB32) && dst == AMVHIP_PIX_YUV420P) return kRouteRgbIn;
+    if (src == AMVHIP_PIX_RGB24 && dst == AMVHIP_PIX_YUVJ420P) return kRouteRgbIn;
+    if (pix_420(src) && (dst == AMVHIP_PIX_RGB24 || dst == AMVHIP_PIX_BGR24 || dst == AMVHIP_PIX_RGB32 || dst == AMVHIP_PIX_RGB565 ||
+                         dst == AMVHIP_PIX_RGB555))
+        return kRouteRgbOut;
+    return kRouteNone;
+}
+
+// rows and bytes per row of plane p of a w x h picture; rows 0: the format has no such plane.  4:2:0 chroma rounds up (what
+// the decoder makes, mjpegdec.c:312); a to-4:2:0 route from another sampling wants even sizes anyway
+inline void pix_plane_size(int f, uint32_t p, uint32_t w, uint32_t h, uint32_t* row_bytes, uint32_t* rows) {
+    *row_bytes = 0;
+    *rows = 0;
+    if (p == 0) { *row_bytes = w * pix_bpp(f); *rows = h; return; }
+    if (!pix_planar_yuv(f)) return;
+    *row_bytes = pix_444(f) ? w : (w + 1) / 2;
+    *rows = pix_420(f) ? (h + 1) / 2 : h;
+}
+
+// what a pair asks of the picture size (0: refused)
+inline int pix_size_ok(int src_fmt, int dst_fmt, uint32_t w, uint32_t h) {
+    if (!size_ok(w, h)) return 0;
+    const PixRoute r = pix_route(src_fmt, dst_fmt);
+    const bool any = r == kRouteGray || r == kRouteRgbOut || (r == kRoutePlanes && pix_420(src_fmt));
+    return any || (!(w & 1) && !(h & 1));
+}
+
+// bytes of one frame: plane 0 with rows `stride` apart, the chroma planes (if any) behind it at their own width
+inline uint64_t pix_frame_bytes(int fmt, uint32_t stride, uint32_t height) {
+    if (fmt < 0 || fmt >= AMVHIP_PIX_COUNT) return 0;
+    if (!pix_planar_yuv(fmt)) return (uint64_t)stride * height;
+    const uint64_t cs = pix_444(fmt) ? stride : (stride + 1) / 2, cr = pix_420(fmt) ? (height + 1) / 2 : height;
+    return (uint64_t)stride * height + 2 * cs * cr;
+}
+
+// ---- audio resample -----------------------------------------------------------------------------
+
+constexpr uint32_t kBankPhases = 1024;   // kAudioPhases of amv_kernels.h (the audio entry points assert that they agree)
+
+// av_resample_init (resample2.c:183-190) as audio_resample_init calls it (resample.c:165): 16 taps, cutoff 0.8
+inline uint32_t audio_filter_length(uint32_t in_rate, uint32_t out_rate) {
+    const double f = out_rate * 0.8 / in_rate, factor = f > 1.0 ? 1.0 : f;
+    const int fl = (int)ceil(16 / factor);
+    return fl > 1 ? (uint32_t)fl : 1u;
+}
+
+inline int64_t audio_index0(uint32_t fl) { return -(int64_t)kBankPhases * ((fl - 1) / 2); }
+
+inline double kaiser_bessel(double x) {   // bessel() of resample2.c:74-85
+    double v = 1, t = 1;
+    x = x * x / 4;
+    for (int i = 1; i < 50; i++) {
+        t *= x / (i * i);
+        v += t;
+    }
+    return v;
+}
+
+// av_build_filter(filter, factor, fl, 1024, 1 << 15, 9) -- resample2.c:93-139, the Kaiser sibling of build_resample_filter:
+// same double / float operations in the same order; rows padded with zero taps to fl_pad
+inline void build_audio_bank(std::vector<int16_t>& bank, uint32_t in_rate, uint32_t out_rate, uint32_t fl, uint32_t fl_pad) {
+    const double f = out_rate * 0.8 / in_rate;
+    const double factor = f > 1.0 ? 1.0 : f;
+    const int center = ((int)fl - 1) / 2;
+    std::vector<double> tab(fl);
+    bank.assign((size_t)kBankPhases * fl_pad, 0);
+    for (int ph = 0; ph < (int)kBankPhases; ph++) {
+        double norm = 0;
+        for (int i = 0; i < (int)fl; i++) {
+            const double x = M_PI * ((double)(i - center) - (double)ph / (int)kBankPhases) * factor;
+            double y = x == 0 ? 1.0 : sin(x) / x;
+            const double w = 2.0 * x / (factor * (int)fl * M_PI);
+            y *= kaiser_bessel(9 * sqrt(1 - w * w > 0 ? 1 - w * w : 0));
+            tab[i] = y;
+            norm += y;
+        }
+        for (int i = 0; i < (int)fl; i++) {
+            const long v = lrintf((float)(tab[i] * (1 << 15) / norm));
+            bank[(size_t)ph * fl_pad + i] = (int16_t)(v < -32768 ? -32768 : (v > 32767 ? 32767 : v));
+        }
+    }
+}
+
+// the state av_resample leaves after `count` outputs (resample2.c:288-293, :307-316): index and frac move on, the input
+// frames the index has passed are consumed (returned)
+inline uint64_t audio_advance(int64_t& index, uint64_t& frac, uint64_t count, uint64_t D, uint32_t out_rate) {
+    const uint64_t total = frac + count * D;
+    int64_t next = index + (int64_t)(total / out_rate);
+    frac = total % out_rate;
+    const uint64_t consumed = next > 0 ? (uint64_t)next >> 10 : 0;
+    if (next >= 0) next &= kBankPhases - 1;
+    index = next;
+    return consumed;
+}
+
+// ---- ADPCM ------------------------------------------------------------------------------------
+
+// launched sweeps of the chained encode of n chunks: until the list is expected to be a couple of hundred entries (it
+// starts at ~0.41 n and shrinks ~3.7x per sweep on ordinary audio; counted here as n shrinking 3.3x).  The front sweep
+// behind them (a workgroup per entry, four chunks looked ahead) and the one-workgroup settle kernel take the rest
+inline uint32_t adpcm_default_sweeps(uint32_t n) {
+    uint32_t sweeps = 0;
+    for (uint64_t left = n; left > 512u; left = left * 3u / 10u) ++sweeps;
+    if (n <= 64u) sweeps = 0u;
+    return sweeps;
+}
+
+}  // namespace amv

@@ -70,7 +70,7 @@ void launch_layout(const uint32_t* lens, uint32_t n, const LayoutSpec& a, const 
                    bool force_large, hipStream_t s);
 // Frames whose chunk is more than twice the batch's mean chunk (by the pieces the layout gave their scans: ws_line) ->
 // heavy[0 .. count[0]), the others -> light[0 .. count[1]); count[0..1] zeroed by the caller.  A chip-filling batch decodes
-// the light ones one lane per frame and the heavy ones with several lanes each (amvhip_api.hip: entropy_front).
+// the light ones one lane per frame and the heavy ones with several lanes each (amvhip_decode.hip: entropy_front).
 void launch_split_by_weight(const uint32_t* lens, uint32_t n, const uint32_t* ws_line, uint32_t* heavy, uint32_t* light, uint32_t* count,
                             hipStream_t s);
 // list/list_count: optional frame list; *queue: a zeroed task counter per launch

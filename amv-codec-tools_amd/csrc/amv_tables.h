@@ -92,7 +92,7 @@ static constexpr int16_t kSinQ14[65] = {
     13395, 13623, 13842, 14053, 14256, 14449, 14635, 14811, 14978, 15137, 15286, 15426, 15557,
     15679, 15791, 15893, 15986, 16069, 16143, 16207, 16261, 16305, 16340, 16364, 16379, 16384};
 
-// ---- device-side table images built once by the host (amvhip_api.hip) ------------------
+// ---- device-side table images built once by the host (amv_host_plan.h) ----------------
 
 // Two-level Huffman decode tables.  Level 1 is indexed by the next 9 bits, level 2 by the
 // 7 bits after those.  Entry: bits 0-7 symbol (or level-2 page), bits 8-12 code length,

@@ -1,0 +1,257 @@
+// amvhip_encode.hip -- video encode behind the C ABI: pixels or planes to chunks, the picture rescaler in front of it.
+#include "amvhip_ctx.h"
+
+using namespace amv;
+
+extern "C" int amvhip_encode_coefs_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                                       uint32_t qbias, int16_t* d_coef, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!encode_size_ok(w, h, qbias) || pix_stride < w * 3 || (n && (!d_pix || !d_coef)))
+        return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
+    if ((uintptr_t)d_coef & 15u) return fail(c, AMVHIP_ERR_ARG, "encode: coef must be 16-byte aligned");
+    if (int r = use_device(c)) return r;
+    const FrameGeom g = make_geom(w, h);
+    {
+        Timed t(c, AMVHIP_K_FDCT, (hipStream_t)stream);
+        launch_forward(d_pix, pix_stride, is_bgr, n, kAllFrames, n, g, qbias, d_coef, (hipStream_t)stream);
+    }
+    return check_launch(c, "forward");
+}
+
+// Pixels -> chunks for n frames, RGB (yuv == nullptr) or planar YUVJ420P (the context is locked).  The one-kernel
+// encoder takes the batch; what it hands back -- and the whole batch in AMVHIP_ENTROPY_SERIAL mode -- goes through
+// amv_forward_kernel + amv_pack_kernel a round of dense lines at a time (with a list the count is on the device: the
+// rounds past it find nothing to do and leave at once -- usually all of them).
+static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n,
+                       const FrameGeom& g, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
+                       hipStream_t stream) {
+    const uint32_t bound = amvhip_encode_bound(g.width, g.height);
+    const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
+    const uint32_t round = fallback_round(n, g, 1024u, 2u);
+    if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
+    if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
+    if (int r = ensure(c, c->flag, 16)) return r;
+    if (int r = ensure(c, c->enc_retry, ((size_t)n + 4) * 8)) return r;   // (the encoder's own: the decode path's counter is read by amvhip_entropy_stats)
+    uint32_t* retry_count = (uint32_t*)c->enc_retry.p;
+    uint32_t* retry_list = retry_count + 8;
+    HIP_TRY(c, hipMemsetAsync(retry_count, 0, 32, stream));
+    const bool fused = c->entropy_mode != AMVHIP_ENTROPY_SERIAL;
+    if (fused) {
+        Timed t(c, AMVHIP_K_PACK, stream);
+        launch_encode_frames(d_pix, pix_stride, is_bgr, yuv, n, g, qbias, book, (uint8_t*)c->tmp.p, bound, d_lens, retry_list,
+                             retry_count, stream);
+    }
+    if (int r = check_launch(c, "encode_frames")) return r;
+    for (uint32_t base = 0; base < n; base += round) {
+        const uint32_t items = n - base < round ? n - base : round;
+        const FrameSel sel{fused ? retry_list : nullptr, fused ? retry_count : nullptr, base, items};
+        {
+            Timed t(c, AMVHIP_K_FDCT, stream);
+            if (yuv) launch_forward_yuv(*yuv, n, sel, items, g, qbias, (int16_t*)c->coef.p, stream);
+            else launch_forward(d_pix, pix_stride, is_bgr, n, sel, items, g, qbias, (int16_t*)c->coef.p, stream);
+        }
+        {
+            Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
+            launch_pack((const int16_t*)c->coef.p, n, sel, items, g, book, (uint8_t*)c->tmp.p, bound, d_lens, stream);
+        }
+        if (int r = check_launch(c, "forward + pack")) return r;
+    }
+    {
+        Timed t(c, AMVHIP_K_COMPACT, stream);
+        launch_compact((const uint8_t*)c->tmp.p, bound, d_lens, n, d_offs, d_blob, blob_cap, (int32_t*)c->flag.p, stream);
+    }
+    return check_launch(c, "compact");
+}
+
+extern "C" int amvhip_encode_batch_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                                       uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!encode_size_ok(w, h, qbias) || pix_stride < w * 3 || (n && !d_pix))
+        return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
+    if (n && (!d_blob || !d_offs || !d_lens)) return fail(c, AMVHIP_ERR_ARG, "encode: null output");
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return encode_core(c, d_pix, pix_stride, is_bgr, nullptr, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens,
+                       (hipStream_t)stream);
+}
+
+static int encode_yuv_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr, uint32_t y_stride, uint32_t c_stride,
+                          uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t rows422, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias,
+                          uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!encode_size_ok(w, h, qbias) || y_stride < w || c_stride < w / 2 ||
+        (n && (!d_y || !d_cb || !d_cr || !d_blob || !d_offs || !d_lens)))
+        return fail(c, AMVHIP_ERR_ARG, "encode_yuv: bad argument (width/height must be even)");
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const YuvSource yuv{d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, rows422};
+    return encode_core(c, nullptr, 0u, 0, &yuv, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+}
+
+extern "C" int amvhip_encode_yuv420_batch_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr, uint32_t y_stride,
+                                              uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
+                                              uint32_t h, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
+                                              void* stream) {
+    return encode_yuv_dev(c, d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, d_blob, blob_cap, d_offs,
+                          d_lens, stream);
+}
+
+extern "C" int amvhip_encode_yuv422_batch_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr, uint32_t y_stride,
+                                              uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
+                                              uint32_t h, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
+                                              void* stream) {
+    return encode_yuv_dev(c, d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 1u, n, w, h, qbias, d_blob, blob_cap, d_offs,
+                          d_lens, stream);
+}
+
+// the device-to-host half of the host-buffer encoders: offs/lens, then the chunks
+static int encode_fetch(amvhip_ctx* c, hipStream_t hs, uint32_t n, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
+    int32_t overflow = 0;
+    HIP_TRY(c, hipMemcpyAsync(offs, c->h_offs.p, (size_t)n * 8, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(c, hipMemcpyAsync(lens, c->h_lens.p, (size_t)n * 4, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(c, hipMemcpyAsync(&overflow, c->flag.p, 4, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(c, hipStreamSynchronize(hs));
+    const uint64_t total = offs[n - 1] + lens[n - 1];
+    if (overflow || total > blob_cap)
+        return fail(c, AMVHIP_ERR_SPACE, "encode: the chunks need more than the %llu bytes of blob", (unsigned long long)blob_cap);
+    HIP_TRY(c, hipMemcpyAsync(blob, c->h_out.p, total, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(c, hipStreamSynchronize(hs));
+    return AMVHIP_OK;
+}
+
+extern "C" int amvhip_encode_batch(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                                   uint32_t qbias, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (n && (!pix || !blob || !offs || !lens)) return fail(c, AMVHIP_ERR_ARG, "encode: null argument");
+    if (n == 0) return AMVHIP_OK;
+    hipStream_t hs;
+    if (int r = host_stream(c, &hs)) return r;
+    const size_t in_bytes = (size_t)pix_stride * h * n;
+    std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
+    if (int r = stage(c, c->h_in, in_bytes, pix, in_bytes, hs)) return r;
+    if (int r = ensure(c, c->h_out, blob_cap + 16)) return r;
+    if (int r = ensure(c, c->h_offs, (size_t)n * 8)) return r;
+    if (int r = ensure(c, c->h_lens, (size_t)n * 4)) return r;
+    if (int r = amvhip_encode_batch_dev(c, (const uint8_t*)c->h_in.p, pix_stride, is_bgr, n, w, h, qbias,
+                                        (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p,
+                                        (uint32_t*)c->h_lens.p, hs))
+        return r;
+    return encode_fetch(c, hs, n, blob, blob_cap, offs, lens);
+}
+
+static int encode_yuv_host(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride, uint32_t c_stride,
+                           uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t rows422, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias,
+                           uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!size_ok(w, h) || (w & 1) || (h & 1) || y_stride < w || c_stride < w / 2 || (n && (!y || !cb || !cr || !blob || !offs || !lens)))
+        return fail(c, AMVHIP_ERR_ARG, "encode_yuv420: bad argument");
+    if (n == 0) return AMVHIP_OK;
+    hipStream_t hs;
+    if (int r = host_stream(c, &hs)) return r;
+    // staged tight: Y w*h, Cb, Cr (w/2 x h/2, or w/2 x h when the source is 4:2:2) per frame
+    const uint32_t cw = w / 2, chh = rows422 ? h : h / 2;
+    const uint64_t fb = (uint64_t)w * h + 2ull * cw * chh;
+    std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
+    if (int r = ensure(c, c->h_in, fb * n)) return r;
+    if (int r = ensure(c, c->h_out, blob_cap + 16)) return r;
+    if (int r = ensure(c, c->h_offs, (size_t)n * 8)) return r;
+    if (int r = ensure(c, c->h_lens, (size_t)n * 4)) return r;
+    uint8_t* d = (uint8_t*)c->h_in.p;
+    for (uint32_t i = 0; i < n; ++i) {
+        HIP_TRY(c, hipMemcpy2DAsync(d + i * fb, w, y + i * y_frame_stride, y_stride, w, h, hipMemcpyHostToDevice, hs));
+        HIP_TRY(c, hipMemcpy2DAsync(d + i * fb + (uint64_t)w * h, cw, cb + i * c_frame_stride, c_stride, cw, chh, hipMemcpyHostToDevice, hs));
+        HIP_TRY(c, hipMemcpy2DAsync(d + i * fb + (uint64_t)w * h + (uint64_t)cw * chh, cw, cr + i * c_frame_stride, c_stride, cw, chh, hipMemcpyHostToDevice, hs));
+    }
+    if (int r = encode_yuv_dev(c, d, d + (uint64_t)w * h, d + (uint64_t)w * h + (uint64_t)cw * chh, w, cw, fb, fb, rows422, n, w, h, qbias,
+                               (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs))
+        return r;
+    return encode_fetch(c, hs, n, blob, blob_cap, offs, lens);
+}
+
+extern "C" int amvhip_encode_yuv420_batch(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride,
+                                          uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
+                                          uint32_t h, uint32_t qbias, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
+    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, blob, blob_cap, offs, lens);
+}
+
+extern "C" int amvhip_encode_yuv422_batch(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride,
+                                          uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
+                                          uint32_t h, uint32_t qbias, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
+    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 1u, n, w, h, qbias, blob, blob_cap, offs, lens);
+}
+
+// ---- picture rescale ------------------------------------------------------------------------------------------------
+
+static ResamplePlanes resample_planes(const PixPicture& p, uint32_t w, uint32_t h) {
+    return ResamplePlanes{p.p[0], p.p[1], p.p[2], p.stride[0], p.stride[1], p.frame[0], p.frame[1], w, h};
+}
+
+// img_resample_full_init (imgresample.c:425-472) for one pair of sizes
+static ResampleFilters resample_filters(uint32_t src_w, uint32_t src_h, uint32_t dst_w, uint32_t dst_h) {
+    ResampleFilters f;
+    f.h_incr = resample_incr(src_w, dst_w);
+    f.v_incr = resample_incr(src_h, dst_h);
+    build_resample_filter(f.h, dst_w, src_w);
+    build_resample_filter(f.v, dst_h, src_h);
+    return f;
+}
+
+// n frames, 65535 (the launch's most) at a time
+int amv::resample_launch(amvhip_ctx* c, const PixPicture& src, uint32_t src_w, uint32_t src_h, const PixPicture& dst, uint32_t dst_w,
+                         uint32_t dst_h, uint32_t n, bool to_jpeg, hipStream_t st) {
+    const ResampleFilters f = resample_filters(src_w, src_h, dst_w, dst_h);
+    for (uint32_t base = 0; base < n; base += 65535u) {
+        ResamplePlanes s = resample_planes(src, src_w, src_h), d = resample_planes(dst, dst_w, dst_h);
+        s.y += base * s.y_frame; s.cb += base * s.c_frame; s.cr += base * s.c_frame;
+        d.y += base * d.y_frame; d.cb += base * d.c_frame; d.cr += base * d.c_frame;
+        launch_resample(s, d, f, n - base < 65535u ? n - base : 65535u, st, to_jpeg);
+    }
+    return check_launch(c, "resample");
+}
+
+extern "C" int amvhip_resample_yuv420_dev(amvhip_ctx* c, const uint8_t* d_src_y, const uint8_t* d_src_cb, const uint8_t* d_src_cr,
+                                          uint32_t src_y_stride, uint32_t src_c_stride, uint64_t src_y_frame, uint64_t src_c_frame,
+                                          uint32_t src_w, uint32_t src_h, uint8_t* d_dst_y, uint8_t* d_dst_cb, uint8_t* d_dst_cr,
+                                          uint32_t dst_y_stride, uint32_t dst_c_stride, uint64_t dst_y_frame, uint64_t dst_c_frame,
+                                          uint32_t dst_w, uint32_t dst_h, uint32_t n, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!size_ok(src_w, src_h) || !size_ok(dst_w, dst_h) || src_w < 2 || src_h < 2 || dst_w < 2 || dst_h < 2 ||
+        src_y_stride < src_w || src_c_stride < src_w / 2 || dst_y_stride < dst_w || dst_c_stride < dst_w / 2 ||
+        (n && (!d_src_y || !d_src_cb || !d_src_cr || !d_dst_y || !d_dst_cb || !d_dst_cr)))
+        return fail(c, AMVHIP_ERR_ARG, "resample: bad argument");
+    if (n == 0) return AMVHIP_OK;
+    if (n > 65535u) return fail(c, AMVHIP_ERR_ARG, "resample: at most 65535 frames per call");
+    if (int r = use_device(c)) return r;
+    return resample_launch(c, make_picture(d_src_y, d_src_cb, d_src_cr, src_y_stride, src_c_stride, src_y_frame, src_c_frame), src_w, src_h,
+                           make_picture(d_dst_y, d_dst_cb, d_dst_cr, dst_y_stride, dst_c_stride, dst_y_frame, dst_c_frame), dst_w, dst_h, n,
+                           false, (hipStream_t)stream);
+}
+
+int amv::encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap,
+                            uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
+    const YuvSource yuv = yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h));
+    return encode_core(c, nullptr, 0u, 0, &yuv, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens, stream);
+}
+
+// rescale + encode in one call: what ffmpeg.c:757-814 does per picture (sws_scale, then avcodec_encode_video) for a
+// source that is not the target size.  The rescaled planes live in the context's workspace.
+extern "C" int amvhip_encode_yuv420_scaled_batch_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr,
+                                                     uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                                     uint32_t src_w, uint32_t src_h, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias,
+                                                     uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!encode_size_ok(w, h, qbias) || !size_ok(src_w, src_h) || (n && (!d_blob || !d_offs || !d_lens)))
+        return fail(c, AMVHIP_ERR_ARG, "encode_scaled: bad argument (width/height must be even)");
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    // the rescaled planes are the context's: the lock is held from their allocation to the last launch that reads them
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int r = ensure(c, c->scaled, amvhip_yuv420_frame_bytes(w, h) * n)) return r;
+    const PixPicture dst = tight_420((uint8_t*)c->scaled.p, w, h);
+    if (int r = amvhip_resample_yuv420_dev(c, d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, src_w, src_h, dst.p[0],
+                                           dst.p[1], dst.p[2], dst.stride[0], dst.stride[1], dst.frame[0], dst.frame[1], w, h, n, stream))
+        return r;
+    return encode_scaled_tail(c, n, w, h, qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+}

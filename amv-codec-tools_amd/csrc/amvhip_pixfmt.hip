@@ -1,0 +1,328 @@
+// amvhip_pixfmt.hip -- pixel formats behind the C ABI: img_convert, the sws_scale shim, and the shim joined to the
+// encoder and the decoder.
+#include "amvhip_ctx.h"
+
+using namespace amv;
+
+namespace {
+
+int pix_picture_ok(int f, const PixPicture& pic, uint32_t w, uint32_t h) {
+    for (uint32_t p = 0; p < 3; ++p) {
+        uint32_t rb, rows;
+        pix_plane_size(f, p, w, h, &rb, &rows);
+        if (!rows) continue;
+        if (!pic.p[p] || ((uintptr_t)pic.p[p] & 3u) || pic.stride[p] < rb) return 0;
+    }
+    return 1;
+}
+
+// one supported pair, n frames, on st (the context is locked); every argument checked by the caller
+int convert_launch(amvhip_ctx* c, int src_fmt, const PixPicture& src, int dst_fmt, const PixPicture& dst, uint32_t w, uint32_t h, uint32_t n,
+                   hipStream_t st) {
+    Timed t(c, AMVHIP_K_PIXFMT, st);
+    switch (pix_route(src_fmt, dst_fmt)) {
+        case kRoutePlanes: case kRouteGray: {
+            const bool to_jpeg = !pix_jpeg(src_fmt) && (dst_fmt == AMVHIP_PIX_GRAY8 || pix_jpeg(dst_fmt));
+            const bool to_ccir = pix_jpeg(src_fmt) && dst_fmt != AMVHIP_PIX_GRAY8 && !pix_jpeg(dst_fmt);
+            PixPlaneJobs jobs{};
+            jobs.count = dst_fmt == AMVHIP_PIX_GRAY8 ? 1u : 3u;
+            // 4:2:0 to 4:2:0 takes the chroma planes whole, (w + 1) / 2 x (h + 1) / 2; the shrinking routes have even sizes
+            const uint32_t cw = (w + 1) / 2, chh = (h + 1) / 2;
+            for (uint32_t p = 0; p < jobs.count; ++p) {
+                PixPlaneJob& j = jobs.j[p];
+                j = PixPlaneJob{src.p[p], dst.p[p], src.stride[p], dst.stride[p], src.frame[p], dst.frame[p], p ? cw : w, p ? chh : h, kPixCopy,
+                                kPixRangeNone};
+                if (p) j.resize = pix_420(src_fmt) ? kPixCopy : (pix_444(src_fmt) ? kPixShrink22 : kPixShrink12);
+                if (to_jpeg) j.range = p ? kPixCCcirToJpeg : kPixYCcirToJpeg;
+                if (to_ccir) j.range = p ? kPixCJpegToCcir : kPixYJpegToCcir;
+            }
+            launch_pix_planes(jobs, n, st);
+            break;
+        }
+        case kRoutePackedIn: {
+            const bool uyvy = src_fmt == AMVHIP_PIX_UYVY422;
+            PixPicture d = dst;
+            if (uyvy) { std::swap(d.p[1], d.p[2]); std::swap(d.stride[1], d.stride[2]); std::swap(d.frame[1], d.frame[2]); }
+            launch_pix_packed_in(src, d, w, h, uyvy, n, st);
+            break;
+        }
+        case kRoutePackedOut: {
+            const bool uyvy = dst_fmt == AMVHIP_PIX_UYVY422;
+            PixPicture s = src;
+            if (uyvy) { std::swap(s.p[1], s.p[2]); std::swap(s.stride[1], s.stride[2]); std::swap(s.frame[1], s.frame[2]); }
+            launch_pix_packed_out(s, dst, w, h, uyvy, n, st);
+            break;
+        }
+        case kRouteRgbIn: {
+            // RGB_TO_Y_CCIR / _U_CCIR / _V_CCIR (colorspace.h:99-109) towards YUV420P, RGB_TO_Y / _U / _V (:87-97) towards YUVJ420P
+            const bool jpeg = dst_fmt == AMVHIP_PIX_YUVJ420P;
+            const double ys = jpeg ? 1.0 : 219.0 / 255.0, cs = jpeg ? 1.0 : 224.0 / 255.0;
+            const int yr = pix_fix(0.29900 * ys), yg = pix_fix(0.58700 * ys), yb = pix_fix(0.11400 * ys);
+            const int ur = -pix_fix(0.16874 * cs), ug = -pix_fix(0.33126 * cs), ub = pix_fix(0.50000 * cs);
+            const int vr = pix_fix(0.50000 * cs), vg = -pix_fix(0.41869 * cs), vb = -pix_fix(0.08131 * cs);
+            const bool red_first = src_fmt == AMVHIP_PIX_RGB24;   // BGR24 and RGB32 (B G R A in memory) have blue at +0
+            PixRgbIn k;
+            k.y[0] = red_first ? yr : yb; k.y[1] = yg; k.y[2] = red_first ? yb : yr;
+            k.yadd = 512 + (jpeg ? 0 : 16 << 10);
+            k.u[0] = red_first ? ur : ub; k.u[1] = ug; k.u[2] = red_first ? ub : ur;
+            k.v[0] = red_first ? vr : vb; k.v[1] = vg; k.v[2] = red_first ? vb : vr;
+            launch_pix_rgb_in(src, dst, w, h, pix_bpp(src_fmt), k, n, st);
+            break;
+        }
+        case kRouteRgbOut: {
+            // YUV_TO_RGB1_CCIR / 2_CCIR (colorspace.h:34-50) from YUV420P, YUV_TO_RGB1 / 2 (:52-67) from YUVJ420P
+            const bool jpeg = src_fmt == AMVHIP_PIX_YUVJ420P;
+            const double s = jpeg ? 1.0 : 255.0 / 224.0;
+            const int r[2] = {0, pix_fix(1.40200 * s)}, g[2] = {-pix_fix(0.34414 * s), -pix_fix(0.71414 * s)}, b[2] = {pix_fix(1.77200 * s), 0};
+            const bool blue_first = dst_fmt == AMVHIP_PIX_BGR24 || dst_fmt == AMVHIP_PIX_RGB32;
+            PixRgbOut k;
+            k.ymul = jpeg ? 1024 : pix_fix(255.0 / 219.0);
+            k.yoff = jpeg ? 0 : 16;
+            for (int i = 0; i < 2; ++i) { k.c0[i] = blue_first ? b[i] : r[i]; k.c1[i] = g[i]; k.c2[i] = blue_first ? r[i] : b[i]; }
+            k.rshift = dst_fmt == AMVHIP_PIX_RGB565 ? 11u : 10u;
+            k.gdrop = dst_fmt == AMVHIP_PIX_RGB565 ? 2u : 3u;
+            launch_pix_rgb_out(src, dst, w, h, pix_bpp(dst_fmt), k, n, st);
+            break;
+        }
+        default: return fail(c, AMVHIP_ERR_ARG, "img_convert: no one-step route from format %d to format %d", src_fmt, dst_fmt);
+    }
+    return check_launch(c, "img_convert");
+}
+
+// av_picture_copy (imgconvert.c:808-863) for two pictures of one format
+int copy_launch(amvhip_ctx* c, int fmt, const PixPicture& src, const PixPicture& dst, uint32_t w, uint32_t h, uint32_t n, hipStream_t st) {
+    Timed t(c, AMVHIP_K_PIXFMT, st);
+    PixPlaneJobs jobs{};
+    for (uint32_t p = 0; p < 3; ++p) {
+        uint32_t rb, rows;
+        pix_plane_size(fmt, p, w, h, &rb, &rows);
+        if (!rows) continue;
+        jobs.j[jobs.count++] = PixPlaneJob{src.p[p], dst.p[p], src.stride[p], dst.stride[p], src.frame[p], dst.frame[p], rb, rows, kPixCopy,
+                                           kPixRangeNone};
+    }
+    launch_pix_planes(jobs, n, st);
+    return check_launch(c, "picture copy");
+}
+
+// what both img_convert entry points ask of the pair and of the size
+int convert_args_ok(amvhip_ctx* c, int src_fmt, int dst_fmt, uint32_t w, uint32_t h) {
+    if (pix_route(src_fmt, dst_fmt) == kRouteNone)
+        return fail(c, AMVHIP_ERR_ARG, "img_convert: no one-step route from format %d to format %d", src_fmt, dst_fmt);
+    if (!pix_size_ok(src_fmt, dst_fmt, w, h)) return fail(c, AMVHIP_ERR_ARG, "img_convert: bad size %ux%u (this route wants even sizes)", w, h);
+    return AMVHIP_OK;
+}
+
+// sws_scale (imgresample.c:599-690), the context locked.  Towards YUVJ420P at another size the closing YUV420P -> YUVJ420P
+// step rides in the rescaler's store: no pass of its own.
+int sws_core(amvhip_ctx* c, int src_fmt, const PixPicture& src, uint32_t src_w, uint32_t src_h, int dst_fmt, const PixPicture& dst,
+             uint32_t dst_w, uint32_t dst_h, uint32_t n, hipStream_t st) {
+    if (src_w == dst_w && src_h == dst_h) {
+        if (src_fmt == dst_fmt) return copy_launch(c, src_fmt, src, dst, dst_w, dst_h, n, st);
+        return convert_launch(c, src_fmt, src, dst_fmt, dst, dst_w, dst_h, n, st);
+    }
+    PixPicture in = src;
+    if (src_fmt != AMVHIP_PIX_YUV420P) {
+        const uint64_t fb = amvhip_yuv420_frame_bytes(src_w, src_h);
+        if (int r = ensure(c, c->pix_in, fb * n)) return r;
+        in = tight_420((uint8_t*)c->pix_in.p, src_w, src_h);
+        if (int r = convert_launch(c, src_fmt, src, AMVHIP_PIX_YUV420P, in, src_w, src_h, n, st)) return r;
+    }
+    if (dst_fmt == AMVHIP_PIX_YUV420P || dst_fmt == AMVHIP_PIX_YUVJ420P)
+        return resample_launch(c, in, src_w, src_h, dst, dst_w, dst_h, n, dst_fmt == AMVHIP_PIX_YUVJ420P, st);
+    const uint64_t fb = amvhip_yuv420_frame_bytes(dst_w, dst_h);
+    if (int r = ensure(c, c->pix_out, fb * n)) return r;
+    const PixPicture mid = tight_420((uint8_t*)c->pix_out.p, dst_w, dst_h);
+    // img_resample writes (w >> 1) x (h >> 1) chroma, the routines out of YUV420P read (w + 1) / 2 x (h + 1) / 2: the reference
+    // leaves an odd picture's last chroma column and row undefined, here they are 128 (no colour) whatever the workspace held
+    if (((dst_w | dst_h) & 1) && dst_fmt != AMVHIP_PIX_GRAY8) HIP_TRY(c, hipMemsetAsync(c->pix_out.p, 128, fb * n, st));
+    if (int r = resample_launch(c, in, src_w, src_h, mid, dst_w, dst_h, n, false, st)) return r;
+    return convert_launch(c, AMVHIP_PIX_YUV420P, mid, dst_fmt, dst, dst_w, dst_h, n, st);
+}
+
+// the checks of amvhip_sws_scale_dev, shared with the entries built on it
+// (dst == nullptr: the destination is the context's own)
+int sws_args_ok(amvhip_ctx* c, int src_fmt, const PixPicture& src, uint32_t src_w, uint32_t src_h, int dst_fmt, const PixPicture* dst,
+                uint32_t dst_w, uint32_t dst_h) {
+    if (src_fmt < 0 || src_fmt >= AMVHIP_PIX_COUNT || dst_fmt < 0 || dst_fmt >= AMVHIP_PIX_COUNT)
+        return fail(c, AMVHIP_ERR_ARG, "sws_scale: unknown pixel format");
+    if (!size_ok(src_w, src_h) || !size_ok(dst_w, dst_h)) return fail(c, AMVHIP_ERR_ARG, "sws_scale: bad picture size");
+    if (src_w == dst_w && src_h == dst_h) {
+        if (src_fmt != dst_fmt && (pix_route(src_fmt, dst_fmt) == kRouteNone || !pix_size_ok(src_fmt, dst_fmt, dst_w, dst_h)))
+            return fail(c, AMVHIP_ERR_ARG, "sws_scale: no one-step route from format %d to format %d at %ux%u", src_fmt, dst_fmt, dst_w, dst_h);
+    } else {
+        if (src_w < 2 || src_h < 2 || dst_w < 2 || dst_h < 2) return fail(c, AMVHIP_ERR_ARG, "sws_scale: a rescaled picture is at least 2x2");
+        if (src_fmt != AMVHIP_PIX_YUV420P &&
+            (pix_route(src_fmt, AMVHIP_PIX_YUV420P) == kRouteNone || !pix_size_ok(src_fmt, AMVHIP_PIX_YUV420P, src_w, src_h)))
+            return fail(c, AMVHIP_ERR_ARG, "sws_scale: no one-step route from format %d to YUV420P at %ux%u", src_fmt, src_w, src_h);
+        if (dst_fmt != AMVHIP_PIX_YUV420P && dst_fmt != AMVHIP_PIX_YUVJ420P &&
+            (pix_route(AMVHIP_PIX_YUV420P, dst_fmt) == kRouteNone || !pix_size_ok(AMVHIP_PIX_YUV420P, dst_fmt, dst_w, dst_h)))
+            return fail(c, AMVHIP_ERR_ARG, "sws_scale: no one-step route from YUV420P to format %d at %ux%u", dst_fmt, dst_w, dst_h);
+    }
+    if (!pix_picture_ok(src_fmt, src, src_w, src_h) || (dst && !pix_picture_ok(dst_fmt, *dst, dst_w, dst_h)))
+        return fail(c, AMVHIP_ERR_ARG, "sws_scale: null or misaligned plane, or a row pitch below the row");
+    return AMVHIP_OK;
+}
+
+}  // namespace
+
+extern "C" uint64_t amvhip_pix_frame_bytes(int fmt, uint32_t stride, uint32_t height) { return pix_frame_bytes(fmt, stride, height); }
+
+extern "C" int amvhip_img_convert_supported(int src_fmt, int dst_fmt, uint32_t w, uint32_t h) {
+    return pix_route(src_fmt, dst_fmt) != kRouteNone && pix_size_ok(src_fmt, dst_fmt, w, h);
+}
+
+extern "C" int amvhip_img_convert_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2,
+                                      uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                                      int dst_fmt, uint8_t* d_dst0, uint8_t* d_dst1, uint8_t* d_dst2, uint32_t dst_stride, uint32_t dst_c_stride,
+                                      uint64_t dst_frame_stride, uint64_t dst_c_frame_stride, uint32_t w, uint32_t h, uint32_t n, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (int r = convert_args_ok(c, src_fmt, dst_fmt, w, h)) return r;
+    const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    const PixPicture dst = make_picture(d_dst0, d_dst1, d_dst2, dst_stride, dst_c_stride, dst_frame_stride, dst_c_frame_stride);
+    if (!pix_picture_ok(src_fmt, src, w, h) || !pix_picture_ok(dst_fmt, dst, w, h))
+        return fail(c, AMVHIP_ERR_ARG, "img_convert: null or misaligned plane, or a row pitch below the row");
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return convert_launch(c, src_fmt, src, dst_fmt, dst, w, h, n, (hipStream_t)stream);
+}
+
+// host buffers: the planes are staged tight on the device (rows of exactly the row's bytes), converted, and the
+// destination rows copied back row by row -- bytes between the caller's rows and frames are never touched
+extern "C" int amvhip_img_convert(amvhip_ctx* c, int src_fmt, const uint8_t* src0, const uint8_t* src1, const uint8_t* src2,
+                                  uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                                  int dst_fmt, uint8_t* dst0, uint8_t* dst1, uint8_t* dst2, uint32_t dst_stride, uint32_t dst_c_stride,
+                                  uint64_t dst_frame_stride, uint64_t dst_c_frame_stride, uint32_t w, uint32_t h, uint32_t n) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (int r = convert_args_ok(c, src_fmt, dst_fmt, w, h)) return r;
+    const PixPicture hs = make_picture(src0, src1, src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    const PixPicture hd = make_picture(dst0, dst1, dst2, dst_stride, dst_c_stride, dst_frame_stride, dst_c_frame_stride);
+    PixPicture ds{}, dd{};
+    uint64_t bytes[2] = {0, 0};
+    for (int side = 0; side < 2; ++side) {
+        const int f = side ? dst_fmt : src_fmt;
+        const PixPicture& hp = side ? hd : hs;
+        PixPicture& dp = side ? dd : ds;
+        uint64_t off[4] = {0, 0, 0, 0};
+        for (uint32_t p = 0; p < 3; ++p) {
+            uint32_t rb, rows;
+            pix_plane_size(f, p, w, h, &rb, &rows);
+            if (rows && (!hp.p[p] || hp.stride[p] < rb)) return fail(c, AMVHIP_ERR_ARG, "img_convert: null plane, or a row pitch below the row");
+            dp.stride[p] = rb;
+            off[p + 1] = off[p] + (((uint64_t)rb * rows + 15u) & ~15ull);    // every staged plane starts 16-byte aligned
+        }
+        for (uint32_t p = 0; p < 3; ++p) {
+            dp.frame[p] = off[3];
+            dp.p[p] = (uint8_t*)off[p];                                      // offset for now
+        }
+        bytes[side] = off[3] * n;
+    }
+    if (n == 0) return AMVHIP_OK;
+    hipStream_t st;
+    if (int r = host_stream(c, &st)) return r;
+    std::lock_guard<std::mutex> hlk(c->hmu);
+    if (int r = ensure(c, c->h_in, bytes[0])) return r;
+    if (int r = ensure(c, c->h_out, bytes[1])) return r;
+    for (uint32_t p = 0; p < 3; ++p) {
+        ds.p[p] = (uint8_t*)c->h_in.p + (uintptr_t)ds.p[p];
+        dd.p[p] = (uint8_t*)c->h_out.p + (uintptr_t)dd.p[p];
+    }
+    for (int side = 0; side < 2; ++side) {
+        const int f = side ? dst_fmt : src_fmt;
+        if (side) {
+            std::lock_guard<std::mutex> lk(c->mu);
+            if (int r = convert_launch(c, src_fmt, ds, dst_fmt, dd, w, h, n, st)) return r;
+        }
+        for (uint32_t p = 0; p < 3; ++p) {
+            uint32_t rb, rows;
+            pix_plane_size(f, p, w, h, &rb, &rows);
+            if (!rows) continue;
+            for (uint32_t i = 0; i < n; ++i) {
+                if (!side)
+                    HIP_TRY(c, hipMemcpy2DAsync(ds.p[p] + i * ds.frame[p], rb, hs.p[p] + i * hs.frame[p], hs.stride[p], rb, rows,
+                                                hipMemcpyHostToDevice, st));
+                else
+                    HIP_TRY(c, hipMemcpy2DAsync(hd.p[p] + i * hd.frame[p], hd.stride[p], dd.p[p] + i * dd.frame[p], rb, rb, rows,
+                                                hipMemcpyDeviceToHost, st));
+            }
+        }
+    }
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return AMVHIP_OK;
+}
+
+extern "C" int amvhip_sws_scale_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2,
+                                    uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                                    uint32_t src_w, uint32_t src_h, int dst_fmt, uint8_t* d_dst0, uint8_t* d_dst1, uint8_t* d_dst2,
+                                    uint32_t dst_stride, uint32_t dst_c_stride, uint64_t dst_frame_stride, uint64_t dst_c_frame_stride,
+                                    uint32_t dst_w, uint32_t dst_h, uint32_t n, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    const PixPicture dst = make_picture(d_dst0, d_dst1, d_dst2, dst_stride, dst_c_stride, dst_frame_stride, dst_c_frame_stride);
+    if (int r = sws_args_ok(c, src_fmt, src, src_w, src_h, dst_fmt, &dst, dst_w, dst_h)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);   // the intermediates are the context's
+    return sws_core(c, src_fmt, src, src_w, src_h, dst_fmt, dst, dst_w, dst_h, n, (hipStream_t)stream);
+}
+
+// ffmpeg.c:757-814 for any supported source: the shim to YUVJ420P, then the encoder
+extern "C" int amvhip_encode_fmt_scaled_batch_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1,
+                                                  const uint8_t* d_src2, uint32_t src_stride, uint32_t src_c_stride,
+                                                  uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_w, uint32_t src_h,
+                                                  uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap,
+                                                  uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!encode_size_ok(w, h, qbias) || (n && (!d_blob || !d_offs || !d_lens)))
+        return fail(c, AMVHIP_ERR_ARG, "encode_fmt: bad argument (width/height must be even)");
+    const bool same = src_w == w && src_h == h;
+    // the two sources the encoder reads itself (its colour stage is the reference's rgb24_to_yuvj420p; BGR24 is that routine
+    // with the weights exchanged, as amvhip_encode_batch_dev has always taken it)
+    if (same && (src_fmt == AMVHIP_PIX_RGB24 || src_fmt == AMVHIP_PIX_BGR24)) {
+        if (src_frame_stride != (uint64_t)src_stride * h && n > 1)
+            return fail(c, AMVHIP_ERR_ARG, "encode_fmt: RGB frames at the target size lie back to back (frame stride = stride * height)");
+        return amvhip_encode_batch_dev(c, d_src0, src_stride, src_fmt == AMVHIP_PIX_BGR24, n, w, h, qbias, d_blob, blob_cap, d_offs, d_lens, stream);
+    }
+    if (same && src_fmt == AMVHIP_PIX_YUVJ420P)
+        return amvhip_encode_yuv420_batch_dev(c, d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride, n, w, h,
+                                              qbias, d_blob, blob_cap, d_offs, d_lens, stream);
+    const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    if (int r = sws_args_ok(c, src_fmt, src, src_w, src_h, AMVHIP_PIX_YUVJ420P, nullptr, w, h)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    // the planes in between are the context's: the lock is held from their allocation to the last launch that reads them
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int r = ensure(c, c->scaled, amvhip_yuv420_frame_bytes(w, h) * n)) return r;
+    const PixPicture dst = tight_420((uint8_t*)c->scaled.p, w, h);
+    if (int r = sws_core(c, src_fmt, src, src_w, src_h, AMVHIP_PIX_YUVJ420P, dst, w, h, n, (hipStream_t)stream)) return r;
+    return encode_scaled_tail(c, n, w, h, qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+}
+
+// the decoder of the patched FFmpeg, then img_convert towards what the next stage wants (ffmpeg -i x.amv -pix_fmt ...)
+extern "C" int amvhip_decode_fmt_batch_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                           const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, uint32_t flags, int dst_fmt,
+                                           uint8_t* d_out, uint32_t out_stride, int32_t* d_status, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!(flags & AMVHIP_FLAG_FFMPEG)) return fail(c, AMVHIP_ERR_ARG, "decode_fmt: AMVHIP_FLAG_FFMPEG is required (the planes are that decoder's)");
+    if (flags & AMVHIP_FLAG_FFMPEG_KEEP) return fail(c, AMVHIP_ERR_ARG, "decode_fmt: AMVHIP_FLAG_FFMPEG_KEEP needs the caller's planes; d_out is not in plane form");
+    if (pix_route(AMVHIP_PIX_YUVJ420P, dst_fmt) == kRouteNone)
+        return fail(c, AMVHIP_ERR_ARG, "decode_fmt: no one-step route from YUVJ420P to format %d", dst_fmt);
+    if (int r = decode_args_ok(c, d_blob, d_offs, d_lens, n, w, h, flags, d_out, d_status)) return r;
+    const uint64_t out_frame = amvhip_pix_frame_bytes(dst_fmt, out_stride, h);
+    PixPicture dst = make_picture(d_out, nullptr, nullptr, out_stride, (out_stride + 1) / 2, out_frame, out_frame);
+    if (dst_fmt == AMVHIP_PIX_YUV420P) {
+        dst.p[1] = d_out + (uint64_t)out_stride * h;
+        dst.p[2] = dst.p[1] + (uint64_t)dst.stride[1] * ((h + 1) / 2);
+    }
+    if (out_stride < w * pix_bpp(dst_fmt)) return fail(c, AMVHIP_ERR_ARG, "decode_fmt: out_stride below the row");
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const uint64_t fb = amvhip_yuv420_frame_bytes(w, h);
+    if (int r = ensure(c, c->pix_dec, fb * n)) return r;
+    if (int r = decode_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, flags, (uint8_t*)c->pix_dec.p, d_status, c->set[0],
+                            (hipStream_t)stream, (hipStream_t)stream))
+        return r;
+    return convert_launch(c, AMVHIP_PIX_YUVJ420P, tight_420((uint8_t*)c->pix_dec.p, w, h), dst_fmt, dst, w, h, n, (hipStream_t)stream);
+}
+

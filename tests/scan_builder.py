@@ -217,7 +217,7 @@ def records_of(blocks):
 
 
 def record_space(chunk_len, nblocks):
-    """the records a frame is given (amvhip_api.hip entropy_records: 2 per chunk byte + 2 per block + 64, no more than
+    """the records a frame is given (amv_host_plan.h entropy_plan: 2 per chunk byte + 2 per block + 64, no more than
     66 per block, in whole lines of 32)"""
     hi = (nblocks * 66 + 95) & ~31
     return (min(2 * chunk_len + 2 * nblocks + 64, hi) + 31) // 32 * 32

@@ -277,6 +277,23 @@ def test_reconstruction_piece_map_arithmetic(tmp_path):
     assert out.returncode == 0 and out.stdout.startswith("ok "), out.stdout + out.stderr
 
 
+def test_host_plan_arithmetic(tmp_path):
+    """amv_host_plan.h (what the host decides before a launch: the Huffman table images, the entropy stage's buffer sizes and
+    the fall-back rounds, the rescaler's and the audio resampler's filter banks, the pixel-format routes) walked on the CPU
+    by tests/c/host_plan_test.cc, a stand-alone program under the address and undefined-behaviour sanitizers; the record
+    space it prints for a few (chunk length, blocks) pairs is the figure scan_builder.record_space states"""
+    from scan_builder import record_space
+    exe = str(tmp_path / "host_plan_test")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "amv-codec-tools_amd", "csrc"), os.path.join(ROOT, "tests", "c", "host_plan_test.cc"), "-o", exe],
+                   check=True)
+    pairs = [(0, 6), (1, 6), (201, 6), (202, 6), (203, 6), (5000, 480), (15359, 480), (15360, 480), (15361, 480), (10 ** 6, 7200)]   # around min()'s switch
+    out = subprocess.run([exe] + [str(v) for p in pairs for v in p], capture_output=True, text=True)
+    lines = out.stdout.splitlines()
+    assert out.returncode == 0 and lines and lines[-1].startswith("ok ") and not out.stderr, out.stdout[-2000:] + out.stderr[-4000:]
+    assert [tuple(int(v) for v in l.split()[1:]) for l in lines if l.startswith("rec ")] == [(n, b, record_space(n, b)) for n, b in pairs]
+
+
 def test_host_c_under_sanitizers(amv1, tmp_path):
     """SURVEY.md section 5 for the PRODUCT's host C: host/amvlib_compat.c (the reader parses untrusted AMV files -- chunk
     lengths from the file size its reads and its buffers, AMVDec.c:150-238 is what it replaces) and host/amv_container.c,

@@ -2128,7 +2128,7 @@ def test_mixed_stream_keeps_the_parallel_kernels(pkg, orc):
     noise in between, whose chunks are many times the mean -- no frame is handed to the one-lane serial kernel
     (amvhip_entropy_stats), and every byte and status equals the oracle's.  Both parallel entropy kernels: the
     speculative lanes a small batch gets and the one-lane-per-frame kernel of a chip-filling batch (AMVHIP_SYNC_LANES=1).
-    A frame's record space is two words per byte of its chunk + two per block (amvhip_api.hip: `add_rec`, `hi_rec`), never
+    A frame's record space is two words per byte of its chunk + two per block (amv_host_plan.h: `add_rec`, `hi_rec`), never
     more than a frame with every coefficient non-zero could fill -- white noise stays on the parallel kernels too, a crafted
     scan with every coefficient non-zero does not --
     and chunks that overlap in the blob (their lengths add up to more than the blob holds) are decoded all the same."""
