@@ -124,6 +124,11 @@ SYMBOLS = {
     "amvhip_sws_scale_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
     "amvhip_encode_fmt_scaled_batch_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "amvhip_decode_fmt_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
+    "amvhip_lowres_dim": (_u32, [_u32, _u32]),
+    "amvhip_lowres_frame_bytes": (_u64, [_u32, _u32, _u32]),
+    "amvhip_decode_lowres_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
+    "amvhip_decode_lowres_batch": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp]),
+    "amvhip_reconstruct_lowres_dev": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp]),
     "amvhip_audio_resample_out_samples": (_u64, [_u32, _u32, _u64]),
     "amvhip_audio_resample_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _vp]),
     "amvhip_audio_resample_batch": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _u32, _u32]),
@@ -340,6 +345,26 @@ class Context:
         return self._check(self.lib.amvhip_decode_fmt_batch_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, flags,
                                                                 dst_fmt, _ptr(out), out_stride, _ptr(status), stream),
                            "decode_fmt_batch_dev")
+
+    # reduced-size decode (lowres 1..3: 1/2, 1/4, 1/8 size)
+    def lowres_dim(self, full, lowres):
+        return self.lib.amvhip_lowres_dim(full, lowres)
+
+    def lowres_frame_bytes(self, w, h, lowres):
+        return self.lib.amvhip_lowres_frame_bytes(w, h, lowres)
+
+    def decode_lowres_batch_dev(self, blob, blob_bytes, offs, lens, n, w, h, flags, lowres, dst_fmt, out, out_stride, status, stream=None):
+        return self._check(self.lib.amvhip_decode_lowres_batch_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, flags,
+                                                                   lowres, dst_fmt, _ptr(out), out_stride, _ptr(status), stream),
+                           "decode_lowres_batch_dev")
+
+    def decode_lowres_batch(self, blob, blob_bytes, offs, lens, n, w, h, flags, lowres, dst_fmt, out, out_stride, status):
+        return self._check(self.lib.amvhip_decode_lowres_batch(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, flags,
+                                                               lowres, dst_fmt, _ptr(out), out_stride, _ptr(status)), "decode_lowres_batch")
+
+    def reconstruct_lowres_dev(self, coef, nmcu_ok, n, w, h, lowres, out, stream=None):
+        return self._check(self.lib.amvhip_reconstruct_lowres_dev(self.h, _ptr(coef), _ptr(nmcu_ok), n, w, h, lowres, _ptr(out), stream),
+                           "reconstruct_lowres_dev")
 
     def audio_resample_out_samples(self, in_rate, out_rate, in_samples):
         return audio_resample_out_samples(in_rate, out_rate, in_samples)

@@ -126,6 +126,50 @@ inline uint32_t fallback_round(uint32_t n, const FrameGeom& g, uint32_t most, ui
     return round < n ? round : n;
 }
 
+// ---- reduced-size decode (lowres 1..3: pictures of 1/2, 1/4, 1/8 the size) ---------------------------------------------
+
+// what avcodec_set_dimensions makes of a size (utils.c:141-142): ceil(full / 2^lowres); 0 for lowres > 3
+inline uint32_t lowres_dim(uint32_t full, uint32_t lowres) { return lowres > 3u ? 0u : (full + (1u << lowres) - 1u) >> lowres; }
+
+// the three tight planes of a reduced picture: Y W_L x H_L, then Cb, Cr of (W_L + 1) / 2 x (H_L + 1) / 2
+inline uint64_t lowres_frame_bytes(uint32_t w, uint32_t h, uint32_t lowres) {
+    if (lowres > 3u) return 0;
+    const uint64_t wl = lowres_dim(w, lowres), hl = lowres_dim(h, lowres);
+    return wl * hl + 2u * ((wl + 1u) / 2u) * ((hl + 1u) / 2u);
+}
+
+// the full-size start row of a component (mjpegdec.c:675): canvas row r lands at plane row start - r
+inline int ffmpeg_start_row(uint32_t height, bool chroma) {
+    const uint32_t mcu_rows = (height + 15u) / 16u;
+    return (chroma ? 1 : 2) * (int)(8u * mcu_rows - ((height >> 1) & 7u)) - 1;
+}
+
+// ... scaled down: reduced canvas row r_L (= full-size canvas row >> lowres) lands at plane row lowres_start_row - r_L.
+// start + 1 is the count of plane rows the full-size formula can reach; the reduced count is that, rounded up.
+inline int lowres_start_row(uint32_t height, uint32_t lowres, bool chroma) {
+    return ((ffmpeg_start_row(height, chroma) + 1 + (1 << lowres) - 1) >> lowres) - 1;
+}
+
+// rows of a reduced plane
+inline uint32_t lowres_plane_rows(uint32_t height, uint32_t lowres, bool chroma) {
+    const uint32_t hl = lowres_dim(height, lowres);
+    return chroma ? (hl + 1u) / 2u : hl;
+}
+
+// plane rows 0 .. lowres_rows_reached - 1 are the ones the rule sends a canvas row to.  All of them for h % 16 <= 8; the
+// other heights leave the bottom rows of the plane without a canvas row, as the full-size formula does (the caller
+// clears the output first: lowres_store_covers_planes)
+inline uint32_t lowres_rows_reached(uint32_t height, uint32_t lowres, bool chroma) {
+    const uint32_t rows = lowres_plane_rows(height, lowres, chroma);
+    const int reach = lowres_start_row(height, lowres, chroma) + 1;
+    return reach < (int)rows ? (uint32_t)(reach > 0 ? reach : 0) : rows;
+}
+
+inline bool lowres_store_covers_planes(uint32_t height, uint32_t lowres) {
+    return lowres_rows_reached(height, lowres, false) == lowres_plane_rows(height, lowres, false) &&
+           lowres_rows_reached(height, lowres, true) == lowres_plane_rows(height, lowres, true);
+}
+
 // ---- picture rescale --------------------------------------------------------------------------
 
 // av_build_filter(filter, factor, NB_TAPS = 4, NB_PHASES = 16, 1 << FILTER_BITS, type 0) -- libavcodec/resample2.c:93-140

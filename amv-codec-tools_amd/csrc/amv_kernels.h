@@ -105,6 +105,11 @@ void launch_reconstruct(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_
 void launch_reconstruct_yuv(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameSel& sel, uint32_t items,
                             const FrameGeom& g, uint64_t yuv_frame_bytes, uint8_t* out, hipStream_t s);
 bool yuv_store_covers_planes(const FrameGeom& g);
+// ... at 1/2, 1/4, 1/8 size (amv_reconstruct_lowres.hip, amv_reconstruct_yuv_lowres_kernel<L, kRound>; lowres = L = 1..3):
+// j_rev_dct4 / 2 / 1 over the top-left coefficients of each block, the planes of lowres_dim(w) x lowres_dim(h) placed by
+// lowres_start_row (amv_host_plan.h).  The caller clears the output first where lowres_store_covers_planes says no.
+void launch_reconstruct_yuv_lowres(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameSel& sel, uint32_t items,
+                                   const FrameGeom& g, uint32_t lowres, uint8_t* out, hipStream_t s);
 
 // ---- encode -------------------------------------------------------------------------------
 // planar YUVJ420P source (what the reference's amv_encoder takes, mjpegenc.c:493): frame i's planes at

@@ -167,7 +167,12 @@ int decode_args_ok(amvhip_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs,
                    uint32_t h, uint32_t flags, const uint8_t* d_out, const int32_t* d_status);
 int decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
                 uint32_t n, uint32_t w, uint32_t h, uint32_t flags, uint8_t* d_out, int32_t* d_status, DecodeSet& b,
-                hipStream_t front, hipStream_t back);
+                hipStream_t front, hipStream_t back, uint32_t lowres = 0);   // lowres 1..3: the reduced planes (flags = AMVHIP_FLAG_FFMPEG)
+
+// ---- amvhip_pixfmt.hip (the caller holds c->mu) ------------------------------------------------------------------------
+// one supported img_convert pair (pix_route), n frames, on st; every argument checked by the caller
+int pix_convert_launch(amvhip_ctx* c, int src_fmt, const PixPicture& src, int dst_fmt, const PixPicture& dst, uint32_t w, uint32_t h, uint32_t n,
+                       hipStream_t st);
 
 // ---- amvhip_encode.hip (the caller holds c->mu) ------------------------------------------------------------------------
 // what every encoder asks of the target size and of qbias

@@ -75,9 +75,11 @@ static int entropy_front(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_byt
 }
 
 static int reconstruct_launch(amvhip_ctx* c, const SyncSinks& sinks, const uint32_t* d_nmcu_ok, uint32_t n, const FrameSel& sel,
-                              uint32_t items, const FrameGeom& g, uint32_t flags, uint8_t* d_out, hipStream_t st) {
+                              uint32_t items, const FrameGeom& g, uint32_t flags, uint8_t* d_out, hipStream_t st, uint32_t lowres = 0) {
     Timed t(c, AMVHIP_K_RECON, st);
-    if (flags & AMVHIP_FLAG_FFMPEG)   // the patched FFmpeg's amv_decoder: YUVJ420P planes
+    if (lowres)   // ... at 1/2, 1/4, 1/8 size
+        launch_reconstruct_yuv_lowres(sinks, d_nmcu_ok, n, sel, items, g, lowres, d_out, st);
+    else if (flags & AMVHIP_FLAG_FFMPEG)   // the patched FFmpeg's amv_decoder: YUVJ420P planes
         launch_reconstruct_yuv(sinks, d_nmcu_ok, n, sel, items, g, amvhip_yuv420_frame_bytes(g.width, g.height), d_out, st);
     else
         launch_reconstruct(sinks, d_nmcu_ok, n, sel, items, g, flags, d_out, st);
@@ -86,8 +88,12 @@ static int reconstruct_launch(amvhip_ctx* c, const SyncSinks& sinks, const uint3
 
 // bytes of the output no kernel writes are cleared first: row padding (AMVDec.c:283), and in FFmpeg mode the plane
 // rows mjpegdec.c:672-677 leaves untouched for some heights
-static int clear_unwritten(amvhip_ctx* c, uint32_t n, const FrameGeom& g, uint32_t flags, uint8_t* d_out, hipStream_t st) {
+static int clear_unwritten(amvhip_ctx* c, uint32_t n, const FrameGeom& g, uint32_t flags, uint8_t* d_out, hipStream_t st, uint32_t lowres = 0) {
     if (flags & AMVHIP_FLAG_FFMPEG_KEEP) return AMVHIP_OK;   // what no block covers stays as the caller had it
+    if (lowres) {
+        if (!lowres_store_covers_planes(g.height, lowres)) HIP_TRY(c, hipMemsetAsync(d_out, 0, lowres_frame_bytes(g.width, g.height, lowres) * n, st));
+        return AMVHIP_OK;
+    }
     if (flags & AMVHIP_FLAG_FFMPEG) {
         if (!yuv_store_covers_planes(g)) HIP_TRY(c, hipMemsetAsync(d_out, 0, amvhip_yuv420_frame_bytes(g.width, g.height) * n, st));
     } else if (g.stride != g.width * 3) {
@@ -184,7 +190,7 @@ extern "C" int amvhip_huffman_decode_dev(amvhip_ctx* c, const uint8_t* d_blob, u
 // context's own with `back` waiting for `front`).  Caller holds the lock.
 int amv::decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
                        uint32_t n, uint32_t w, uint32_t h, uint32_t flags, uint8_t* d_out, int32_t* d_status, DecodeSet& b,
-                       hipStream_t front, hipStream_t back) {
+                       hipStream_t front, hipStream_t back, uint32_t lowres) {
     const FrameGeom g = make_geom(w, h);
     // (rounds of up to 16 384 frames: every round is a pair of launches that usually find nothing to do, and a batch that
     // small is latency-bound -- three rounds cost the 10 000-frame stream 3 % of its step)
@@ -204,9 +210,9 @@ int amv::decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, 
         HIP_TRY(c, hipStreamWaitEvent(back, c->ev_front, 0));
     }
     hipStream_t st = back;
-    if (int r = clear_unwritten(c, n, g, flags, d_out, st)) return r;
+    if (int r = clear_unwritten(c, n, g, flags, d_out, st, lowres)) return r;
     if (fb.list)   // the frames in records form (a launch that skips the others)
-        if (int r = reconstruct_launch(c, sinks, d_nmcu, n, kAllFrames, n, g, flags, d_out, st)) return r;
+        if (int r = reconstruct_launch(c, sinks, d_nmcu, n, kAllFrames, n, g, flags, d_out, st, lowres)) return r;
     // The others, a round of dense lines at a time.  With a list the count is on the device: the rounds past it find
     // nothing to do and leave at once (usually all of them: one pair of empty launches per round).
     for (uint32_t base = 0; base < fb.items; base += round) {
@@ -217,7 +223,7 @@ int amv::decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, 
                            fb.count, base, items, true, sinks.ok_in_blocks != 0u, st);
         }
         if (int r = check_launch(c, "huffman")) return r;
-        if (int r = reconstruct_launch(c, sinks, d_nmcu, n, FrameSel{fb.list, fb.count, base, items}, items, g, flags, d_out, st)) return r;
+        if (int r = reconstruct_launch(c, sinks, d_nmcu, n, FrameSel{fb.list, fb.count, base, items}, items, g, flags, d_out, st, lowres)) return r;
     }
     c->ws_bytes_per_frame = (double)(c->ws.cap + c->coef.cap + c->ws_bytes.cap + c->ws_line.cap + c->set[0].cap() + c->set[1].cap()) / n;
     return AMVHIP_OK;
@@ -342,3 +348,92 @@ extern "C" int amvhip_decode_batch(amvhip_ctx* c, const uint8_t* blob, uint64_t 
     return amvhip_sync(c);
 }
 
+
+// ---- reduced-size decode (lowres 1..3): include/amvhip.h states the rule ------------------------------------------------
+extern "C" uint32_t amvhip_lowres_dim(uint32_t full, uint32_t lowres) { return lowres_dim(full, lowres); }
+
+extern "C" uint64_t amvhip_lowres_frame_bytes(uint32_t w, uint32_t h, uint32_t lowres) { return lowres_frame_bytes(w, h, lowres); }
+
+extern "C" int amvhip_reconstruct_lowres_dev(amvhip_ctx* c, const int16_t* d_coef, const uint32_t* d_nmcu_ok, uint32_t n, uint32_t w, uint32_t h,
+                                             uint32_t lowres, uint8_t* d_out, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (lowres < 1u || lowres > 3u) return fail(c, AMVHIP_ERR_ARG, "reconstruct_lowres: lowres must be 1, 2 or 3");
+    if (!size_ok(w, h) || (n && (!d_coef || !d_nmcu_ok || !d_out))) return fail(c, AMVHIP_ERR_ARG, "reconstruct_lowres: bad argument");
+    if (((uintptr_t)d_out & 3u) || ((uintptr_t)d_coef & 15u))
+        return fail(c, AMVHIP_ERR_ARG, "reconstruct_lowres: out must be 4-byte, coef 16-byte aligned");
+    if (int r = use_device(c)) return r;
+    if (n == 0) return AMVHIP_OK;
+    const FrameGeom g = make_geom(w, h);
+    SyncSinks sinks{};
+    sinks.coef = const_cast<int16_t*>(d_coef);
+    if (int r = clear_unwritten(c, n, g, AMVHIP_FLAG_FFMPEG, d_out, (hipStream_t)stream, lowres)) return r;
+    return reconstruct_launch(c, sinks, d_nmcu_ok, n, kAllFrames, n, g, AMVHIP_FLAG_FFMPEG, d_out, (hipStream_t)stream, lowres);
+}
+
+// what both decode entry points ask of the mode, the format and the row pitch (before anything touches a device)
+static int lowres_args_ok(amvhip_ctx* c, uint32_t w, uint32_t flags, uint32_t lowres, int dst_fmt, uint32_t out_stride) {
+    if (flags != AMVHIP_FLAG_FFMPEG)
+        return fail(c, AMVHIP_ERR_ARG, "decode_lowres: flags must be exactly AMVHIP_FLAG_FFMPEG (the reduced planes are that decoder's)");
+    if (lowres < 1u || lowres > 3u) return fail(c, AMVHIP_ERR_ARG, "decode_lowres: lowres must be 1, 2 or 3");
+    const uint32_t wl = lowres_dim(w, lowres);
+    if (dst_fmt == AMVHIP_PIX_YUVJ420P) {
+        if (out_stride != wl) return fail(c, AMVHIP_ERR_ARG, "decode_lowres: the YUVJ420P planes are tight, out_stride must be %u", wl);
+    } else {
+        if (pix_route(AMVHIP_PIX_YUVJ420P, dst_fmt) == kRouteNone)
+            return fail(c, AMVHIP_ERR_ARG, "decode_lowres: no one-step route from YUVJ420P to format %d", dst_fmt);
+        if (out_stride < wl * pix_bpp(dst_fmt)) return fail(c, AMVHIP_ERR_ARG, "decode_lowres: out_stride below the row");
+    }
+    return AMVHIP_OK;
+}
+
+extern "C" int amvhip_decode_lowres_batch_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                              const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, uint32_t flags, uint32_t lowres,
+                                              int dst_fmt, uint8_t* d_out, uint32_t out_stride, int32_t* d_status, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (int r = lowres_args_ok(c, w, flags, lowres, dst_fmt, out_stride)) return r;
+    if (int r = decode_args_ok(c, d_blob, d_offs, d_lens, n, w, h, flags, d_out, d_status)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t st = (hipStream_t)stream;
+    if (dst_fmt == AMVHIP_PIX_YUVJ420P) return decode_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, flags, d_out, d_status, c->set[0], st, st, lowres);
+    // the other formats: the planes in the context's workspace, then img_convert at the reduced size
+    const uint32_t wl = lowres_dim(w, lowres), hl = lowres_dim(h, lowres);
+    if (int r = ensure(c, c->pix_dec, lowres_frame_bytes(w, h, lowres) * n)) return r;
+    if (int r = decode_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, flags, (uint8_t*)c->pix_dec.p, d_status, c->set[0], st, st, lowres))
+        return r;
+    const uint64_t out_frame = pix_frame_bytes(dst_fmt, out_stride, hl);
+    PixPicture dst = make_picture(d_out, nullptr, nullptr, out_stride, (out_stride + 1) / 2, out_frame, out_frame);
+    if (dst_fmt == AMVHIP_PIX_YUV420P) {
+        dst.p[1] = d_out + (uint64_t)out_stride * hl;
+        dst.p[2] = dst.p[1] + (uint64_t)dst.stride[1] * ((hl + 1) / 2);
+    }
+    return pix_convert_launch(c, AMVHIP_PIX_YUVJ420P, tight_420((uint8_t*)c->pix_dec.p, wl, hl), dst_fmt, dst, wl, hl, n, st);
+}
+
+extern "C" int amvhip_decode_lowres_batch(amvhip_ctx* c, const uint8_t* blob, uint64_t blob_bytes, const uint64_t* offs, const uint32_t* lens,
+                                          uint32_t n, uint32_t w, uint32_t h, uint32_t flags, uint32_t lowres, int dst_fmt, uint8_t* out,
+                                          uint32_t out_stride, int32_t* status) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (int r = lowres_args_ok(c, w, flags, lowres, dst_fmt, out_stride)) return r;
+    if (!size_ok(w, h) || (n && (!blob || !offs || !lens || !out))) return fail(c, AMVHIP_ERR_ARG, "decode_lowres: bad argument");
+    if (n == 0) return AMVHIP_OK;
+    hipStream_t st;
+    if (int r = host_stream(c, &st)) return r;
+    const uint64_t fb = pix_frame_bytes(dst_fmt, out_stride, lowres_dim(h, lowres));
+    std::lock_guard<std::mutex> hlk(c->hmu);
+    if (int r = stage(c, c->h_in, blob_bytes + 16, blob, blob_bytes, st)) return r;
+    if (int r = stage(c, c->h_offs, (size_t)n * 8, offs, (size_t)n * 8, st)) return r;
+    if (int r = stage(c, c->h_lens, (size_t)n * 4, lens, (size_t)n * 4, st)) return r;
+    // bytes between a row's end and out_stride stay as the CALLER had them: the caller's frames go up first
+    if (int r = ensure(c, c->h_out, fb * n)) return r;
+    if (dst_fmt != AMVHIP_PIX_YUVJ420P) HIP_TRY(c, hipMemcpyAsync(c->h_out.p, out, fb * n, hipMemcpyHostToDevice, st));
+    if (int r = ensure(c, c->h_status, (size_t)n * 4)) return r;
+    if (int r = amvhip_decode_lowres_batch_dev(c, (const uint8_t*)c->h_in.p, blob_bytes, (const uint64_t*)c->h_offs.p, (const uint32_t*)c->h_lens.p,
+                                               n, w, h, flags, lowres, dst_fmt, (uint8_t*)c->h_out.p, out_stride, (int32_t*)c->h_status.p, st))
+        return r;
+    HIP_TRY(c, hipMemcpyAsync(out, c->h_out.p, fb * n, hipMemcpyDeviceToHost, st));
+    if (status) HIP_TRY(c, hipMemcpyAsync(status, c->h_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return AMVHIP_OK;
+}

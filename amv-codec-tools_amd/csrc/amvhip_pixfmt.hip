@@ -165,6 +165,11 @@ int sws_args_ok(amvhip_ctx* c, int src_fmt, const PixPicture& src, uint32_t src_
 
 }  // namespace
 
+int amv::pix_convert_launch(amvhip_ctx* c, int src_fmt, const PixPicture& src, int dst_fmt, const PixPicture& dst, uint32_t w, uint32_t h, uint32_t n,
+                            hipStream_t st) {
+    return convert_launch(c, src_fmt, src, dst_fmt, dst, w, h, n, st);
+}
+
 extern "C" uint64_t amvhip_pix_frame_bytes(int fmt, uint32_t stride, uint32_t height) { return pix_frame_bytes(fmt, stride, height); }
 
 extern "C" int amvhip_img_convert_supported(int src_fmt, int dst_fmt, uint32_t w, uint32_t h) {

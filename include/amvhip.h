@@ -519,6 +519,52 @@ int amvhip_decode_fmt_batch_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t
                                 uint32_t width, uint32_t height, uint32_t flags, int dst_fmt,
                                 uint8_t *d_out, uint32_t out_stride, int32_t *d_status, void *stream);
 /*
+ * Reduced-size decode: pictures of 1/2, 1/4 or 1/8 the size (lowres = 1, 2, 3) straight from the entropy stage, for
+ * contact sheets, scrub bars and preview strips -- the full-size reconstruction is neither run nor written.
+ *
+ * The block arithmetic is the reference's `-lowres` (libavcodec/utils.c:707, dsputil.c:3870-3889, mjpegdec.c:711), byte
+ * for byte: decode_block's dequantisation (sp5x Q60 tables, +1024 on the DC), then j_rev_dct4 / j_rev_dct2 /
+ * j_rev_dct1 (jrevdct.c:952-1156) over the top-left 4x4 / 2x2 / 1x1 coefficients of each block, every store into
+ * the block wrapped to int16 as DCTELEM is, and put_pixels_clamped4_c / 2_c / ff_jref_idct1_put (dsputil.c:461-493,
+ * 3774-3801) with the 0..255 clamp of ff_cropTbl.
+ *
+ * The placement is this library's: the full-size placement of AMVHIP_FLAG_FFMPEG scaled down.  The reference's own
+ * cannot serve for AMV: its flip takes the start row from the full-size 8 * mb_height and does not shift it
+ * (mjpegdec.c:675), aiming the first block far below a picture that avcodec_set_dimensions (utils.c:141-142) has
+ * already shrunk, and ffmpeg.c:2699 sets CODEC_FLAG_EMU_EDGE whenever lowres is set, which that flip asserts
+ * against (mjpegdec.c:674).  The rule, with bs = 8 >> lowres and `start` the full-size start row of the component
+ * (v * (8 * mcu_rows - ((height / 2) & 7)) - 1 with v = 2 for luma and 1 for chroma: mjpegdec.c:675):
+ *     start_L = ((start + 1 + (1 << lowres) - 1) >> lowres) - 1;
+ *     row i of a block at canvas row sy, column sx (full-size units) lands at plane row start_L - ((sy >> lowres) + i),
+ *     column sx >> lowres; rows and columns outside the plane are dropped.
+ * Luma is W_L x H_L with W_L = amvhip_lowres_dim(width, lowres), H_L likewise; Cb and Cr are (W_L + 1) / 2 x
+ * (H_L + 1) / 2; the planes are tight, Y then Cb then Cr: amvhip_lowres_frame_bytes per frame.  For height % 16 of 0 or
+ * 8 this is the exact vertical flip of the reduced canvas; for other heights it keeps the full-size picture's row shift,
+ * so a thumbnail is a downscale of what the full-size mode shows.  Every byte of every plane is written by every call
+ * (plane rows no canvas row reaches -- height % 16 above 8 -- are zero); MCUs at or after a frame's first error are
+ * zero, as in the plain compat mode.
+ *
+ * amvhip_decode_lowres_batch_dev: arguments as amvhip_decode_fmt_batch_dev.  flags must be exactly AMVHIP_FLAG_FFMPEG
+ * (amvlib has no such mode; AMVHIP_FLAG_FFMPEG_KEEP is refused); lowres 1..3 (0 is refused: the full-size entry points
+ * stay the only way to their output).  dst_fmt AMVHIP_PIX_YUVJ420P writes the planes into d_out, and out_stride must
+ * equal W_L; every other format amvhip_decode_fmt_batch_dev takes goes through workspace planes and img_convert at
+ * W_L x H_L (d_out: n frames of amvhip_pix_frame_bytes(dst_fmt, out_stride, H_L)).  amvhip_decode_lowres_batch: the same
+ * from and to host buffers, synchronous.  amvhip_reconstruct_lowres_dev: the back half alone on dense coefficient lines,
+ * as amvhip_reconstruct_dev with AMVHIP_FLAG_FFMPEG (any int16 anywhere).
+ */
+uint32_t amvhip_lowres_dim(uint32_t full, uint32_t lowres);              /* ceil(full / 2^lowres); 0 for lowres > 3 */
+uint64_t amvhip_lowres_frame_bytes(uint32_t width, uint32_t height, uint32_t lowres);   /* the three tight planes */
+int amvhip_decode_lowres_batch_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes,
+                                   const uint64_t *d_offs, const uint32_t *d_lens, uint32_t n,
+                                   uint32_t width, uint32_t height, uint32_t flags, uint32_t lowres, int dst_fmt,
+                                   uint8_t *d_out, uint32_t out_stride, int32_t *d_status, void *stream);
+int amvhip_decode_lowres_batch(amvhip_ctx *ctx, const uint8_t *blob, uint64_t blob_bytes,
+                               const uint64_t *offs, const uint32_t *lens, uint32_t n,
+                               uint32_t width, uint32_t height, uint32_t flags, uint32_t lowres, int dst_fmt,
+                               uint8_t *out, uint32_t out_stride, int32_t *status);
+int amvhip_reconstruct_lowres_dev(amvhip_ctx *ctx, const int16_t *d_coef, const uint32_t *d_nmcu_ok, uint32_t n,
+                                  uint32_t width, uint32_t height, uint32_t lowres, uint8_t *d_out, void *stream);
+/*
  * The audio resampler in front of the ADPCM encoder: audio_resample (libavcodec/resample.c:129-242) over av_resample
  * (resample2.c:182-324), what ffmpeg.c:1639-1641 / :502 run for `-ac 1 -ar 22050` (AMVmuxer/Makefile:16).  16-tap (at
  * 0.8 of the lower rate's Nyquist: 40 taps at 44.1 kHz -> 22.05 kHz, 44 at 48 kHz, 88 at 96 kHz), 1024-phase, Kaiser-windowed
