@@ -123,6 +123,12 @@ SYMBOLS = {
     "amvhip_img_convert": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32]),
     "amvhip_sws_scale_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
     "amvhip_encode_fmt_scaled_batch_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_pad_color_from_rgb": (None, [_u32, _vp]),
+    "amvhip_deinterlace_supported": (_int, [_int, _u32, _u32]),
+    "amvhip_deinterlace_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
+    "amvhip_deinterlace": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32]),
+    "amvhip_video_frontend_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _vp]),
+    "amvhip_encode_frontend_batch_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "amvhip_decode_fmt_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
     "amvhip_lowres_dim": (_u32, [_u32, _u32]),
     "amvhip_lowres_frame_bytes": (_u64, [_u32, _u32, _u32]),
@@ -194,6 +200,23 @@ def load_library():
 
 class AmvHipError(RuntimeError):
     pass
+
+
+class Frontend(ctypes.Structure):
+    """amvhip_frontend of include/amvhip.h: the stages around the shim (all zero: none)"""
+    _fields_ = [("deinterlace", _u32), ("crop_top", _u32), ("crop_bottom", _u32), ("crop_left", _u32), ("crop_right", _u32),
+                ("pad_top", _u32), ("pad_bottom", _u32), ("pad_left", _u32), ("pad_right", _u32), ("pad_color", ctypes.c_uint8 * 3)]
+
+    def __init__(self, deinterlace=0, crop=(0, 0, 0, 0), pad=(0, 0, 0, 0), pad_color=(16, 128, 128)):
+        """crop and pad as (top, bottom, left, right)"""
+        super().__init__(int(deinterlace), *crop, *pad, (ctypes.c_uint8 * 3)(*pad_color))
+
+
+def pad_color_from_rgb(rrggbb):
+    """-padcolor RRGGBB -> (Y, Cb, Cr) as the pad bands are written; needs no device"""
+    out = (ctypes.c_uint8 * 3)()
+    load_library().amvhip_pad_color_from_rgb(rrggbb, ctypes.cast(out, ctypes.c_void_p))
+    return tuple(out)
 
 
 def _ptr(x):
@@ -340,6 +363,32 @@ class Context:
         return self._check(self.lib.amvhip_encode_fmt_scaled_batch_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n, w, h, qbias,
                                                                        _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), stream),
                            "encode_fmt_scaled_batch_dev")
+
+    # the video front end (deinterlace, crop, rescale / convert, pad).  fe: a Frontend, or None for all zero
+    @staticmethod
+    def _fe(fe):
+        return None if fe is None else ctypes.addressof(fe)
+
+    def pad_color_from_rgb(self, rrggbb):
+        return pad_color_from_rgb(rrggbb)
+
+    def deinterlace_supported(self, fmt, w, h):
+        return self.lib.amvhip_deinterlace_supported(fmt, w, h)
+
+    def deinterlace_dev(self, fmt, src, dst, w, h, n, stream=None):
+        return self._check(self.lib.amvhip_deinterlace_dev(self.h, fmt, *self._pic(src), *self._pic(dst), w, h, n, stream), "deinterlace_dev")
+
+    def deinterlace(self, fmt, src, dst, w, h, n):
+        return self._check(self.lib.amvhip_deinterlace(self.h, fmt, *self._pic(src), *self._pic(dst), w, h, n), "deinterlace")
+
+    def video_frontend_dev(self, src_fmt, src, src_w, src_h, n, fe, dst, w, h, stream=None):
+        return self._check(self.lib.amvhip_video_frontend_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n, self._fe(fe), *self._pic(dst),
+                                                              w, h, stream), "video_frontend_dev")
+
+    def encode_frontend_batch_dev(self, src_fmt, src, src_w, src_h, n, fe, w, h, qbias, blob, blob_cap, offs, lens, stream=None):
+        return self._check(self.lib.amvhip_encode_frontend_batch_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n, self._fe(fe), w, h,
+                                                                     qbias, _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), stream),
+                           "encode_frontend_batch_dev")
 
     def decode_fmt_batch_dev(self, blob, blob_bytes, offs, lens, n, w, h, flags, dst_fmt, out, out_stride, status, stream=None):
         return self._check(self.lib.amvhip_decode_fmt_batch_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, flags,

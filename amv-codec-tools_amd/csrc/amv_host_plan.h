@@ -258,6 +258,159 @@ inline uint64_t pix_frame_bytes(int fmt, uint32_t stride, uint32_t height) {
     return (uint64_t)stride * height + 2 * cs * cr;
 }
 
+// ---- video front end: deinterlace, crop, rescale / convert, pad (pre_process_video_frame + do_video_out) --------------
+
+// avpicture_deinterlace's own list (imgconvert.c:2824-2831) among our formats; the YUVJ formats are not in it
+inline int deinterlace_ok(int fmt, uint32_t w, uint32_t h) {
+    const bool listed = fmt == AMVHIP_PIX_YUV420P || fmt == AMVHIP_PIX_YUV422P || fmt == AMVHIP_PIX_YUV444P || fmt == AMVHIP_PIX_GRAY8;
+    return listed && size_ok(w, h) && !(w & 3) && !(h & 3);
+}
+
+// opt_pad_color (ffmpeg.c:2246-2271): RGB_TO_Y / _U / _V with shift 0 on r = rgb >> 16 (unmasked, as there), the ints
+// then written as bytes by av_picture_pad's memset
+inline void pad_color_from_rgb(uint32_t rrggbb, uint8_t out[3]) {
+    auto fix = [](double x) { return (int)(x * 1024 + 0.5); };
+    const int r = (int)(rrggbb >> 16), g = (int)((rrggbb >> 8) & 255u), b = (int)(rrggbb & 255u);
+    out[0] = (uint8_t)((fix(0.29900) * r + fix(0.58700) * g + fix(0.11400) * b + 512) >> 10);
+    out[1] = (uint8_t)(((-fix(0.16874) * r - fix(0.33126) * g + fix(0.50000) * b + 511) >> 10) + 128);
+    out[2] = (uint8_t)(((fix(0.50000) * r - fix(0.41869) * g - fix(0.08131) * b + 511) >> 10) + 128);
+}
+
+// chroma shifts of a planar YUV format (pix_fmt_info's x_chroma_shift / y_chroma_shift); 0, 0 for the others
+inline uint32_t pix_xshift(int f) { return pix_planar_yuv(f) && !pix_444(f) ? 1u : 0u; }
+inline uint32_t pix_yshift(int f) { return pix_420(f) ? 1u : 0u; }
+
+struct FrontRect { uint32_t x, y, w, h; };   // samples of one plane
+
+enum FrontRefusal { kFrontOk = 0, kFrontOddBand, kFrontCropNotPlanar, kFrontCropTooLarge, kFrontPadTooLarge, kFrontOddTarget, kFrontNoRoute };
+
+inline const char* front_refusal_text(int r) {
+    switch (r) {
+        case kFrontOddBand: return "crop and pad bands are even";
+        case kFrontCropNotPlanar: return "only planar YUV sources are cropped (av_picture_crop)";
+        case kFrontCropTooLarge: return "the crop bands leave less than 2x2 of the source";
+        case kFrontPadTooLarge: return "the pad bands leave a window of less than 2x2";
+        case kFrontOddTarget: return "bad source or target size (the target's width and height are even)";
+        case kFrontNoRoute: return "the shim has no route from the source format to YUVJ420P at these sizes";
+        default: return "";
+    }
+}
+
+struct FrontPlan {
+    int refusal;                 // kFrontOk: the rest is valid
+    bool deinterlace;            // the stage runs (asked for and avpicture_deinterlace takes the format and size)
+    bool crop, pad;
+    bool rescale;                // ffmpeg.c:1653-1659: the sizes or the format differ -> sws_scale; else the copy route
+    uint32_t src_planes;         // planes of the source format
+    uint32_t crop_w, crop_h;     // the rescaler's source size
+    uint32_t win_w, win_h;       // the rescaler's target size
+    FrontRect src_full[3];       // x = y = 0: the source planes (w in bytes of a row)
+    FrontRect src_win[3];        // what the crop keeps of them
+    FrontRect dst_full[3];       // the encoder's YUVJ420P planes
+    FrontRect dst_win[3];        // the window the rescaler (or the copy) fills; the rest of dst_full is bands
+    uint64_t deint_frame_bytes;  // workspace per frame: the deinterlaced window, tight, planes 16-byte aligned (0: stage off)
+    uint64_t deint_plane_off[3];
+    uint64_t padded_frame_bytes; // workspace per frame of the encoder's picture (tight YUV420P layout)
+};
+
+// every band of *fe zero (fe == NULL too)
+inline bool front_is_identity(const amvhip_frontend* fe) {
+    return !fe || !(fe->deinterlace | fe->crop_top | fe->crop_bottom | fe->crop_left | fe->crop_right | fe->pad_top | fe->pad_bottom |
+                    fe->pad_left | fe->pad_right);
+}
+
+// the shim's own demands on a pair of sizes towards YUVJ420P (what amvhip_sws_scale_dev checks before it looks at pointers)
+inline bool front_shim_ok(int src_fmt, uint32_t sw, uint32_t sh, uint32_t dw, uint32_t dh) {
+    if (src_fmt < 0 || src_fmt >= AMVHIP_PIX_COUNT || !size_ok(sw, sh) || !size_ok(dw, dh)) return false;
+    if (sw == dw && sh == dh)
+        return src_fmt == AMVHIP_PIX_YUVJ420P || (pix_route(src_fmt, AMVHIP_PIX_YUVJ420P) != kRouteNone && pix_size_ok(src_fmt, AMVHIP_PIX_YUVJ420P, dw, dh));
+    if (sw < 2 || sh < 2 || dw < 2 || dh < 2) return false;
+    return src_fmt == AMVHIP_PIX_YUV420P || (pix_route(src_fmt, AMVHIP_PIX_YUV420P) != kRouteNone && pix_size_ok(src_fmt, AMVHIP_PIX_YUV420P, sw, sh));
+}
+
+inline FrontPlan front_plan(int src_fmt, uint32_t src_w, uint32_t src_h, const amvhip_frontend* fe, uint32_t width, uint32_t height) {
+    static const amvhip_frontend none = {};
+    const amvhip_frontend& f = fe ? *fe : none;
+    FrontPlan p;
+    memset(&p, 0, sizeof p);
+    auto refuse = [&p](int why) { p.refusal = why; return p; };
+    if (src_fmt < 0 || src_fmt >= AMVHIP_PIX_COUNT || !size_ok(src_w, src_h) || !size_ok(width, height) || (width & 1) || (height & 1))
+        return refuse(kFrontOddTarget);
+    if ((f.crop_top | f.crop_bottom | f.crop_left | f.crop_right | f.pad_top | f.pad_bottom | f.pad_left | f.pad_right) & 1u) return refuse(kFrontOddBand);
+    p.crop = (f.crop_top | f.crop_bottom | f.crop_left | f.crop_right) != 0;
+    p.pad = (f.pad_top | f.pad_bottom | f.pad_left | f.pad_right) != 0;
+    if (p.crop && !pix_planar_yuv(src_fmt)) return refuse(kFrontCropNotPlanar);
+    if ((uint64_t)f.crop_top + f.crop_bottom + 2u > src_h || (uint64_t)f.crop_left + f.crop_right + 2u > src_w) return refuse(kFrontCropTooLarge);
+    if ((uint64_t)f.pad_top + f.pad_bottom + 2u > height || (uint64_t)f.pad_left + f.pad_right + 2u > width) return refuse(kFrontPadTooLarge);
+    p.crop_w = src_w - f.crop_left - f.crop_right;
+    p.crop_h = src_h - f.crop_top - f.crop_bottom;
+    p.win_w = width - f.pad_left - f.pad_right;
+    p.win_h = height - f.pad_top - f.pad_bottom;
+    if (!front_shim_ok(src_fmt, p.crop_w, p.crop_h, p.win_w, p.win_h)) return refuse(kFrontNoRoute);
+    p.rescale = p.crop_w != p.win_w || p.crop_h != p.win_h || src_fmt != AMVHIP_PIX_YUVJ420P;
+    p.deinterlace = f.deinterlace && deinterlace_ok(src_fmt, src_w, src_h);
+    const uint32_t xs = pix_xshift(src_fmt), ys = pix_yshift(src_fmt);
+    for (uint32_t i = 0; i < 3; ++i) {
+        uint32_t rb, rows;
+        pix_plane_size(src_fmt, i, src_w, src_h, &rb, &rows);
+        if (!rows) continue;
+        p.src_planes = i + 1;
+        p.src_full[i] = FrontRect{0, 0, rb, rows};
+        if (!p.crop) { p.src_win[i] = p.src_full[i]; continue; }
+        // av_picture_crop (imgconvert.c:2236-2238): the origin moves by the band >> shift; the size is the cropped picture's plane
+        uint32_t wb, wr;
+        pix_plane_size(src_fmt, i, p.crop_w, p.crop_h, &wb, &wr);
+        p.src_win[i] = FrontRect{i ? f.crop_left >> xs : f.crop_left, i ? f.crop_top >> ys : f.crop_top, wb, wr};
+    }
+    for (uint32_t i = 0; i < 3; ++i) {
+        const uint32_t s = i ? 1u : 0u;
+        p.dst_full[i] = FrontRect{0, 0, width >> s, height >> s};
+        p.dst_win[i] = FrontRect{f.pad_left >> s, f.pad_top >> s, p.win_w >> s, p.win_h >> s};
+    }
+    if (p.deinterlace) {
+        uint64_t off = 0;
+        for (uint32_t i = 0; i < p.src_planes; ++i) {
+            p.deint_plane_off[i] = off;
+            off += ((uint64_t)p.src_win[i].w * p.src_win[i].h + 15u) & ~15ull;
+        }
+        p.deint_frame_bytes = off;
+    }
+    p.padded_frame_bytes = (uint64_t)width * height + 2ull * (width / 2) * (height / 2);
+    return p;
+}
+
+// The bands of one padded plane as items of up to four bytes, for amv_pad_bands_kernel: the rows above and below the window
+// whole (ceil(W / 4) items a row), then the columns left and right of the window on its own rows.  Host and device count
+// and place them with these functions.
+struct PadPlane {
+    uint32_t W, H;               // the plane
+    uint32_t wx, wy, ww, wh;     // the window inside it
+    uint32_t color;              // the byte, four times over
+};
+struct PadItem { uint32_t row, col, len; };
+#if defined(__HIPCC__)
+#define AMV_HD __host__ __device__
+#else
+#define AMV_HD
+#endif
+AMV_HD inline uint32_t pad_items(const PadPlane& q) {
+    const uint32_t right = q.W - q.wx - q.ww;
+    return (q.H - q.wh) * ((q.W + 3u) >> 2) + q.wh * (((q.wx + 3u) >> 2) + ((right + 3u) >> 2));
+}
+AMV_HD inline PadItem pad_item(const PadPlane& q, uint32_t t) {
+    const uint32_t per_row = (q.W + 3u) >> 2, full = (q.H - q.wh) * per_row;
+    if (t < full) {
+        const uint32_t r = t / per_row, k = t - r * per_row, col = 4u * k;
+        return PadItem{r < q.wy ? r : r + q.wh, col, q.W - col < 4u ? q.W - col : 4u};
+    }
+    t -= full;
+    const uint32_t right = q.W - q.wx - q.ww, nl = (q.wx + 3u) >> 2, per = nl + ((right + 3u) >> 2);
+    const uint32_t r = t / per, k = t - r * per;
+    if (k < nl) return PadItem{q.wy + r, 4u * k, q.wx - 4u * k < 4u ? q.wx - 4u * k : 4u};
+    const uint32_t off = 4u * (k - nl);
+    return PadItem{q.wy + r, q.wx + q.ww + off, right - off < 4u ? right - off : 4u};
+}
+
 // ---- audio resample -----------------------------------------------------------------------------
 
 constexpr uint32_t kBankPhases = 1024;   // kAudioPhases of amv_kernels.h (the audio entry points assert that they agree)

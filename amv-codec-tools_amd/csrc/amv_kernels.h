@@ -200,6 +200,25 @@ void launch_pix_rgb_in(const PixPicture& src, const PixPicture& dst, uint32_t w,
 void launch_pix_rgb_out(const PixPicture& src, const PixPicture& dst, uint32_t w, uint32_t h, uint32_t bpp, const PixRgbOut& k, uint32_t n,
                         hipStream_t s);
 
+// ---- video front end (amv_frontend.hip): avpicture_deinterlace and av_picture_pad's bands ------------------------------
+struct DeintPlane {         // one plane: the window x0, y0, w, h of a source plane of full_h rows -> a destination of w x h
+    const uint8_t* src;     // the FULL plane's origin
+    uint8_t* dst;           // the window's origin
+    uint32_t sstride, dstride;
+    uint64_t sframe, dframe;
+    uint32_t x0, y0, w, h, full_h;
+};
+struct DeintJobs { DeintPlane j[3]; uint32_t count; };
+void launch_deinterlace(const DeintJobs& jobs, uint32_t n, hipStream_t s);
+struct PadBandPlane {       // one padded plane: geometry as PadPlane of amv_host_plan.h (the items are counted and placed there)
+    uint8_t* dst;
+    uint32_t stride;
+    uint64_t frame;
+    uint32_t W, H, wx, wy, ww, wh, color;
+};
+struct PadBandJobs { PadBandPlane j[3]; };
+void launch_pad_bands(const PadBandJobs& jobs, uint32_t n, hipStream_t s);
+
 // ---- audio resample (amv_audio_resample.hip): audio_resample of libavcodec/resample.c over av_resample (resample2.c) --
 constexpr uint32_t kAudioPhases = 1024;                       // 1 << phase_shift (resample.c:165)
 constexpr uint32_t kAudioSpan = 4096;                         // input frames of one workgroup's LDS span (per channel)

@@ -1,7 +1,7 @@
 // amvhip_ctx.h -- the context behind the C ABI of include/amvhip.h, and what its files share (internal to libamvhip.so).
 //
 // The ABI is split by domain: amvhip_context.hip (context, timing, statistics), amvhip_decode.hip, amvhip_encode.hip
-// (encoders, picture rescale), amvhip_pixfmt.hip (img_convert, the sws_scale shim) and amvhip_audio.hip (resampler, ADPCM).
+// (encoders, picture rescale), amvhip_pixfmt.hip (img_convert, the sws_scale shim, the video front end) and amvhip_audio.hip (resampler, ADPCM).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -52,6 +52,8 @@ struct amvhip_ctx {
     DevBuf coef, tmp, flag, map, start, enc_retry, stats, ws, ws_line, layout, ws_bytes, scaled, trellis_ws, chain, split;
     // the shim around the rescaler: the source as YUV420P, the rescaled YUV420P ahead of a last conversion, the decoder's planes
     DevBuf pix_in, pix_out, pix_dec;
+    // the video front end: the deinterlaced (and cropped) source ahead of the shim
+    DevBuf fe_deint;
     // audio resampler: filter banks by (in_rate << 32 | out_rate), uploaded once and kept; the tile counts of the last call
     std::map<uint64_t, DevBuf> audio_banks;
     DevBuf audio_tiles;

@@ -1,5 +1,5 @@
-// amvhip_pixfmt.hip -- pixel formats behind the C ABI: img_convert, the sws_scale shim, and the shim joined to the
-// encoder and the decoder.
+// amvhip_pixfmt.hip -- pixel formats behind the C ABI: img_convert, the sws_scale shim, the shim joined to the encoder and
+// the decoder, and the stages of ffmpeg's video front end around it (deinterlace, crop, pad).
 #include "amvhip_ctx.h"
 
 using namespace amv;
@@ -192,16 +192,12 @@ extern "C" int amvhip_img_convert_dev(amvhip_ctx* c, int src_fmt, const uint8_t*
     return convert_launch(c, src_fmt, src, dst_fmt, dst, w, h, n, (hipStream_t)stream);
 }
 
-// host buffers: the planes are staged tight on the device (rows of exactly the row's bytes), converted, and the
-// destination rows copied back row by row -- bytes between the caller's rows and frames are never touched
-extern "C" int amvhip_img_convert(amvhip_ctx* c, int src_fmt, const uint8_t* src0, const uint8_t* src1, const uint8_t* src2,
-                                  uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
-                                  int dst_fmt, uint8_t* dst0, uint8_t* dst1, uint8_t* dst2, uint32_t dst_stride, uint32_t dst_c_stride,
-                                  uint64_t dst_frame_stride, uint64_t dst_c_frame_stride, uint32_t w, uint32_t h, uint32_t n) {
-    if (!c) return AMVHIP_ERR_ARG;
-    if (int r = convert_args_ok(c, src_fmt, dst_fmt, w, h)) return r;
-    const PixPicture hs = make_picture(src0, src1, src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
-    const PixPicture hd = make_picture(dst0, dst1, dst2, dst_stride, dst_c_stride, dst_frame_stride, dst_c_frame_stride);
+// host buffers: the planes are staged tight on the device (rows of exactly the row's bytes), `launch`ed on (staged source,
+// staged destination, stream; the context locked), and the destination rows copied back row by row -- bytes between the
+// caller's rows and frames are never touched
+template <class Launch>
+static int host_staged(amvhip_ctx* c, const char* what, int src_fmt, const PixPicture& hs, int dst_fmt, const PixPicture& hd, uint32_t w, uint32_t h,
+                uint32_t n, Launch launch) {
     PixPicture ds{}, dd{};
     uint64_t bytes[2] = {0, 0};
     for (int side = 0; side < 2; ++side) {
@@ -212,7 +208,7 @@ extern "C" int amvhip_img_convert(amvhip_ctx* c, int src_fmt, const uint8_t* src
         for (uint32_t p = 0; p < 3; ++p) {
             uint32_t rb, rows;
             pix_plane_size(f, p, w, h, &rb, &rows);
-            if (rows && (!hp.p[p] || hp.stride[p] < rb)) return fail(c, AMVHIP_ERR_ARG, "img_convert: null plane, or a row pitch below the row");
+            if (rows && (!hp.p[p] || hp.stride[p] < rb)) return fail(c, AMVHIP_ERR_ARG, "%s: null plane, or a row pitch below the row", what);
             dp.stride[p] = rb;
             off[p + 1] = off[p] + (((uint64_t)rb * rows + 15u) & ~15ull);    // every staged plane starts 16-byte aligned
         }
@@ -236,7 +232,7 @@ extern "C" int amvhip_img_convert(amvhip_ctx* c, int src_fmt, const uint8_t* src
         const int f = side ? dst_fmt : src_fmt;
         if (side) {
             std::lock_guard<std::mutex> lk(c->mu);
-            if (int r = convert_launch(c, src_fmt, ds, dst_fmt, dd, w, h, n, st)) return r;
+            if (int r = launch(ds, dd, st)) return r;
         }
         for (uint32_t p = 0; p < 3; ++p) {
             uint32_t rb, rows;
@@ -254,6 +250,19 @@ extern "C" int amvhip_img_convert(amvhip_ctx* c, int src_fmt, const uint8_t* src
     }
     HIP_TRY(c, hipStreamSynchronize(st));
     return AMVHIP_OK;
+}
+
+extern "C" int amvhip_img_convert(amvhip_ctx* c, int src_fmt, const uint8_t* src0, const uint8_t* src1, const uint8_t* src2,
+                                  uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                                  int dst_fmt, uint8_t* dst0, uint8_t* dst1, uint8_t* dst2, uint32_t dst_stride, uint32_t dst_c_stride,
+                                  uint64_t dst_frame_stride, uint64_t dst_c_frame_stride, uint32_t w, uint32_t h, uint32_t n) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (int r = convert_args_ok(c, src_fmt, dst_fmt, w, h)) return r;
+    return host_staged(c, "img_convert", src_fmt, make_picture(src0, src1, src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride),
+                       dst_fmt, make_picture(dst0, dst1, dst2, dst_stride, dst_c_stride, dst_frame_stride, dst_c_frame_stride), w, h, n,
+                       [&](const PixPicture& ds, const PixPicture& dd, hipStream_t st) {
+                           return convert_launch(c, src_fmt, ds, dst_fmt, dd, w, h, n, st);
+                       });
 }
 
 extern "C" int amvhip_sws_scale_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2,
@@ -331,3 +340,184 @@ extern "C" int amvhip_decode_fmt_batch_dev(amvhip_ctx* c, const uint8_t* d_blob,
     return convert_launch(c, AMVHIP_PIX_YUVJ420P, tight_420((uint8_t*)c->pix_dec.p, w, h), dst_fmt, dst, w, h, n, (hipStream_t)stream);
 }
 
+
+// ---- the video front end: pre_process_video_frame (ffmpeg.c:579-623) and do_video_out up to the encoder (:730-765) ------
+namespace {
+
+// avpicture_deinterlace over the window `win` of every plane (the whole planes: win = full), n frames, on st
+int deinterlace_launch(amvhip_ctx* c, const PixPicture& src, const PixPicture& dst, uint32_t planes, const FrontRect* full, const FrontRect* win,
+                       uint32_t n, hipStream_t st) {
+    Timed t(c, AMVHIP_K_PIXFMT, st);
+    DeintJobs jobs{};
+    jobs.count = planes;
+    for (uint32_t p = 0; p < planes; ++p)
+        jobs.j[p] = DeintPlane{src.p[p], dst.p[p], src.stride[p], dst.stride[p], src.frame[p], dst.frame[p], win[p].x, win[p].y, win[p].w, win[p].h,
+                               full[p].h};
+    launch_deinterlace(jobs, n, st);
+    return check_launch(c, "deinterlace");
+}
+
+// the bytes [first, end) the n frames of plane p touch
+void plane_span(int fmt, const PixPicture& pic, uint32_t p, uint32_t w, uint32_t h, uint32_t n, uintptr_t* first, uintptr_t* end) {
+    uint32_t rb, rows;
+    pix_plane_size(fmt, p, w, h, &rb, &rows);
+    *first = (uintptr_t)pic.p[p];
+    *end = rows && n ? *first + (uint64_t)(n - 1) * pic.frame[p] + (uint64_t)(rows - 1) * pic.stride[p] + rb : *first;
+}
+
+int deinterlace_args_ok(amvhip_ctx* c, int fmt, uint32_t w, uint32_t h) {
+    if (!deinterlace_ok(fmt, w, h))
+        return fail(c, AMVHIP_ERR_ARG, "deinterlace: format %d at %ux%u is not taken (YUV420P, YUV422P, YUV444P, GRAY8; sizes multiples of 4)", fmt, w, h);
+    return AMVHIP_OK;
+}
+
+int deinterlace_whole(amvhip_ctx* c, int fmt, const PixPicture& src, const PixPicture& dst, uint32_t w, uint32_t h, uint32_t n, hipStream_t st) {
+    FrontRect full[3] = {};
+    uint32_t planes = 0;
+    for (uint32_t i = 0; i < 3; ++i) {
+        uint32_t rb, rows;
+        pix_plane_size(fmt, i, w, h, &rb, &rows);
+        if (!rows) continue;
+        full[i] = FrontRect{0, 0, rb, rows};
+        planes = i + 1;
+    }
+    return deinterlace_launch(c, src, dst, planes, full, full, n, st);
+}
+
+// the stages in the reference's order into dst (YUVJ420P, width x height); c->mu held, every argument checked
+int frontend_core(amvhip_ctx* c, int src_fmt, const PixPicture& src, uint32_t n, const amvhip_frontend* fe, const FrontPlan& p, const PixPicture& dst,
+                  hipStream_t st) {
+    PixPicture cur = src;
+    if (p.deinterlace) {
+        // deinterlace, then crop: only what the crop keeps is made, tight, in the source's format
+        if (int r = ensure(c, c->fe_deint, p.deint_frame_bytes * n)) return r;
+        PixPicture d{};
+        for (uint32_t i = 0; i < p.src_planes; ++i) {
+            d.p[i] = (uint8_t*)c->fe_deint.p + p.deint_plane_off[i];
+            d.stride[i] = p.src_win[i].w;
+            d.frame[i] = p.deint_frame_bytes;
+        }
+        if (int r = deinterlace_launch(c, src, d, p.src_planes, p.src_full, p.src_win, n, st)) return r;
+        cur = d;
+    } else if (p.crop) {
+        for (uint32_t i = 0; i < p.src_planes; ++i) cur.p[i] += (uint64_t)p.src_win[i].y * cur.stride[i] + p.src_win[i].x;   // av_picture_crop
+    }
+    PixPicture win = dst;                                            // resampling_dst: a cropped view of the padded picture
+    for (uint32_t i = 0; i < 3; ++i) win.p[i] += (uint64_t)p.dst_win[i].y * win.stride[i] + p.dst_win[i].x;
+    if (int r = sws_core(c, src_fmt, cur, p.crop_w, p.crop_h, AMVHIP_PIX_YUVJ420P, win, p.win_w, p.win_h, n, st)) return r;
+    if (!p.pad) return AMVHIP_OK;
+    Timed t(c, AMVHIP_K_PIXFMT, st);
+    PadBandJobs jobs{};
+    for (uint32_t i = 0; i < 3; ++i)
+        jobs.j[i] = PadBandPlane{dst.p[i], dst.stride[i], dst.frame[i], p.dst_full[i].w, p.dst_full[i].h, p.dst_win[i].x, p.dst_win[i].y,
+                                 p.dst_win[i].w, p.dst_win[i].h, (fe ? fe->pad_color[i] : 0u) * 0x01010101u};
+    launch_pad_bands(jobs, n, st);
+    return check_launch(c, "pad bands");
+}
+
+// what both front-end entries ask of the source and of the bands; *p filled
+int frontend_args_ok(amvhip_ctx* c, int src_fmt, const PixPicture& src, uint32_t src_w, uint32_t src_h, const amvhip_frontend* fe, uint32_t w,
+                     uint32_t h, FrontPlan* p) {
+    *p = front_plan(src_fmt, src_w, src_h, fe, w, h);
+    if (p->refusal) return fail(c, AMVHIP_ERR_ARG, "video front end: %s", front_refusal_text(p->refusal));
+    if (!pix_picture_ok(src_fmt, src, src_w, src_h))
+        return fail(c, AMVHIP_ERR_ARG, "video front end: null or misaligned source plane, or a row pitch below the row");
+    return AMVHIP_OK;
+}
+
+}  // namespace
+
+extern "C" void amvhip_pad_color_from_rgb(uint32_t rrggbb, uint8_t out[3]) {
+    if (out) pad_color_from_rgb(rrggbb, out);
+}
+
+extern "C" int amvhip_deinterlace_supported(int fmt, uint32_t w, uint32_t h) { return deinterlace_ok(fmt, w, h); }
+
+extern "C" int amvhip_deinterlace_dev(amvhip_ctx* c, int fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2,
+                                      uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                                      uint8_t* d_dst0, uint8_t* d_dst1, uint8_t* d_dst2, uint32_t dst_stride, uint32_t dst_c_stride,
+                                      uint64_t dst_frame_stride, uint64_t dst_c_frame_stride, uint32_t w, uint32_t h, uint32_t n, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (int r = deinterlace_args_ok(c, fmt, w, h)) return r;
+    const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    const PixPicture dst = make_picture(d_dst0, d_dst1, d_dst2, dst_stride, dst_c_stride, dst_frame_stride, dst_c_frame_stride);
+    if (!pix_picture_ok(fmt, src, w, h) || !pix_picture_ok(fmt, dst, w, h))
+        return fail(c, AMVHIP_ERR_ARG, "deinterlace: null or misaligned plane, or a row pitch below the row");
+    // out of place only: a lane reads rows that another lane writes
+    const uint32_t planes = fmt == AMVHIP_PIX_GRAY8 ? 1u : 3u;
+    for (uint32_t i = 0; i < planes; ++i)
+        for (uint32_t k = 0; k < planes; ++k) {
+            uintptr_t s0, s1, d0, d1;
+            plane_span(fmt, src, i, w, h, n, &s0, &s1);
+            plane_span(fmt, dst, k, w, h, n, &d0, &d1);
+            if (s0 < d1 && d0 < s1) return fail(c, AMVHIP_ERR_ARG, "deinterlace: source and destination overlap");
+        }
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return deinterlace_whole(c, fmt, src, dst, w, h, n, (hipStream_t)stream);
+}
+
+extern "C" int amvhip_deinterlace(amvhip_ctx* c, int fmt, const uint8_t* src0, const uint8_t* src1, const uint8_t* src2, uint32_t src_stride,
+                                  uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint8_t* dst0, uint8_t* dst1,
+                                  uint8_t* dst2, uint32_t dst_stride, uint32_t dst_c_stride, uint64_t dst_frame_stride,
+                                  uint64_t dst_c_frame_stride, uint32_t w, uint32_t h, uint32_t n) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (int r = deinterlace_args_ok(c, fmt, w, h)) return r;
+    const PixPicture hs = make_picture(src0, src1, src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    const PixPicture hd = make_picture(dst0, dst1, dst2, dst_stride, dst_c_stride, dst_frame_stride, dst_c_frame_stride);
+    const uint32_t planes = fmt == AMVHIP_PIX_GRAY8 ? 1u : 3u;
+    for (uint32_t i = 0; i < planes; ++i)
+        for (uint32_t k = 0; k < planes; ++k) {
+            if (!hs.p[i] || !hd.p[k]) return fail(c, AMVHIP_ERR_ARG, "deinterlace: null plane");
+            uintptr_t s0, s1, d0, d1;
+            plane_span(fmt, hs, i, w, h, n, &s0, &s1);
+            plane_span(fmt, hd, k, w, h, n, &d0, &d1);
+            if (s0 < d1 && d0 < s1) return fail(c, AMVHIP_ERR_ARG, "deinterlace: source and destination overlap");
+        }
+    return host_staged(c, "deinterlace", fmt, hs, fmt, hd, w, h, n, [&](const PixPicture& ds, const PixPicture& dd, hipStream_t st) {
+        return deinterlace_whole(c, fmt, ds, dd, w, h, n, st);
+    });
+}
+
+extern "C" int amvhip_video_frontend_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2,
+                                         uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                                         uint32_t src_w, uint32_t src_h, uint32_t n, const amvhip_frontend* fe, uint8_t* d_y, uint8_t* d_cb,
+                                         uint8_t* d_cr, uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                         uint32_t w, uint32_t h, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    const PixPicture dst = make_picture(d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride);
+    FrontPlan p;
+    if (int r = frontend_args_ok(c, src_fmt, src, src_w, src_h, fe, w, h, &p)) return r;
+    if (!pix_picture_ok(AMVHIP_PIX_YUVJ420P, dst, w, h))
+        return fail(c, AMVHIP_ERR_ARG, "video front end: null or misaligned destination plane, or a row pitch below the row");
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);   // the intermediates are the context's
+    return frontend_core(c, src_fmt, src, n, fe, p, dst, (hipStream_t)stream);
+}
+
+extern "C" int amvhip_encode_frontend_batch_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2,
+                                                uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride,
+                                                uint64_t src_c_frame_stride, uint32_t src_w, uint32_t src_h, uint32_t n,
+                                                const amvhip_frontend* fe, uint32_t w, uint32_t h, uint32_t qbias, uint8_t* d_blob,
+                                                uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    // no stage asked for: the entry without them, its fused and direct routes included
+    if (front_is_identity(fe))
+        return amvhip_encode_fmt_scaled_batch_dev(c, src_fmt, d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride,
+                                                  src_w, src_h, n, w, h, qbias, d_blob, blob_cap, d_offs, d_lens, stream);
+    if (!encode_size_ok(w, h, qbias) || (n && (!d_blob || !d_offs || !d_lens)))
+        return fail(c, AMVHIP_ERR_ARG, "encode_frontend: bad argument (width/height must be even)");
+    const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    FrontPlan p;
+    if (int r = frontend_args_ok(c, src_fmt, src, src_w, src_h, fe, w, h, &p)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    // the padded picture is the context's: the lock is held from its allocation to the last launch that reads it
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int r = ensure(c, c->scaled, p.padded_frame_bytes * n)) return r;
+    if (int r = frontend_core(c, src_fmt, src, n, fe, p, tight_420((uint8_t*)c->scaled.p, w, h), (hipStream_t)stream)) return r;
+    return encode_scaled_tail(c, n, w, h, qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+}

@@ -420,9 +420,9 @@ int amvhip_encode_yuv420_scaled_batch_dev(amvhip_ctx *ctx, const uint8_t *d_y, c
  * 0, 0 for the rest).  A picture is handed over flat, as in amvhip_resample_yuv420_dev: plane pointers, the row pitch of
  * plane 0 and of the chroma planes, the frame pitch of plane 0 and of the chroma planes (bytes); frame i's planes start
  * i frame pitches on.  Plane pointers must be 4-byte aligned.  No byte beyond a row's bytes and no row beyond the
- * picture's height is written: pictures may be strided.  Cropping (av_picture_crop, ffmpeg.c:730-738) is pointer and size
- * arithmetic the caller does on planar sources.  Padding (av_picture_pad) and the -r frame duplication / dropping of
- * ffmpeg.c:705-728 are not offered.
+ * picture's height is written: pictures may be strided.  Deinterlacing (avpicture_deinterlace), cropping (av_picture_crop,
+ * ffmpeg.c:730-738) and padding (av_picture_pad) are amvhip_video_frontend_dev's, further down.  The -r frame duplication /
+ * dropping of ffmpeg.c:705-728 is not offered.
  *
  * A (src, dst) pair is supported when the reference reaches it in ONE step -- a routine of convert_table
  * (imgconvert.c:1940-2190), the planar route (:2415-2513: luma copied, chroma through ff_img_copy_plane / shrink12 /
@@ -505,6 +505,67 @@ int amvhip_encode_fmt_scaled_batch_dev(amvhip_ctx *ctx, int src_fmt, const uint8
                                        uint64_t src_c_frame_stride, uint32_t src_width, uint32_t src_height, uint32_t n,
                                        uint32_t width, uint32_t height, uint32_t qbias, uint8_t *d_blob, uint64_t blob_cap,
                                        uint64_t *d_offs, uint32_t *d_lens, void *stream);
+/*
+ * The rest of ffmpeg's video front end: -deinterlace (pre_process_video_frame, ffmpeg.c:579-623), -crop*, -pad* and
+ * -padcolor (do_video_out, :730-765), around the shim above.  The stages run in the reference's order, each byte for byte
+ * its own: deinterlace at the source size and format, crop, sws_scale into the window of the padded picture, the bands.
+ *
+ * Deinterlace (avpicture_deinterlace, imgconvert.c:2673-2864, the C branch): per plane, even rows copied, odd row 2k + 1 =
+ * clamp((-r[2k-1] + 4 r[2k] + 2 r[2k+1] + 4 r[2k+2] - r[2k+3] + 4) >> 3) with r[-1] = r[0] and, for the last row, both rows
+ * below it the row itself.  Accepted for YUV420P, YUV422P, YUV444P and GRAY8 with width and height multiples of 4
+ * (amvhip_deinterlace_supported; no context or device needed) -- the YUVJ formats are not in the reference's list.
+ * amvhip_deinterlace_dev / amvhip_deinterlace (host buffers, synchronous) are the stage alone: one format for both
+ * sides, pictures flat as in amvhip_img_convert_dev; anything else than the list returns AMVHIP_ERR_ARG, and so do source
+ * and destination that overlap (the reference's in-place form, :2794-2817, gives the same bytes as its out-of-place one, so
+ * nothing is lost).  ffmpeg.c:602-608 goes on without deinterlacing when the routine refuses: amvhip_video_frontend_dev
+ * does the same, a caller of the stage alone asks amvhip_deinterlace_supported first.
+ *
+ * Crop (av_picture_crop, :2224-2244): planar YUV sources only (AMVHIP_ERR_ARG otherwise), plane origins moved by
+ * top, left (chroma: >> the format's shifts).  Behind a deinterlace only the kept rows and columns are computed.
+ * Pad (av_picture_pad, :2246-2304): the encoder's picture is width x height, the rescaler's target the window
+ * (width - pad_left - pad_right) x (height - pad_top - pad_bottom) inside it; the bands of plane i are the byte pad_color[i]
+ * written unconverted into the YUVJ420P planes ({16, 128, 128} is ffmpeg's default; amvhip_pad_color_from_rgb is
+ * -padcolor RRGGBB's arithmetic, ffmpeg.c:2246-2271).  The result is defined for every combination: the window is the
+ * rescaled (or, sizes and format equal, copied) picture, every other byte the colour.  The reference is that too, except with
+ * crop + pad and no rescale, where its row copy takes the uncropped pitch and runs past the window (and, without a bottom or
+ * right band, past the buffer): there it is not a function of its input, and the clean result is ours.
+ *
+ * All bands are even (AMVHIP_ERR_ARG), leave at least 2 x 2 of the source and of the window, and the shim must have a
+ * route from src_fmt at the cropped size to YUVJ420P at the window's size.  fe == NULL: every field zero.
+ *
+ * amvhip_video_frontend_dev         n YUVJ420P pictures of width x height (even) into the caller's planes
+ * amvhip_encode_frontend_batch_dev  the same into the context's workspace, then the encoder; with fe NULL or all zero it IS
+ *                                   amvhip_encode_fmt_scaled_batch_dev (its fused RGB24 / BGR24 and direct YUVJ420P routes too);
+ *                                   a blob too small is reported as there: the chunks that do not fit have length 0
+ */
+typedef struct amvhip_frontend {
+    uint32_t deinterlace;                                    /* 0 / 1 */
+    uint32_t crop_top, crop_bottom, crop_left, crop_right;   /* source pixels, even */
+    uint32_t pad_top, pad_bottom, pad_left, pad_right;       /* encoder pixels, even */
+    uint8_t pad_color[3];                                    /* Y, Cb, Cr as written; {16,128,128} is ffmpeg's default */
+} amvhip_frontend;
+void amvhip_pad_color_from_rgb(uint32_t rrggbb, uint8_t out[3]);
+int amvhip_deinterlace_supported(int fmt, uint32_t width, uint32_t height);
+int amvhip_deinterlace_dev(amvhip_ctx *ctx, int fmt, const uint8_t *d_src0, const uint8_t *d_src1, const uint8_t *d_src2,
+                           uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                           uint8_t *d_dst0, uint8_t *d_dst1, uint8_t *d_dst2,
+                           uint32_t dst_stride, uint32_t dst_c_stride, uint64_t dst_frame_stride, uint64_t dst_c_frame_stride,
+                           uint32_t width, uint32_t height, uint32_t n, void *stream);
+int amvhip_deinterlace(amvhip_ctx *ctx, int fmt, const uint8_t *src0, const uint8_t *src1, const uint8_t *src2,
+                       uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                       uint8_t *dst0, uint8_t *dst1, uint8_t *dst2,
+                       uint32_t dst_stride, uint32_t dst_c_stride, uint64_t dst_frame_stride, uint64_t dst_c_frame_stride,
+                       uint32_t width, uint32_t height, uint32_t n);
+int amvhip_video_frontend_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1, const uint8_t *d_src2,
+                              uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                              uint32_t src_width, uint32_t src_height, uint32_t n, const amvhip_frontend *fe,
+                              uint8_t *d_y, uint8_t *d_cb, uint8_t *d_cr, uint32_t y_stride, uint32_t c_stride,
+                              uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t width, uint32_t height, void *stream);
+int amvhip_encode_frontend_batch_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1, const uint8_t *d_src2,
+                                     uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride,
+                                     uint64_t src_c_frame_stride, uint32_t src_width, uint32_t src_height, uint32_t n,
+                                     const amvhip_frontend *fe, uint32_t width, uint32_t height, uint32_t qbias, uint8_t *d_blob,
+                                     uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens, void *stream);
 /*
  * Decoder + back end in one call: the patched FFmpeg's amv decoder (AMVHIP_FLAG_FFMPEG, required: AMVHIP_ERR_ARG without)
  * into workspace planes, then img_convert YUVJ420P -> dst_fmt (yuvj420p_to_*, imgconvert.c:1977-1993; the planar route for
