@@ -5,6 +5,7 @@
 // the wave has scattered the segment's (block, index, value) records into a zeroed LDS image of the blocks (16-byte
 // granules XOR-swizzled by the record's block field so that the per-lane 128-byte reads do not collide on banks) and
 // added the DC base of the entropy lane that decoded the block (SyncSinks::lane_tab).
+// Around it, the frame the reconstruction kernels share: select_frame, segment_of, next_item, launch_segments.
 #pragma once
 #include <cstdlib>
 
@@ -14,7 +15,6 @@
 namespace amv {
 
 constexpr uint32_t kSegImageBytes = 60u * 128u;   // the LDS image of a segment's <= 60 blocks; 128 spare bytes follow it
-constexpr uint32_t kDummyRecordWord = 0x8000u;   // bit 15: a filler no block owns (amv_decode_sync.hip's kDummyRecord)
 // the scatter's numbers (tests/test_scatter_model.py restates the arithmetic on them)
 constexpr uint32_t kScatterSwizzleMask = 0x38u;     // (word >> 3) & this: the block field's low three bits over the index's granule bits
 constexpr uint32_t kScatterFieldShift = 6u;         // the block field's place in the word
@@ -28,9 +28,6 @@ __device__ __forceinline__ void seg_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// s_img: kSegImageBytes + 128 bytes of LDS, 16-byte aligned; the caller may reuse it after a seg_sync().
-// segidx: this segment's number in the frame (mcu_row * segments_per_row + segment).
-// Returns true when this lane holds a block (lane < cnt * 6).
 // Which frame this workgroup works on: work item `item` of the launch (FrameSel); false when there is none (past
 // the end of a round's work).  slot: where the frame's dense lines live, if it has any.  A default launch has one
 // item per workgroup (blockIdx.x); a round launch is small and its workgroups walk the round's items.
@@ -43,15 +40,36 @@ __device__ __forceinline__ bool select_frame(const FrameSel& sel, uint32_t n, ui
     return true;
 }
 
+// The segment a wave works on: the WAVE's, the same in every lane -- wave-uniform by contract.  The scatter keeps what it
+// derives from it in scalar registers; a caller whose (item, my, seg) come from threadIdx loses nothing but those.
+struct Segment {
+    uint32_t f, slot;                    // the frame; where its dense lines live, if it has any (select_frame)
+    uint32_t m0, cnt, ok, mcu0;          // first MCU column; MCUs (<= kSegMcus); nmcu_ok[f]; first MCU, counted in the frame
+    uint32_t segidx, nsegs;              // the segment's number in the frame (my * nseg + seg); segments per frame
+};
+// segment `seg` (of nseg) of MCU row `my` of the frame select_frame gave
+__device__ __forceinline__ Segment segment_of(uint32_t f, uint32_t slot, const uint32_t* __restrict__ nmcu_ok, const FrameGeom& g,
+                                              uint32_t nseg, uint32_t my, uint32_t seg) {
+    const uint32_t m0 = seg * kSegMcus;
+    return {f, slot, m0, min(kSegMcus, g.mcu_cols - m0), nmcu_ok[f], my * g.mcu_cols + m0, my * nseg + seg, g.mcu_rows * nseg};
+}
+// The item loop of a kernel: `do { select_frame or return; segment_of; ... } while (next_item<kRound>(pm, item));`.  A
+// default launch has one item per workgroup; the workgroups of a round launch walk on, the segment's LDS free again.
+template <bool kRound>
+__device__ __forceinline__ bool next_item(const PieceMap& pm, uint32_t& item) {
+    if (!kRound) return false;
+    seg_sync();
+    item += piece_stride(pm);
+    return true;
+}
+
+// s_img: kSegImageBytes + 128 bytes of LDS, 16-byte aligned; the caller may reuse it after a seg_sync().
+// Returns true when this lane holds a block (lane < cnt * 6).
 // dense_only: a round launch -- the frame's lines are in slot `slot` whatever rec_count says.  A default launch over
 // records leaves frames that went to the serial kernel alone: skip = true (for the whole workgroup), nothing loaded.
-// f, slot, segidx, mcu0, cnt and ok are the WAVE's: the same in every lane (a wave owns one segment).  The scatter keeps
-// what it derives from them in scalar registers; a caller whose values come from threadIdx loses nothing but those.
-__device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, uint32_t f, uint32_t slot, bool dense_only,
-                                                    const FrameGeom& g, uint32_t segidx,
-                                                    uint32_t nsegs, uint32_t mcu0, uint32_t cnt, uint32_t ok, uint32_t lane,
-                                                    uint8_t* s_img, uint32_t (&c)[32], bool& skip) {
-    constexpr uint32_t kWave = 64;
+__device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, const Segment& sg, bool dense_only, const FrameGeom& g,
+                                                    uint32_t lane, uint8_t* s_img, uint32_t (&c)[32], bool& skip) {
+    const uint32_t f = sg.f, slot = sg.slot, segidx = sg.segidx, nsegs = sg.nsegs, mcu0 = sg.mcu0, cnt = sg.cnt, ok = sg.ok;
     const uint32_t nb = cnt * 6u;
     // everything the wave must know before it can ask for its records is requested at once (one round trip to
     // memory, not three in a row): form of the frame, the segment's record range
@@ -86,7 +104,7 @@ __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, uint32_
 #pragma unroll
         for (uint32_t j = 0; j < kAhead; ++j) {
             const uint32_t i = j * 4u * kWave + lane * 4u;
-            q[j] = Rec4{{kDummyRecordWord, kDummyRecordWord, kDummyRecordWord, kDummyRecordWord}};
+            q[j] = Rec4{{kDummyRecord, kDummyRecord, kDummyRecord, kDummyRecord}};
             if (i < nrec) q[j] = *reinterpret_cast<const Rec4*>(rec + i);   // (may read up to 3 words past r1: see ensure())
         }
         uint4* img16 = reinterpret_cast<uint4*>(s_img);
@@ -113,7 +131,7 @@ __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, uint32_
                     const int32_t left = (int32_t)(nrec - base - j * 4u * kWave) - (int32_t)(lane * 4u);   // records from this lane's first on
 #pragma unroll
                     for (uint32_t e = 0; e < 4u; ++e)
-                        if (left <= (int32_t)e) q[j].w[e] = kDummyRecordWord;
+                        if (left <= (int32_t)e) q[j].w[e] = kDummyRecord;
                 }
 #pragma unroll
                 for (uint32_t e = 0; e < 4u; ++e) {
@@ -184,6 +202,16 @@ __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, uint32_
 // int16 number `i` of a block held as 32 dwords
 __device__ __forceinline__ int coef_at(const uint32_t (&c)[32], int i) {
     return (i & 1) ? ((int)c[i >> 1] >> 16) : (int)(int16_t)(c[i >> 1] & 0xffffu);
+}
+
+// The launches of a reconstruction call (amv_piece_map.h: for_each_launch): kernel `part` for a default launch, `walk` for a
+// round (sel.round != 0), row_groups workgroups of `block` threads per item; they take (sinks, nmcu_ok, n, sel, g, pm, tail...).
+template <class Kernel, class... Tail>
+static inline void launch_segments(Kernel part, Kernel walk, uint32_t block, uint32_t row_groups, const SyncSinks& sinks, const uint32_t* nmcu_ok,
+                            uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, hipStream_t s, Tail... tail) {
+    for_each_launch(row_groups, segs_per_row(g), items, sel.round != 0u, [&](const PieceMap& pm, uint32_t grid) {
+        hipLaunchKernelGGL(sel.round ? walk : part, dim3(grid), dim3(block), 0, s, sinks, nmcu_ok, n, sel, g, pm, tail...);
+    });
 }
 
 }  // namespace amv

@@ -18,6 +18,7 @@
 // Compiled with -fwrapv: the integer pipeline relies on two's-complement wrap exactly as the
 // reference's compiler output does.
 #include "amv_kernels.h"
+#include "amv_segment.h"
 
 namespace amv {
 
@@ -26,8 +27,6 @@ namespace amv {
 // ============================================================================================
 
 namespace {
-
-constexpr int kWave = 64;
 
 struct BitReader {
     const uint8_t* base;  // 4-byte aligned address at or before the chunk

@@ -54,18 +54,17 @@
 #include <atomic>
 
 #include "amv_kernels.h"
+#include "amv_segment.h"
 
 namespace amv {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr uint32_t kRingWords = 16;       // LDS words per lane: the window of its stream a lane works in
 // Records are staged per lane in LDS and leave as whole, aligned pieces of eight (a 4-byte store per record from 64
 // lanes into 64 different lines was written back to HBM as partial lines several times over: 9.8 GB of writes per
 // 160 000 frames for 0.7 GB of records, and those stores were what the walk waited on).  A lane's staging column holds
-// two pieces.
-constexpr uint32_t kDummyRecord = 0x8000u;    // bit 15: a filler no block owns
+// two pieces, padded with kDummyRecord.
 constexpr uint32_t kNever = 0xffffffffu;
 
 __device__ __forceinline__ void wave_sync() {
@@ -296,7 +295,6 @@ struct SegGeom {
     uint32_t per_row;     // segments per row
     uint32_t count;       // segments per frame
 };
-constexpr uint32_t kSegMcus = 10;   // = amv_reconstruct.hip's
 
 // stage: this lane's column of the wave's staging area; record slot q of lane l lives at dword q * 64 + l (the
 // bank depends on the lane only, the address is one shift-and-add)
@@ -1294,7 +1292,7 @@ void launch_huffman_sync(const uint32_t* ws, const uint32_t* ws_bytes, uint32_t 
                          const HuffDecodeImage* d_img, const SyncSinks& sinks, int32_t* status, uint32_t* nmcu_ok,
                          uint32_t* queue, unsigned long long* stats, uint32_t cus, hipStream_t s) {
     if (n == 0) return;
-    const uint32_t per_row = (g.mcu_cols + kSegMcus - 1u) / kSegMcus;
+    const uint32_t per_row = segs_per_row(g);
     SyncOut out{sinks.rec, sinks.rec_line, sinks.seg_start, sinks.lane_tab, SegGeom{g.mcu_cols, per_row, per_row * g.mcu_rows},
                 sinks.lanes, sinks.rec_count, sinks.retry_list, sinks.retry_count, sinks.ok_in_blocks};
 #define AMV_SYNC_ARGS ws, ws_bytes, n, list, list_count, g, ws_line, d_img, out, status, nmcu_ok, queue, stats, cus, s

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kWave) void amv_forward_kernel(Source in, uint32_t 
 static void launch_forward_any(const Source& in, bool yuv, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g,
                                uint32_t qbias, int16_t* coef, hipStream_t s) {
     if (items == 0) return;
-    const uint32_t nseg = (g.mcu_cols + kSegMcus - 1) / kSegMcus;
+    const uint32_t nseg = segs_per_row(g);
     const uint32_t per_seg = (g.mcu_cols + nseg - 1) / nseg;      // balanced: 11 columns -> 6 + 5
     const uint64_t grid = (uint64_t)(sel.round && items > 64u ? 64u : items) * g.mcu_rows * nseg;
     if (yuv)

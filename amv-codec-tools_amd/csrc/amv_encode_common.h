@@ -10,12 +10,10 @@
 // fixed tables (AmvJpeg.c:30-61) and a true -128 level shift so that amvlib and the patched FFmpeg both decode it.
 #pragma once
 #include "amv_kernels.h"
+#include "amv_segment.h"
 
 namespace amv {
 namespace enc {
-
-constexpr int kWave = 64;
-constexpr int kSegMcus = 10;
 
 __device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 

@@ -407,7 +407,7 @@ void launch_encode_frames(const uint8_t* pix, uint32_t pix_stride, int is_bgr, c
                           uint32_t qbias, const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens,
                           uint32_t* retry_list, uint32_t* retry_count, hipStream_t s) {
     if (n == 0) return;
-    const uint32_t nseg = (g.mcu_cols + kSegMcus - 1) / kSegMcus;
+    const uint32_t nseg = segs_per_row(g);
     const uint32_t per_seg = (g.mcu_cols + nseg - 1) / nseg;      // balanced: 11 columns -> 6 + 5
     if (yuv)
         hipLaunchKernelGGL(amv_encode_frame_kernel<true>, dim3(n), dim3(kLanes), 0, s, Source{nullptr, 0u, 0, *yuv}, n, g, nseg, per_seg,

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/amvhip.h"
+#include "amv_segment.h"
 #include "amv_tables.h"
 
 namespace amv {
@@ -111,7 +112,7 @@ inline EntropyPlan entropy_plan(uint32_t n, uint64_t blob_bytes, const FrameGeom
     const uint64_t by_stream = (2u * blob_bytes + (uint64_t)n * (p.add_rec + 31u)) / 32u + 1u;
     if (by_stream < p.cap_lines) p.cap_lines = by_stream;
     if (p.cap_lines > 0xffffffffull) p.cap_lines = 0xffffffffull;
-    p.segs = ((g.mcu_cols + 9u) / 10u) * g.mcu_rows;
+    p.segs = segs_per_row(g) * g.mcu_rows;
     return p;
 }
 

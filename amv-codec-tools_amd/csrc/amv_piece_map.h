@@ -4,11 +4,7 @@
 #include <cstdint>
 #include <cstdlib>
 
-#if defined(__HIPCC__)
-#define AMV_HD __host__ __device__
-#else
-#define AMV_HD
-#endif
+#include "amv_segment.h"
 
 namespace amv {
 
@@ -62,6 +58,24 @@ inline uint32_t most_items(const PieceMap& pm) {
         if (v > 0 && (unsigned long)v < most) return (uint32_t)v;
     }
     return most;
+}
+
+// The launches of one reconstruction call: launch(pm, grid) for each.  A round is one launch of min(items, kRoundWalkers)
+// walkers (they go on to item0 + piece_stride, ...); a default launch goes in parts of <= `most` items (0: most_items).
+template <class Launch>
+static inline void for_each_launch(uint32_t row_groups, uint32_t nseg, uint32_t items, bool round, Launch launch, uint32_t most = 0u) {
+    PieceMap pm = make_piece_map(row_groups, nseg);
+    if (round) {
+        const uint32_t grid = set_walkers(pm, items < kRoundWalkers ? items : kRoundWalkers);
+        if (items) launch(pm, grid);
+        return;
+    }
+    if (!most) most = most_items(pm);
+    for (uint32_t base = 0; base < items; base += most) {
+        pm.item_base = base;
+        const uint32_t grid = set_walkers(pm, items - base < most ? items - base : most);
+        launch(pm, grid);
+    }
 }
 
 }  // namespace amv

@@ -1,7 +1,8 @@
 // amv_reconstruct.hip -- everything after the entropy stage: dequantise, inverse DCT, YCbCr->BGR,
 // bottom-up store (IQtIZzBlock / Fast_IDCT / GetYUV / StoreBuffer, AmvJpeg.c:1010-1059, 754-840).
 //
-// One wave per MCU-row segment (<= 10 MCUs = 60 blocks = 160 pixels of 16 rows):
+// One wave per MCU-row segment (<= 10 MCUs = 60 blocks = 160 pixels of 16 rows); which segment, the walk over a round's
+// items and the launches are the frame amv_block_load.h gives all three back halves:
 //   A. lane b loads block b's 64 coefficients into registers: from its dense 128-byte line, or --
 //      records form -- after the wave has scattered the segment's (block, index, value) records and
 //      DC values into a zeroed LDS image of the 60 blocks (16-byte granules XOR-swizzled by block so
@@ -27,8 +28,6 @@ namespace {
 
 struct __attribute__((aligned(4))) Px12 { uint32_t w[3]; };   // four BGR pixels
 
-constexpr int kWave = 64;
-constexpr int kSegMcus = 10;   // MCUs per wave: 60 of 64 lanes busy in the transform
 // Waves per workgroup: four consecutive MCU rows of a frame.  The waves share nothing (a segment's LDS is its wave's);
 // the workgroup only exists so that the chip launches a quarter as many of them -- 1.28 M single-wave workgroups per
 // 160 000 frames of 160x120 cost 8 % of the kernel's time in launches (profiles/r02_launch_rate.txt).
@@ -152,9 +151,8 @@ __global__ __launch_bounds__(kWave * kRows) void amv_reconstruct_kernel(
     static_assert((16 * kPitchY + 2 * 8 * kPitchC) * 2 == kSegImageBytes, "the planes reuse the image");
     // (the wave's number as a scalar: what follows from it -- its MCU row, its LDS, the scatter's constants -- stays out of the vector registers)
     const uint32_t lane = threadIdx.x & 63u, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t nseg = pm.nseg;
-    uint32_t item0, row_group, seg;
-    if (!locate_piece(pm, blockIdx.x, item0, row_group, seg)) return;
+    uint32_t item, row_group, seg;
+    if (!locate_piece(pm, blockIdx.x, item, row_group, seg)) return;
     const uint32_t my = row_group * kRows + wave;
     if (my >= g.mcu_rows) return;                   // (the whole wave)
     int16_t* const s_mem = s_all[wave];
@@ -172,19 +170,16 @@ __global__ __launch_bounds__(kWave * kRows) void amv_reconstruct_kernel(
             qw[4 * i] = q.x; qw[4 * i + 1] = q.y; qw[4 * i + 2] = q.z; qw[4 * i + 3] = q.w;
         }
     }
-    for (uint32_t item = item0;; item += piece_stride(pm)) {
+    do {
     uint32_t f, slot;
     if (!select_frame(sel, n, item, f, slot)) return;
-    const uint32_t m0 = seg * kSegMcus;
-    const uint32_t cnt = min((uint32_t)kSegMcus, g.mcu_cols - m0);
-
-    const uint32_t ok = nmcu_ok[f];
-    const uint32_t mcu0 = my * g.mcu_cols + m0;                       // first MCU of this segment
+    const Segment sg = segment_of(f, slot, nmcu_ok, g, pm.nseg, my, seg);
+    const uint32_t m0 = sg.m0, cnt = sg.cnt, ok = sg.ok, mcu0 = sg.mcu0;
 
     // ---- A + B + C: one block per lane
     uint32_t c[32];
     bool skip;
-    if (load_segment_blocks(in, f, slot, kRound, g, my * nseg + seg, g.mcu_rows * nseg, mcu0, cnt, ok, lane, s_img, c, skip)) {
+    if (load_segment_blocks(in, sg, kRound, g, lane, s_img, c, skip)) {
         const uint32_t m = lane / 6u, k6 = lane % 6u;
         const bool chroma = k6 >= 4u;
         // IQtIZzBlock's gather (AmvJpeg.c:1035-1042): out[nat] = coef[scan(nat)] * step[scan(nat)]
@@ -293,41 +288,24 @@ __global__ __launch_bounds__(kWave * kRows) void amv_reconstruct_kernel(
             off -= g.stride;
         }
     }
-    if (!kRound) return;
-    seg_sync();   // the planes are free again
-    }   // next item of the round
+    } while (next_item<kRound>(pm, item));   // (the planes are free again)
 }
 
-template <int kRows>
-static void launch_rows(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g,
-                        uint32_t flags, uint8_t* out, hipStream_t s) {
-    const uint32_t nseg = (g.mcu_cols + kSegMcus - 1) / kSegMcus;
-    const uint32_t row_groups = (g.mcu_rows + kRows - 1) / kRows;
-    PieceMap pm = make_piece_map(row_groups, nseg);
-    if (sel.round) {   // a round launch is small: its workgroups walk
-        const uint32_t grid = set_walkers(pm, items > 512u ? 512u : items);
-        hipLaunchKernelGGL((amv_reconstruct_kernel<true, kRows>), dim3(grid), dim3(kWave * kRows), 0, s, sinks, nmcu_ok, n, sel, g, pm, flags, out);
-        return;
-    }
-    const uint32_t most = most_items(pm);
-    for (uint32_t base = 0; base < items; base += most) {
-        pm.item_base = base;
-        const uint32_t grid = set_walkers(pm, items - base < most ? items - base : most);
-        hipLaunchKernelGGL((amv_reconstruct_kernel<false, kRows>), dim3(grid), dim3(kWave * kRows), 0, s, sinks, nmcu_ok, n, sel, g, pm, flags, out);
-    }
+template <int kRows, class... Args>
+static void launch_rows(const FrameGeom& g, Args... args) {
+    launch_segments(amv_reconstruct_kernel<false, kRows>, amv_reconstruct_kernel<true, kRows>, kWave * kRows, (g.mcu_rows + kRows - 1) / kRows, args...);
 }
 
 void launch_reconstruct(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameSel& sel, uint32_t items,
                         const FrameGeom& g, uint32_t flags, uint8_t* out, hipStream_t s) {
-    if (items == 0) return;
     // A workgroup's waves are consecutive MCU rows of one frame, and the last workgroup of a frame has idle slots unless
     // the rows divide.  Fives only where fours waste a tenth of the slots more than fives do (176x144, 9 rows: 4.80 ms
     // per 100 000 frames against 5.04): five waves do not spread evenly over a CU's four SIMDs, and 320x240 (15 rows,
     // one slot in sixteen idle in fours) takes 6.29 ms per 64 000 frames in fives against 5.87 in fours.
     const uint32_t slots4 = (g.mcu_rows + 3u) / 4u * 4u, slots5 = (g.mcu_rows + 4u) / 5u * 5u;
     const uint32_t waste4 = slots4 - g.mcu_rows, waste5 = slots5 - g.mcu_rows;
-    if (10u * waste4 * slots5 >= 10u * waste5 * slots4 + slots4 * slots5) launch_rows<5>(sinks, nmcu_ok, n, sel, items, g, flags, out, s);
-    else launch_rows<kRowsPerGroup>(sinks, nmcu_ok, n, sel, items, g, flags, out, s);
+    if (10u * waste4 * slots5 >= 10u * waste5 * slots4 + slots4 * slots5) launch_rows<5>(g, sinks, nmcu_ok, n, sel, items, g, s, flags, out);
+    else launch_rows<kRowsPerGroup>(g, sinks, nmcu_ok, n, sel, items, g, s, flags, out);
 }
 
 // Records -> dense lines (amvhip_huffman_decode_dev, not on the decode path): stage A of the kernel above for one
@@ -341,15 +319,12 @@ __global__ __launch_bounds__(kWave * 4) void amv_expand_records_kernel(SyncSinks
     const uint64_t pairs = (uint64_t)n * segs;
     for (uint64_t p = (uint64_t)blockIdx.x * 4u + wave; p < pairs; p += (uint64_t)gridDim.x * 4u) {
         const uint32_t f = (uint32_t)(p / segs), segidx = (uint32_t)(p % segs);
-        const uint32_t m0 = (segidx % nseg) * kSegMcus;
-        const uint32_t cnt = min((uint32_t)kSegMcus, g.mcu_cols - m0);
-        const uint32_t mcu0 = (segidx / nseg) * g.mcu_cols + m0;
-        const uint32_t ok = nmcu_ok[f];
+        const Segment sg = segment_of(f, f, nmcu_ok, g, nseg, segidx / nseg, segidx % nseg);
         uint32_t c[32];
         bool skip;   // (a frame the serial kernel decodes: its lines are that kernel's)
-        if (load_segment_blocks(in, f, f, false, g, segidx, segs, mcu0, cnt, ok, lane, s_img[wave], c, skip)) {
-            const uint32_t blk = mcu0 * 6u + lane;
-            if (blk >= (in.ok_in_blocks ? ok : ok * 6u)) {   // at or after the first error: no records, but the DC base was added
+        if (load_segment_blocks(in, sg, false, g, lane, s_img[wave], c, skip)) {
+            const uint32_t blk = sg.mcu0 * 6u + lane;
+            if (blk >= (in.ok_in_blocks ? sg.ok : sg.ok * 6u)) {   // at or after the first error: no records, but the DC base was added
 #pragma unroll
                 for (int i = 0; i < 32; ++i) c[i] = 0u;
             }
@@ -363,7 +338,7 @@ __global__ __launch_bounds__(kWave * 4) void amv_expand_records_kernel(SyncSinks
 
 void launch_expand_records(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameGeom& g, int16_t* coef,
                            hipStream_t s) {
-    const uint32_t nseg = (g.mcu_cols + kSegMcus - 1) / kSegMcus;
+    const uint32_t nseg = segs_per_row(g);
     const uint64_t groups = ((uint64_t)n * g.mcu_rows * nseg + 3u) / 4u;
     if (groups == 0) return;
     hipLaunchKernelGGL(amv_expand_records_kernel, dim3(groups < 65536u ? (uint32_t)groups : 65536u), dim3(kWave * 4), 0, s, sinks,

@@ -4,21 +4,16 @@
 // (dsputil.c:50-59), simple_idct_put (simple_idct.c:78-181,183-247,390-398) and the planar YUVJ420P store with
 // the AMV flip (mjpegdec.c:672-677,708-716).  No colour conversion: FFmpeg hands out the three planes.
 //
-// Same work split as amv_reconstruct_kernel: one wave per MCU-row segment (<= 10 MCUs), one 8x8 block per lane
-// held in registers through both passes; a lane then owns 8 rows of 8 output bytes and stores them itself.
+// The work split is the shared frame of amv_block_load.h: one wave per MCU-row segment (<= 10 MCUs), one 8x8 block per
+// lane, held in registers through both passes; a lane then owns 8 rows of 8 output bytes and stores them itself.
 // DCTELEM is int16 in the reference: every value that it stores into a block (dequantised coefficients, row-pass
 // results) is wrapped to 16 bits here too, and the DC-only shortcut of idctRowCondDC -- which is NOT the general
 // row formula (8*dc against (16383*dc + 1024) >> 11) -- is taken per row by a select.
-#include "amv_block_load.h"
+#include "amv_ff_dequant.h"
 
 namespace amv {
 
 namespace {
-
-constexpr int kWave = 64;
-constexpr int kSegMcus = 10;
-
-__device__ __forceinline__ int s16(int x) { return (int)(int16_t)x; }
 
 // idctRowCondDC, simple_idct.c:78-181
 __device__ __forceinline__ void sidct_row(int& r0, int& r1, int& r2, int& r3, int& r4, int& r5, int& r6, int& r7) {
@@ -41,7 +36,7 @@ __device__ __forceinline__ void sidct_row(int& r0, int& r1, int& r2, int& r3, in
 }
 
 // idctSparseColPut, simple_idct.c:183-247 (its `if (col[..])` guards only skip additions of zero); the clip is
-// ff_cropTbl (0..255 over -1024..1279; saturation beyond, where the reference reads outside its table)
+// ff_cropTbl (0..255 over -1024..1279)
 __device__ __forceinline__ void sidct_col(int& c0, int& c1, int& c2, int& c3, int& c4, int& c5, int& c6, int& c7) {
     constexpr int W1 = 22725, W2 = 21407, W3 = 19266, W4 = 16383, W5 = 12873, W6 = 8867, W7 = 4520;
     int a0 = W4 * (c0 + 32), a1 = a0, a2 = a0, a3 = a0;              // (1 << 19) / W4 = 32
@@ -51,15 +46,8 @@ __device__ __forceinline__ void sidct_col(int& c0, int& c1, int& c2, int& c3, in
     b0 += W5 * c5; b1 -= W1 * c5; b2 += W7 * c5; b3 += W3 * c5;
     a0 += W6 * c6; a1 -= W2 * c6; a2 += W2 * c6; a3 -= W6 * c6;
     b0 += W7 * c7; b1 -= W5 * c7; b2 += W3 * c7; b3 -= W1 * c7;
-    // (written as an explicit v_med3: hipcc 7.2 folds pairs of `clamp(x >> 20, 0, 255)` into gfx950's
-    // v_ashr_pk_u8_i32, whose results differed from the plain arithmetic on MI355X in the parity tests)
-    auto clip = [](int x) {
-        int d;
-        asm("v_med3_i32 %0, %1, 0, %2" : "=v"(d) : "v"(x >> 20), "s"(255));
-        return d;
-    };
-    c0 = clip(a0 + b0); c1 = clip(a1 + b1); c2 = clip(a2 + b2); c3 = clip(a3 + b3);
-    c4 = clip(a3 - b3); c5 = clip(a2 - b2); c6 = clip(a1 - b1); c7 = clip(a0 - b0);
+    c0 = crop((a0 + b0) >> 20); c1 = crop((a1 + b1) >> 20); c2 = crop((a2 + b2) >> 20); c3 = crop((a3 + b3) >> 20);
+    c4 = crop((a3 - b3) >> 20); c5 = crop((a2 - b2) >> 20); c6 = crop((a1 - b1) >> 20); c7 = crop((a0 - b0) >> 20);
 }
 
 }  // namespace
@@ -72,30 +60,22 @@ __global__ __launch_bounds__(kWave) void amv_reconstruct_yuv_kernel(
     uint8_t* __restrict__ out) {
     __shared__ __attribute__((aligned(16))) uint8_t s_img[kSegImageBytes + 128];   // + a spare slot per lane (load_segment_blocks)
     const uint32_t lane = threadIdx.x;
-    uint32_t item0, my, seg;   // (one MCU row per workgroup: the row group is the row)
-    if (!locate_piece(pm, blockIdx.x, item0, my, seg)) return;
-    for (uint32_t item = item0;; item += piece_stride(pm)) {
+    uint32_t item, my, seg;   // (one MCU row per workgroup: the row group is the row)
+    if (!locate_piece(pm, blockIdx.x, item, my, seg)) return;
+    do {
     uint32_t f, slot;
     if (!select_frame(sel, n, item, f, slot)) return;
-    const uint32_t m0 = seg * kSegMcus;
-    const uint32_t cnt = min((uint32_t)kSegMcus, g.mcu_cols - m0);
-    const uint32_t ok = nmcu_ok[f];
-    const uint32_t mcu0 = my * g.mcu_cols + m0;
+    const Segment sg = segment_of(f, slot, nmcu_ok, g, pm.nseg, my, seg);
+    const uint32_t m0 = sg.m0;
 
     uint32_t c[32];
     bool skip;
-    if (load_segment_blocks(in, f, slot, kRound, g, my * pm.nseg + seg, g.mcu_rows * pm.nseg, mcu0, cnt, ok, lane, s_img, c, skip)) {
-    const uint32_t m = lane / 6u, k6 = lane % 6u;
-    const bool chroma = k6 >= 4u;
-    // decoded: MCUs before the frame's first error -- or, AMVHIP_FLAG_FFMPEG_KEEP (ok counts blocks then), every whole block
-    // before it: what mjpeg_decode_scan has put into the picture when decode_block fails (mjpegdec.c:699-716)
+    if (load_segment_blocks(in, sg, kRound, g, lane, s_img, c, skip)) {
+    const FfBlock b = ff_block(in, sg, lane);
+    const uint32_t m = b.m, k6 = b.k6;
+    const bool chroma = b.chroma, decoded = b.decoded;
     const bool keep = in.ok_in_blocks != 0u;
-    const bool decoded = keep ? (mcu0 + m) * 6u + k6 < ok : mcu0 + m < ok;
-
-    // decode_block's dequantisation (mjpegdec.c:388-390,417,424): out[natural] = (DCTELEM)(level * q); the DC
-    // arrives as the running sum of differences, FFmpeg keeps 1024 + q0 * that sum (:805) -- equal modulo 2^16,
-    // which is all an int16 store keeps
-    int v[64];
+    int v[64];   // q60_dequantise<8> written out: as the function it costs the round kernel a vector register (181, not 180)
 #pragma unroll
     for (int nat = 0; nat < 64; ++nat) {
         const int scan = kScanOfNatural[nat];
@@ -141,9 +121,7 @@ __global__ __launch_bounds__(kWave) void amv_reconstruct_yuv_kernel(
     }
     }
     }
-    if (!kRound) return;
-    seg_sync();   // the image is free again
-    }   // next item of the round
+    } while (next_item<kRound>(pm, item));   // (the image is free again)
 }
 
 // true when every row of every plane is reached by mjpegdec.c:672-677's formula (then the kernel writes each
@@ -156,20 +134,8 @@ bool yuv_store_covers_planes(const FrameGeom& g) {
 
 void launch_reconstruct_yuv(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameSel& sel, uint32_t items,
                             const FrameGeom& g, uint64_t yuv_frame_bytes, uint8_t* out, hipStream_t s) {
-    if (items == 0) return;
-    const uint32_t nseg = (g.mcu_cols + kSegMcus - 1) / kSegMcus;
-    PieceMap pm = make_piece_map(g.mcu_rows, nseg);   // (the launch order of amv_reconstruct_kernel: amv_block_load.h)
-    if (sel.round) {
-        const uint32_t grid = set_walkers(pm, items > 512u ? 512u : items);
-        hipLaunchKernelGGL(amv_reconstruct_yuv_kernel<true>, dim3(grid), dim3(kWave), 0, s, sinks, nmcu_ok, n, sel, g, pm, yuv_frame_bytes, out);
-        return;
-    }
-    const uint32_t most = most_items(pm);
-    for (uint32_t base = 0; base < items; base += most) {
-        pm.item_base = base;
-        const uint32_t grid = set_walkers(pm, items - base < most ? items - base : most);
-        hipLaunchKernelGGL(amv_reconstruct_yuv_kernel<false>, dim3(grid), dim3(kWave), 0, s, sinks, nmcu_ok, n, sel, g, pm, yuv_frame_bytes, out);
-    }
+    launch_segments(amv_reconstruct_yuv_kernel<false>, amv_reconstruct_yuv_kernel<true>, kWave, g.mcu_rows, sinks, nmcu_ok, n, sel, items, g, s,
+                    yuv_frame_bytes, out);
 }
 
 }  // namespace amv

@@ -9,28 +9,15 @@
 // serve: its AMV flip takes the start row from the full-size 8 * mb_height without a shift (mjpegdec.c:675), and
 // ffmpeg.c:2699 sets CODEC_FLAG_EMU_EDGE with lowres, which the flip asserts against (mjpegdec.c:674).
 //
-// Same work split as amv_reconstruct_yuv_kernel: one wave per MCU-row segment (<= 10 MCUs), one block per lane.  A
+// The work split is the shared frame of amv_block_load.h: one wave per MCU-row segment (<= 10 MCUs), one block per lane.  A
 // lane's block is 4, 2 or 1 bytes wide, so the segment's reduced rows are staged in LDS (the blocks' image is free once
 // the blocks are in registers) and the lanes then write the rows' pieces, a dword where the destination holds one.
-#include "amv_block_load.h"
+#include "amv_ff_dequant.h"
 #include "amv_host_plan.h"
 
 namespace amv {
 
 namespace {
-
-constexpr int kWave = 64;
-constexpr int kSegMcus = 10;
-
-__device__ __forceinline__ int s16(int x) { return (int)(int16_t)x; }
-
-// ff_cropTbl: 0..255 (saturation beyond the table too, as amv_reconstruct_ff.hip has it; written as v_med3 for the
-// reason given there)
-__device__ __forceinline__ int crop(int x) {
-    int d;
-    asm("v_med3_i32 %0, %1, 0, %2" : "=v"(d) : "v"(x), "s"(255));
-    return d;
-}
 
 // the even part of j_rev_dct4, rows (jrevdct.c:1003-1048) and columns (:1081-1126) alike.  Its four branches are not
 // one formula: with d2 == 0 the reference multiplies -d6 by FIX_1_306562965 = 10703, where the general branch gives
@@ -121,35 +108,25 @@ __global__ __launch_bounds__(kWave) void amv_reconstruct_yuv_lowres_kernel(
     static_assert(S::bytes <= kSegImageBytes, "the staged rows fit the blocks' image");
     __shared__ __attribute__((aligned(16))) uint8_t s_img[kSegImageBytes + 128];   // + a spare slot per lane (load_segment_blocks)
     const uint32_t lane = threadIdx.x;
-    uint32_t item0, my, seg;
-    if (!locate_piece(pm, blockIdx.x, item0, my, seg)) return;
-    for (uint32_t item = item0;; item += piece_stride(pm)) {
+    uint32_t item, my, seg;
+    if (!locate_piece(pm, blockIdx.x, item, my, seg)) return;
+    do {
     uint32_t f, slot;
     if (!select_frame(sel, n, item, f, slot)) return;
-    const uint32_t m0 = seg * kSegMcus;
-    const uint32_t cnt = min((uint32_t)kSegMcus, g.mcu_cols - m0);
-    const uint32_t ok = nmcu_ok[f];
-    const uint32_t mcu0 = my * g.mcu_cols + m0;
+    const Segment sg = segment_of(f, slot, nmcu_ok, g, pm.nseg, my, seg);
+    const uint32_t m0 = sg.m0, cnt = sg.cnt;
 
     uint32_t c[32];
     bool skip;
-    const bool has = load_segment_blocks(in, f, slot, kRound, g, my * pm.nseg + seg, g.mcu_rows * pm.nseg, mcu0, cnt, ok, lane, s_img, c, skip);
+    const bool has = load_segment_blocks(in, sg, kRound, g, lane, s_img, c, skip);
     if (!skip) {   // (the same in every lane)
     seg_sync();    // every lane has its block: the image becomes the staged rows
     if (has) {
-        const uint32_t m = lane / 6u, k6 = lane % 6u;
-        const bool chroma = k6 >= 4u;
-        const bool decoded = mcu0 + m < ok;      // MCUs at or after a frame's first error stay zero
+        const FfBlock b = ff_block(in, sg, lane);
+        const uint32_t m = b.m, k6 = b.k6;
+        const bool chroma = b.chroma, decoded = b.decoded;   // blocks at or after a frame's first error stay zero
         int v[bs * bs];
-#pragma unroll
-        for (uint32_t r = 0; r < bs; ++r)
-#pragma unroll
-            for (uint32_t col = 0; col < bs; ++col) {
-                const int nat = (int)(8u * r + col);
-                const int scan = kScanOfNatural[nat];
-                const int step = chroma ? (int)kQ60Chroma[scan] : (int)kQ60Luma[scan];
-                v[bs * r + col] = s16(coef_at(c, scan) * step + (nat == 0 ? 1024 : 0));   // decode_block, mjpegdec.c:388-390,417,424,805
-            }
+        q60_dequantise<(8 >> L)>(c, chroma, v);
         reduced_idct<L>(v);
         const uint32_t row0 = chroma ? (k6 - 4u) * bs : (k6 >> 1) * bs;
         const uint32_t col0 = (chroma ? m : 2u * m + (k6 & 1u)) * bs;
@@ -201,32 +178,17 @@ __global__ __launch_bounds__(kWave) void amv_reconstruct_yuv_lowres_kernel(
         }
     }
     }
-    if (!kRound) return;
-    seg_sync();   // the image is free again
-    }   // next item of the round
+    } while (next_item<kRound>(pm, item));   // (the image is free again)
 }
 
-template <int L>
-static void launch_lowres(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g,
-                          const LowresGeom& lg, uint8_t* out, hipStream_t s) {
-    const uint32_t nseg = (g.mcu_cols + kSegMcus - 1) / kSegMcus;
-    PieceMap pm = make_piece_map(g.mcu_rows, nseg);   // (the launch order of amv_reconstruct_kernel: amv_block_load.h)
-    if (sel.round) {
-        const uint32_t grid = set_walkers(pm, items > 512u ? 512u : items);
-        hipLaunchKernelGGL((amv_reconstruct_yuv_lowres_kernel<L, true>), dim3(grid), dim3(kWave), 0, s, sinks, nmcu_ok, n, sel, g, pm, lg, out);
-        return;
-    }
-    const uint32_t most = most_items(pm);
-    for (uint32_t base = 0; base < items; base += most) {
-        pm.item_base = base;
-        const uint32_t grid = set_walkers(pm, items - base < most ? items - base : most);
-        hipLaunchKernelGGL((amv_reconstruct_yuv_lowres_kernel<L, false>), dim3(grid), dim3(kWave), 0, s, sinks, nmcu_ok, n, sel, g, pm, lg, out);
-    }
+template <int L, class... Args>
+static void launch_lowres(const FrameGeom& g, Args... args) {
+    launch_segments(amv_reconstruct_yuv_lowres_kernel<L, false>, amv_reconstruct_yuv_lowres_kernel<L, true>, kWave, g.mcu_rows, args...);
 }
 
 void launch_reconstruct_yuv_lowres(const SyncSinks& sinks, const uint32_t* nmcu_ok, uint32_t n, const FrameSel& sel, uint32_t items,
                                    const FrameGeom& g, uint32_t lowres, uint8_t* out, hipStream_t s) {
-    if (items == 0 || lowres < 1u || lowres > 3u) return;
+    if (lowres < 1u || lowres > 3u) return;
     LowresGeom lg;
     lg.w = lowres_dim(g.width, lowres);
     lg.h = lowres_dim(g.height, lowres);
@@ -235,9 +197,9 @@ void launch_reconstruct_yuv_lowres(const SyncSinks& sinks, const uint32_t* nmcu_
     lg.start_y = lowres_start_row(g.height, lowres, false);
     lg.start_c = lowres_start_row(g.height, lowres, true);
     lg.frame_bytes = lowres_frame_bytes(g.width, g.height, lowres);
-    if (lowres == 1u) launch_lowres<1>(sinks, nmcu_ok, n, sel, items, g, lg, out, s);
-    else if (lowres == 2u) launch_lowres<2>(sinks, nmcu_ok, n, sel, items, g, lg, out, s);
-    else launch_lowres<3>(sinks, nmcu_ok, n, sel, items, g, lg, out, s);
+    if (lowres == 1u) launch_lowres<1>(g, sinks, nmcu_ok, n, sel, items, g, s, lg, out);
+    else if (lowres == 2u) launch_lowres<2>(g, sinks, nmcu_ok, n, sel, items, g, s, lg, out);
+    else launch_lowres<3>(g, sinks, nmcu_ok, n, sel, items, g, s, lg, out);
 }
 
 }  // namespace amv

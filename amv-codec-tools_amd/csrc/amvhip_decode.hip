@@ -74,46 +74,57 @@ static int entropy_front(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_byt
     return check_launch(c, "huffman_sync");
 }
 
+// Which back half a call's (flags, lowres) ask for, and what follows from that for its output: decided once per call.
+struct BackHalf {
+    enum Kind { kBgr, kYuv, kYuvLowres } kind;   // amvlib's BGR; the patched FFmpeg's YUVJ420P planes; ... at 1/2, 1/4, 1/8 size
+    uint32_t flags, lowres;
+    uint64_t frame_bytes;                        // of the output
+    bool covered;   // false: bytes no kernel writes (row padding, AMVDec.c:283; plane rows mjpegdec.c:672-677 skips) are cleared first
+};
+static BackHalf back_half(uint32_t flags, uint32_t lowres, const FrameGeom& g) {
+    const bool keep = (flags & AMVHIP_FLAG_FFMPEG_KEEP) != 0;
+    if (lowres)
+        return {BackHalf::kYuvLowres, flags, lowres, lowres_frame_bytes(g.width, g.height, lowres), keep || lowres_store_covers_planes(g.height, lowres)};
+    if (flags & AMVHIP_FLAG_FFMPEG)
+        return {BackHalf::kYuv, flags, 0u, amvhip_yuv420_frame_bytes(g.width, g.height), keep || yuv_store_covers_planes(g)};
+    return {BackHalf::kBgr, flags, 0u, g.frame_bytes, keep || g.stride == g.width * 3};
+}
+
 static int reconstruct_launch(amvhip_ctx* c, const SyncSinks& sinks, const uint32_t* d_nmcu_ok, uint32_t n, const FrameSel& sel,
-                              uint32_t items, const FrameGeom& g, uint32_t flags, uint8_t* d_out, hipStream_t st, uint32_t lowres = 0) {
+                              uint32_t items, const FrameGeom& g, const BackHalf& bh, uint8_t* d_out, hipStream_t st) {
     Timed t(c, AMVHIP_K_RECON, st);
-    if (lowres)   // ... at 1/2, 1/4, 1/8 size
-        launch_reconstruct_yuv_lowres(sinks, d_nmcu_ok, n, sel, items, g, lowres, d_out, st);
-    else if (flags & AMVHIP_FLAG_FFMPEG)   // the patched FFmpeg's amv_decoder: YUVJ420P planes
-        launch_reconstruct_yuv(sinks, d_nmcu_ok, n, sel, items, g, amvhip_yuv420_frame_bytes(g.width, g.height), d_out, st);
-    else
-        launch_reconstruct(sinks, d_nmcu_ok, n, sel, items, g, flags, d_out, st);
+    switch (bh.kind) {
+        case BackHalf::kYuvLowres: launch_reconstruct_yuv_lowres(sinks, d_nmcu_ok, n, sel, items, g, bh.lowres, d_out, st); break;
+        case BackHalf::kYuv: launch_reconstruct_yuv(sinks, d_nmcu_ok, n, sel, items, g, bh.frame_bytes, d_out, st); break;
+        case BackHalf::kBgr: launch_reconstruct(sinks, d_nmcu_ok, n, sel, items, g, bh.flags, d_out, st); break;
+    }
     return check_launch(c, "reconstruct");
 }
 
-// bytes of the output no kernel writes are cleared first: row padding (AMVDec.c:283), and in FFmpeg mode the plane
-// rows mjpegdec.c:672-677 leaves untouched for some heights
-static int clear_unwritten(amvhip_ctx* c, uint32_t n, const FrameGeom& g, uint32_t flags, uint8_t* d_out, hipStream_t st, uint32_t lowres = 0) {
-    if (flags & AMVHIP_FLAG_FFMPEG_KEEP) return AMVHIP_OK;   // what no block covers stays as the caller had it
-    if (lowres) {
-        if (!lowres_store_covers_planes(g.height, lowres)) HIP_TRY(c, hipMemsetAsync(d_out, 0, lowres_frame_bytes(g.width, g.height, lowres) * n, st));
-        return AMVHIP_OK;
-    }
-    if (flags & AMVHIP_FLAG_FFMPEG) {
-        if (!yuv_store_covers_planes(g)) HIP_TRY(c, hipMemsetAsync(d_out, 0, amvhip_yuv420_frame_bytes(g.width, g.height) * n, st));
-    } else if (g.stride != g.width * 3) {
-        HIP_TRY(c, hipMemsetAsync(d_out, 0, g.frame_bytes * n, st));
-    }
+static int clear_unwritten(amvhip_ctx* c, uint32_t n, const BackHalf& bh, uint8_t* d_out, hipStream_t st) {
+    if (!bh.covered) HIP_TRY(c, hipMemsetAsync(d_out, 0, bh.frame_bytes * n, st));
     return AMVHIP_OK;
+}
+
+// amvhip_reconstruct_dev and amvhip_reconstruct_lowres_dev (`who`) behind their own argument checks
+static int reconstruct_dense(amvhip_ctx* c, const char* who, const int16_t* d_coef, const uint32_t* d_nmcu_ok, uint32_t n, uint32_t w,
+                             uint32_t h, uint32_t flags, uint32_t lowres, uint8_t* d_out, void* stream) {
+    if (!size_ok(w, h) || (n && (!d_coef || !d_nmcu_ok || !d_out))) return fail(c, AMVHIP_ERR_ARG, "%s: bad argument", who);
+    if (((uintptr_t)d_out & 3u) || ((uintptr_t)d_coef & 15u)) return fail(c, AMVHIP_ERR_ARG, "%s: out must be 4-byte, coef 16-byte aligned", who);
+    if (int r = use_device(c)) return r;
+    if (n == 0) return AMVHIP_OK;
+    const FrameGeom g = make_geom(w, h);
+    const BackHalf bh = back_half(flags, lowres, g);
+    SyncSinks sinks{};
+    sinks.coef = const_cast<int16_t*>(d_coef);
+    if (int r = clear_unwritten(c, n, bh, d_out, (hipStream_t)stream)) return r;
+    return reconstruct_launch(c, sinks, d_nmcu_ok, n, kAllFrames, n, g, bh, d_out, (hipStream_t)stream);
 }
 
 extern "C" int amvhip_reconstruct_dev(amvhip_ctx* c, const int16_t* d_coef, const uint32_t* d_nmcu_ok, uint32_t n, uint32_t w, uint32_t h,
                                       uint32_t flags, uint8_t* d_out, void* stream) {
     if (!c) return AMVHIP_ERR_ARG;
-    if (!size_ok(w, h) || (n && (!d_coef || !d_nmcu_ok || !d_out))) return fail(c, AMVHIP_ERR_ARG, "reconstruct: bad argument");
-    if (((uintptr_t)d_out & 3u) || ((uintptr_t)d_coef & 15u)) return fail(c, AMVHIP_ERR_ARG, "reconstruct: out must be 4-byte, coef 16-byte aligned");
-    if (int r = use_device(c)) return r;
-    if (n == 0) return AMVHIP_OK;
-    const FrameGeom g = make_geom(w, h);
-    SyncSinks sinks{};
-    sinks.coef = const_cast<int16_t*>(d_coef);
-    if (int r = clear_unwritten(c, n, g, flags, d_out, (hipStream_t)stream)) return r;
-    return reconstruct_launch(c, sinks, d_nmcu_ok, n, kAllFrames, n, g, flags, d_out, (hipStream_t)stream);
+    return reconstruct_dense(c, "reconstruct", d_coef, d_nmcu_ok, n, w, h, flags, 0u, d_out, stream);
 }
 
 int amv::decode_args_ok(amvhip_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n, uint32_t w,
@@ -192,6 +203,7 @@ int amv::decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, 
                        uint32_t n, uint32_t w, uint32_t h, uint32_t flags, uint8_t* d_out, int32_t* d_status, DecodeSet& b,
                        hipStream_t front, hipStream_t back, uint32_t lowres) {
     const FrameGeom g = make_geom(w, h);
+    const BackHalf bh = back_half(flags, lowres, g);
     // (rounds of up to 16 384 frames: every round is a pair of launches that usually find nothing to do, and a batch that
     // small is latency-bound -- three rounds cost the 10 000-frame stream 3 % of its step)
     const uint32_t round = fallback_round(n, g, 16384u, 4u);
@@ -210,9 +222,9 @@ int amv::decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, 
         HIP_TRY(c, hipStreamWaitEvent(back, c->ev_front, 0));
     }
     hipStream_t st = back;
-    if (int r = clear_unwritten(c, n, g, flags, d_out, st, lowres)) return r;
+    if (int r = clear_unwritten(c, n, bh, d_out, st)) return r;
     if (fb.list)   // the frames in records form (a launch that skips the others)
-        if (int r = reconstruct_launch(c, sinks, d_nmcu, n, kAllFrames, n, g, flags, d_out, st, lowres)) return r;
+        if (int r = reconstruct_launch(c, sinks, d_nmcu, n, kAllFrames, n, g, bh, d_out, st)) return r;
     // The others, a round of dense lines at a time.  With a list the count is on the device: the rounds past it find
     // nothing to do and leave at once (usually all of them: one pair of empty launches per round).
     for (uint32_t base = 0; base < fb.items; base += round) {
@@ -223,7 +235,7 @@ int amv::decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, 
                            fb.count, base, items, true, sinks.ok_in_blocks != 0u, st);
         }
         if (int r = check_launch(c, "huffman")) return r;
-        if (int r = reconstruct_launch(c, sinks, d_nmcu, n, FrameSel{fb.list, fb.count, base, items}, items, g, flags, d_out, st, lowres)) return r;
+        if (int r = reconstruct_launch(c, sinks, d_nmcu, n, FrameSel{fb.list, fb.count, base, items}, items, g, bh, d_out, st)) return r;
     }
     c->ws_bytes_per_frame = (double)(c->ws.cap + c->coef.cap + c->ws_bytes.cap + c->ws_line.cap + c->set[0].cap() + c->set[1].cap()) / n;
     return AMVHIP_OK;
@@ -302,7 +314,7 @@ extern "C" int amvhip_decode_batch_async(amvhip_ctx* c, const uint8_t* blob, uin
     if (n == 0) return AMVHIP_OK;
     hipStream_t st;
     if (int r = host_stream(c, &st)) return r;
-    const uint64_t fb = (flags & AMVHIP_FLAG_FFMPEG) ? amvhip_yuv420_frame_bytes(w, h) : amvhip_frame_bytes(w, h);
+    const uint64_t fb = back_half(flags, 0u, make_geom(w, h)).frame_bytes;
     // the staging buffers belong to the context: one host-buffer call at a time grows and fills them (hmu orders the
     // host-buffer entry points among themselves; mu, taken inside the _dev calls, orders the kernels' workspace)
     std::lock_guard<std::mutex> hlk(c->hmu);
@@ -358,16 +370,7 @@ extern "C" int amvhip_reconstruct_lowres_dev(amvhip_ctx* c, const int16_t* d_coe
                                              uint32_t lowres, uint8_t* d_out, void* stream) {
     if (!c) return AMVHIP_ERR_ARG;
     if (lowres < 1u || lowres > 3u) return fail(c, AMVHIP_ERR_ARG, "reconstruct_lowres: lowres must be 1, 2 or 3");
-    if (!size_ok(w, h) || (n && (!d_coef || !d_nmcu_ok || !d_out))) return fail(c, AMVHIP_ERR_ARG, "reconstruct_lowres: bad argument");
-    if (((uintptr_t)d_out & 3u) || ((uintptr_t)d_coef & 15u))
-        return fail(c, AMVHIP_ERR_ARG, "reconstruct_lowres: out must be 4-byte, coef 16-byte aligned");
-    if (int r = use_device(c)) return r;
-    if (n == 0) return AMVHIP_OK;
-    const FrameGeom g = make_geom(w, h);
-    SyncSinks sinks{};
-    sinks.coef = const_cast<int16_t*>(d_coef);
-    if (int r = clear_unwritten(c, n, g, AMVHIP_FLAG_FFMPEG, d_out, (hipStream_t)stream, lowres)) return r;
-    return reconstruct_launch(c, sinks, d_nmcu_ok, n, kAllFrames, n, g, AMVHIP_FLAG_FFMPEG, d_out, (hipStream_t)stream, lowres);
+    return reconstruct_dense(c, "reconstruct_lowres", d_coef, d_nmcu_ok, n, w, h, AMVHIP_FLAG_FFMPEG, lowres, d_out, stream);
 }
 
 // what both decode entry points ask of the mode, the format and the row pitch (before anything touches a device)

@@ -1,7 +1,8 @@
 // piece_map_test.cc -- the reconstruction kernels' workgroup -> (item, row group, segment) arithmetic
 // (amv-codec-tools_amd/csrc/amv_piece_map.h) checked on the CPU: for every shape, every workgroup number of a launch
 // names a piece exactly once, by the stated formula, and the divisions by reciprocal agree with real divisions right up
-// to the launch size the host allows.  Built with g++ by tests/test_abi_and_host.py; prints "ok <cases>" or the failure.
+// to the launch size the host allows; and the launches a call is made of (for_each_launch) cover every piece of every item
+// exactly once, whole or in parts, and a round's walkers visit each of its items once.  Built with g++ by tests/test_abi_and_host.py; prints "ok <cases>" or the failure.
 #include <cstdio>
 #include <vector>
 
@@ -57,8 +58,53 @@ static int check_limit(uint32_t row_groups, uint32_t nseg) {
     return 0;
 }
 
+// A call over `items` items as the launchers make it: every (item, row group, segment) is located by exactly one
+// workgroup of exactly one launch -- directly (a default launch, in parts of `most` items; 0: the real most_items), or by
+// the walk item0, item0 + piece_stride, ... of a round launch's workgroups -- and no product a workgroup forms leaves 32 bits.
+static int check_call(uint32_t row_groups, uint32_t nseg, uint32_t items, bool round, uint32_t most) {
+    std::vector<uint8_t> seen((size_t)items * row_groups * nseg, 0);
+    unsigned launches = 0;
+    int bad = 0;
+    for_each_launch(row_groups, nseg, items, round, [&](const PieceMap& pm, uint32_t grid) {
+        ++launches;
+        if ((uint64_t)(grid - 1u) * 8u * nseg > 0xffffffffull || (uint64_t)(pm.units - 1u) * row_groups > 0xffffffffull) bad = 1;
+        if (round && piece_stride(pm) != (items < kRoundWalkers ? items : kRoundWalkers)) bad = 1;
+        for (uint32_t b = 0; b < grid && !bad; ++b) {
+            uint32_t item, rg, seg;
+            if (!locate_piece(pm, b, item, rg, seg)) continue;
+            do {
+                if (item >= items) { bad = round ? bad : 1; break; }   // (a round's walk ends past the last item)
+                uint8_t& s = seen[((size_t)item * row_groups + rg) * nseg + seg];
+                if (s) bad = 1;
+                s = 1;
+                item += piece_stride(pm);
+            } while (round);
+        }
+    }, most);
+    for (uint8_t s : seen) if (!s) bad = 1;
+    const uint32_t want = round || !most ? 1u : (items + most - 1u) / most;   // (no geometry here is near most_items)
+    if (launches != want) bad = 1;
+    if (bad) printf("call rg=%u ns=%u items=%u round=%d most=%u: %u launches\n", row_groups, nseg, items, (int)round, most, launches);
+    return bad;
+}
+
 int main() {
     unsigned cases = 0;
+    for (uint32_t ns : {1u, 2u})                        // 16x16; 176x144-like
+        for (uint32_t rg : {1u, 3u, 15u})
+            for (uint32_t items : {1u, 7u, 8u, 9u, kRoundWalkers, kRoundWalkers + 1u}) {
+                for (uint32_t most : {0u, 1u, 3u, items}) {
+                    if (check_call(rg, ns, items, false, most)) return 1;
+                    ++cases;
+                }
+                if (check_call(rg, ns, items, true, 0u)) return 1;
+                ++cases;
+            }
+    {   // zero items: no launch at all, either way
+        unsigned launches = 0;
+        for (bool round : {false, true}) for_each_launch(3u, 2u, 0u, round, [&](const PieceMap&, uint32_t) { ++launches; });
+        if (launches) return printf("launches for no items\n"), 1;
+    }
     for (uint32_t rg = 1; rg <= 40; ++rg)
         for (uint32_t ns = 1; ns <= 14; ++ns)
             for (uint32_t w : {1u, 2u, 3u, 7u, 8u, 9u, 64u, 129u}) {

@@ -17,7 +17,7 @@ LEVELS = (1, 2, 3)
 # 16x16: one MCU; 160x120: h % 16 = 8; 130x98: the row shift, W_L and H_L odd at L = 2 and 3; 336x32: 21 MCUs per row, three
 # segments, the last one partial; 37x23: odd everywhere, one partial MCU column; 128x96: the first frames of AMV1.amv
 GEOMETRIES = ((16, 16, 8), (160, 120, 4), (130, 98, 3), (336, 32, 3), (37, 23, 5), (128, 96, 6))
-ROUND_WALKERS = 512          # launch_reconstruct_yuv_lowres: a round launch has at most this many workgroup walkers per piece
+ROUND_WALKERS = 512          # amv_segment.h: kRoundWalkers, the most walkers a round launch of any back half has
 
 
 def _chunks(orc, amv1, w, h, n, first=0):
@@ -98,7 +98,8 @@ def test_whole_path(ctx, pkg, orc, amv1, expect, w, h, n, entropy):
 
 def test_round_launch_walks(ctx, pkg, orc, amv1, expect):
     """the smallest batch whose round launch makes a workgroup walk to a second item: one more frame than the launch has
-    walkers (amv_reconstruct_lowres.hip: min(items, 512)), in the mode that sends every frame through the rounds; 16x16"""
+    walkers (amv_piece_map.h: for_each_launch, min(items, kRoundWalkers)), in the mode that sends every frame through the
+    rounds; 16x16"""
     w = h = 16
     n = ROUND_WALKERS + 1
     few = _chunks(orc, amv1, w, h, 7)
@@ -304,6 +305,39 @@ def test_crafted_coefficients(ctx, pkg, crafted):
                 at = int(np.flatnonzero(got[i] != want[i])[0])
                 pytest.fail("%s, lowres %d: byte %d: got %d, want %d" % (crafted["names"][i], L, at, got[i, at], want[i, at]))
         assert not got[-3].any() and got[-2].any() and got[-1].any()             # nmcu_ok 0: all zero
+
+
+@pytest.mark.parametrize("w,h", [(16, 16), (176, 16)], ids=["16x16", "176x16"])
+def test_reconstruct_launch_in_parts(ctx, pkg, orc, monkeypatch, w, h):
+    """a default launch in parts (amv_piece_map.h: for_each_launch with item_base): 7 frames through
+    amvhip_reconstruct_lowres_dev in parts of 3 (AMVHIP_RECON_MOST, read at every launch), at one segment per MCU row and
+    at two with the second one short (11 MCUs); every level, byte for byte the same as the call in one part and as the
+    restatement"""
+    import torch
+    n, nm = 7, ((w + 15) // 16) * ((h + 15) // 16)
+    rng = np.random.default_rng(0x9A27)
+    coef = np.ascontiguousarray(np.stack([cb.ordinary(rng, w, h) for _ in range(n)]).astype(np.int16))
+    ok = np.array([nm, nm, 0, nm, max(nm - 1, 0), nm, nm], np.uint32)
+    d_coef, d_ok = _t(coef), _t(ok)
+    tables = R.q60_tables(orc)
+    for L in LEVELS:
+        fb = ctx.lowres_frame_bytes(w, h, L)
+        want = np.stack([R.picture(coef[i], w, h, L, int(ok[i]), tables) for i in range(n)])
+        got = {}
+        for most in (None, "3"):
+            if most:
+                monkeypatch.setenv("AMVHIP_RECON_MOST", most)
+            else:
+                monkeypatch.delenv("AMVHIP_RECON_MOST", raising=False)
+            d_out = torch.full((n * fb + 1,), FILL, dtype=torch.uint8, device="cuda:0")
+            ctx.reconstruct_lowres_dev(d_coef, d_ok, n, w, h, L, d_out, torch.cuda.current_stream().cuda_stream)
+            torch.cuda.synchronize()
+            out = d_out.cpu().numpy()
+            assert out[-1] == FILL
+            got[most] = out[:-1].reshape(n, fb)
+        monkeypatch.delenv("AMVHIP_RECON_MOST", raising=False)
+        _same(got["3"], got[None], "%dx%d lowres %d, in parts of 3 against one part" % (w, h, L))
+        _same(got["3"], want, "%dx%d lowres %d, in parts of 3" % (w, h, L))
 
 
 def test_dst_fmt(ctx, pkg, orc, amv1):

@@ -724,7 +724,7 @@ def test_decode_fuzz_geometries_and_damage(ctx, orc):
 
 
 def test_reconstruction_launch_in_parts_and_extreme_shapes(ctx, pkg, orc, monkeypatch):
-    """the reconstruction's one-dimensional launch (amv_block_load.h: PieceMap): shapes whose piece counts are not
+    """the reconstruction's one-dimensional launch (amv_piece_map.h: PieceMap, for_each_launch): shapes whose piece counts are not
     powers of two (13 segments per MCU row; 40 MCU rows = 10 row groups; 9 rows = the five-row workgroups), and the
     same batches launched in parts of 3 frames (what a batch too large for the reciprocal division gets) -- every
     byte as the oracle's, in both output modes"""
@@ -746,6 +746,28 @@ def test_reconstruction_launch_in_parts_and_extreme_shapes(ctx, pkg, orc, monkey
             want, wst = _oracle_decode_ffmpeg(orc, chunks, w, h)
             assert (st == wst).all() and (got == want).all(), (w, h, most, "compat")
     monkeypatch.delenv("AMVHIP_RECON_MOST", raising=False)
+
+
+def test_round_launch_walks(ctx, pkg, orc):
+    """the smallest batch whose round launch makes a workgroup walk to a second item: one more frame than a round launch has
+    walkers (amv_segment.h: kRoundWalkers = 512), 16x16, in the mode that sends every frame through the rounds -- the BGR
+    and the full-size FFmpeg back half, every byte and status as the oracle's (tests/test_gpu_lowres.py has the reduced
+    sizes)"""
+    w = h = 16
+    n = 512 + 1
+    few = _synth_chunks(orc, 7, w, h)
+    chunks = [few[(i * 3) % 7] for i in range(n)]
+    pick = np.array([(i * 3) % 7 for i in range(n)])
+    ctx.set_entropy_mode(pkg.ENTROPY_SERIAL)
+    try:
+        got, st = _gpu_decode(ctx, chunks, w, h)
+        want, wst = _oracle_decode(orc, few, w, h)
+        assert (st == wst[pick]).all() and (got == want[pick]).all()
+        got, st = _gpu_decode_ffmpeg(ctx, pkg, chunks, w, h)
+        want, wst = _oracle_decode_ffmpeg(orc, few, w, h)
+        assert (st == wst[pick]).all() and (got == want[pick]).all()
+    finally:
+        ctx.set_entropy_mode(pkg.ENTROPY_AUTO)
 
 
 def test_encode_fuzz_geometries(ctx, orc):
