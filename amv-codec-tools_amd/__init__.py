@@ -150,6 +150,9 @@ SYMBOLS = {
     "amvhip_adpcm_encode_frame": (_int, [_vp, _vp, _u32, ctypes.POINTER(_i32), _vp, _u32]),
     "amvhip_adpcm_encode_trellis_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "amvhip_adpcm_encode_frame_trellis": (_int, [_vp, _vp, _u32, ctypes.POINTER(_i32), _u32, _vp, _u32]),
+    "amvhip_adpcm_encode_trellis_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _i32, _u32, _vp, _vp, _vp, _vp]),
+    "amvhip_adpcm_encode_trellis_stream": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _i32, _u32, _vp, _u64, _vp, _vp]),
+    "amvhip_adpcm_trellis_chain_stats": (_int, [_vp, _vp]),
     "amvhip_amv_audio_pairs": (_u32, [_u32, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]),
     "amvhip_amv_audio_frame_size": (_u32, [_u32, _u32, _u32]),
     "amvhip_adpcm_wav_encode_frame": (_int, [_vp, _vp, _int, _vp, _vp, _int]),
@@ -340,6 +343,14 @@ class Context:
                                                                   _ptr(step_in), _ptr(blob), _ptr(offs), stream),
                            "adpcm_encode_batch_dev")
 
+    def adpcm_encode_trellis_stream_dev(self, pcm, pcm_offs, nsamp, n, first_step_index, trellis, blob, offs, step_out=None,
+                                        stream=None):
+        """`-trellis N` over the chunks of the call as one stream, the step index carried on the device"""
+        return self._check(self.lib.amvhip_adpcm_encode_trellis_stream_dev(self.h, _ptr(pcm), _ptr(pcm_offs), _ptr(nsamp), n,
+                                                                           first_step_index, trellis, _ptr(blob), _ptr(offs),
+                                                                           _ptr(step_out), stream),
+                           "adpcm_encode_trellis_stream_dev")
+
     # pixel formats.  A picture is (planes, stride, c_stride, frame_stride, c_frame_stride) with planes a sequence of up to
     # three tensors / arrays / addresses (packed formats and GRAY8: one)
     @staticmethod
@@ -453,6 +464,13 @@ class Context:
                                                               n, _ptr(step_in), _ptr(blob), blob_bytes, _ptr(offs)),
                            "adpcm_encode_batch")
 
+    def adpcm_encode_trellis_stream(self, pcm, pcm_samples, pcm_offs, nsamp, n, first_step_index, trellis, blob, blob_bytes, offs,
+                                    step_out=None):
+        return self._check(self.lib.amvhip_adpcm_encode_trellis_stream(self.h, _ptr(pcm), pcm_samples, _ptr(pcm_offs), _ptr(nsamp),
+                                                                       n, first_step_index, trellis, _ptr(blob), blob_bytes,
+                                                                       _ptr(offs), _ptr(step_out)),
+                           "adpcm_encode_trellis_stream")
+
     def audio_resample_batch(self, pcm, pcm_samples, pcm_offs, nsamp, n, in_channels, in_rate, out, out_samples, out_offs,
                              out_channels, out_rate):
         return self._check(self.lib.amvhip_audio_resample_batch(self.h, _ptr(pcm), pcm_samples, _ptr(pcm_offs), _ptr(nsamp), n,
@@ -489,6 +507,15 @@ class Context:
         """last chained ADPCM encode: {"exhaustive": bool, "recoded": [chunks coded again in sweep 1, 2, ...]}"""
         out = (ctypes.c_uint32 * 64)()
         self._check(self.lib.amvhip_adpcm_chain_stats(self.h, out), "adpcm_chain_stats")
+        rec = list(out[1:63])
+        while rec and rec[-1] == 0:
+            rec.pop()
+        return {"exhaustive": bool(out[0]), "recoded": rec}
+
+    def adpcm_trellis_chain_stats(self):
+        """last trellis stream call: {"exhaustive": bool (the fall-back route), "recoded": [chunks coded again in sweep 1, 2, ...]}"""
+        out = (ctypes.c_uint32 * 64)()
+        self._check(self.lib.amvhip_adpcm_trellis_chain_stats(self.h, out), "adpcm_trellis_chain_stats")
         rec = list(out[1:63])
         while rec and rec[-1] == 0:
             rec.pop()

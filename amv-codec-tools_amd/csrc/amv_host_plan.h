@@ -484,4 +484,37 @@ inline uint32_t adpcm_default_sweeps(uint32_t n) {
     return sweeps;
 }
 
+// The trellis stream (amvhip_adpcm_encode_trellis_stream_dev).  A chunk's start is guessed by a search over the end of
+// its predecessor's m samples (m even): from the last freeze point but one (adpcm.c:405-417 keeps only the best node at
+// samples 127, 255, ...), so that the guess freezes where the real search does -- 129 to 256 samples, 226 of a
+// 1378-sample chunk.  On 300 chunks of the synthetic audio that guessed wrong 115 / 87 / 77 / 60 / 48 times at
+// N = 1 .. 5, against 128 / 110 / 102 / 87 / 72 for the last 128 samples and 119 / 102 / 94 / 82 / 54 for the last 256
+// (CPU model over the oracle).
+AMV_HD inline uint32_t adpcm_trellis_tail(uint32_t m) { return m <= 256u ? m : m - ((m + 127u) / 128u - 2u) * 128u; }
+
+// sweeps launched behind the guess pass.  The model's lists of 1378-sample chunks were empty after 2 to 4 sweeps at every
+// N; a run of k chunks of a few samples each (their ends follow their starts, and a guess over two samples is no guess)
+// takes k sweeps more, and streams with a quarter of their chunks that short needed up to 11.  A sweep over an empty
+// list is a launch that leaves at once, so the count is generous; past it the fall-back writes the bytes.
+constexpr uint32_t kTrellisSweeps = 16;
+constexpr uint32_t kTrellisSweepsMost = 60;
+
+// its chain workspace for n chunks: state[n] = {start, end}, two lists of n chunk numbers, 192 words of counters
+// ([0..63]: entries of list generation k, [64..127]: chunks coded again by sweep k, [128]: chunks the fall-back takes
+// on, counted from the stream's end) and the fall-back's maps [n][96]: where each of the 89 starts ends
+constexpr uint32_t kTrellisCounterWords = 192, kTrellisNeedWord = 128;
+struct TrellisChainPlan {
+    uint64_t state, list[2], counters, map, bytes;   // byte offsets, and the whole
+};
+inline TrellisChainPlan adpcm_trellis_chain_plan(uint32_t n) {
+    TrellisChainPlan p;
+    p.state = 0;
+    p.list[0] = (uint64_t)n * 8u;
+    p.list[1] = p.list[0] + (uint64_t)n * 4u;
+    p.counters = p.list[1] + (uint64_t)n * 4u;
+    p.map = p.counters + kTrellisCounterWords * 4u;
+    p.bytes = p.map + (uint64_t)n * 96u;
+    return p;
+}
+
 }  // namespace amv

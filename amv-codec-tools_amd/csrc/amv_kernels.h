@@ -278,6 +278,14 @@ void launch_adpcm_encode(const int16_t* pcm, const uint64_t* pcm_offs, const uin
 uint64_t adpcm_trellis_workspace(uint32_t n, uint32_t trellis);
 bool launch_adpcm_trellis(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, const int32_t* step_in,
                           uint32_t trellis, uint8_t* blob, const uint64_t* offs, int32_t* step_out, uint16_t* paths, hipStream_t s);
+// ... and the chunks of a call as ONE stream, the step index carried from chunk to chunk on the device (guessed starts,
+// a fixed number of sweeps over device-built lists, a check, and the 89-start fall-back behind it: see amv_adpcm.hip).
+// first_index 0..88; paths: adpcm_trellis_workspace(n, trellis) bytes; work: adpcm_trellis_chain_plan(n).bytes
+// (amv_host_plan.h), whose counters the launch zeroes; sweeps < 0: the fall-back at once.  Only enqueues; false: refused
+// before anything was queued.
+bool launch_adpcm_trellis_stream(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, uint32_t first_index,
+                                 uint32_t trellis, uint8_t* blob, const uint64_t* offs, int32_t* step_out, uint16_t* paths, void* work,
+                                 int sweeps, hipStream_t s);
 
 // ---- synthetic sources ----------------------------------------------------------------------
 void launch_synth_frames(uint32_t seed, uint32_t first, uint32_t n, uint32_t w, uint32_t h,

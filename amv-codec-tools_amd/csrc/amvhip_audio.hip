@@ -368,6 +368,77 @@ extern "C" int amvhip_adpcm_encode_trellis_batch_dev(amvhip_ctx* c, const int16_
     return check_launch(c, "adpcm_trellis");
 }
 
+// ... and for a stream: the chunks of a call in order, chunk 0 from first_step_index, every other from the index its
+// predecessor ends on (what a loop over amvhip_adpcm_encode_frame_trellis computes), resolved on the device.
+extern "C" int amvhip_adpcm_encode_trellis_stream_dev(amvhip_ctx* c, const int16_t* d_pcm, const uint64_t* d_pcm_offs,
+                                                      const uint32_t* d_nsamp, uint32_t n, int32_t first_step_index, uint32_t trellis,
+                                                      uint8_t* d_blob, const uint64_t* d_offs, int32_t* d_step_out, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (trellis < 1 || trellis > 5 || (n && (!d_pcm || !d_pcm_offs || !d_nsamp || !d_blob || !d_offs)))
+        return fail(c, AMVHIP_ERR_ARG, "adpcm_encode_trellis_stream: bad argument (trellis 1..5)");
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int r = ensure(c, c->trellis_ws, adpcm_trellis_workspace(n, trellis))) return r;
+    if (int r = ensure(c, c->trellis_chain, adpcm_trellis_chain_plan(n).bytes)) return r;
+    const uint32_t first = (uint32_t)(first_step_index < 0 ? 0 : (first_step_index > 88 ? 88 : first_step_index));
+    Timed t(c, AMVHIP_K_ADPCM_ENC, (hipStream_t)stream);
+    // (state, lists and counters live in the context's `trellis_chain` buffer: stream calls of ONE context must be ordered
+    // on the device -- one stream at a time, as for every _dev entry point)
+    if (!launch_adpcm_trellis_stream(d_pcm, d_pcm_offs, d_nsamp, n, first, trellis, d_blob, d_offs, d_step_out, (uint16_t*)c->trellis_ws.p,
+                                     c->trellis_chain.p, c->trellis_sweeps, (hipStream_t)stream))
+        return fail(c, AMVHIP_ERR_DEVICE, "adpcm_encode_trellis_stream: kernel attributes or the counters' memset refused");
+    c->trellis_chain_n = n;
+    return check_launch(c, "adpcm_trellis_stream");
+}
+
+extern "C" int amvhip_adpcm_trellis_chain_stats(amvhip_ctx* c, uint32_t out[64]) {
+    if (!c || !out) return AMVHIP_ERR_ARG;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (!c->trellis_chain_n) return fail(c, AMVHIP_ERR_ARG, "adpcm_trellis_chain_stats: no trellis stream has been coded");
+    uint32_t w[kTrellisCounterWords];
+    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipMemcpy(w, (const uint8_t*)c->trellis_chain.p + adpcm_trellis_chain_plan(c->trellis_chain_n).counters, sizeof w,
+                         hipMemcpyDeviceToHost));
+    out[0] = w[kTrellisNeedWord] ? 1u : 0u;
+    for (int k = 0; k < 62; ++k) out[k + 1] = w[64 + k];
+    out[63] = 0;
+    return AMVHIP_OK;
+}
+
+extern "C" int amvhip_adpcm_encode_trellis_stream(amvhip_ctx* c, const int16_t* pcm, uint64_t pcm_samples, const uint64_t* pcm_offs,
+                                                  const uint32_t* nsamp, uint32_t n, int32_t first_step_index, uint32_t trellis,
+                                                  uint8_t* blob, uint64_t blob_bytes, const uint64_t* offs, int32_t* step_out) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (trellis < 1 || trellis > 5 || (n && (!pcm || !pcm_offs || !nsamp || !blob || !offs)))
+        return fail(c, AMVHIP_ERR_ARG, "adpcm_encode_trellis_stream: bad argument (trellis 1..5)");
+    if (n == 0) return AMVHIP_OK;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (pcm_offs[i] > pcm_samples || nsamp[i] > pcm_samples - pcm_offs[i])
+            return fail(c, AMVHIP_ERR_ARG, "adpcm_encode_trellis_stream: chunk %u reads past pcm", i);
+        if (offs[i] > blob_bytes || 8ull + (nsamp[i] >> 1) > blob_bytes - offs[i])
+            return fail(c, AMVHIP_ERR_SPACE, "adpcm_encode_trellis_stream: blob too small for chunk %u", i);
+    }
+    hipStream_t hs;
+    if (int r = host_stream(c, &hs)) return r;
+    std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
+    if (int r = stage(c, c->h_in, pcm_samples * 2 + 16, pcm, pcm_samples * 2, hs)) return r;
+    if (int r = stage(c, c->h_offs, (size_t)n * 8, offs, (size_t)n * 8, hs)) return r;
+    if (int r = stage(c, c->h_lens, (size_t)n * 4, nsamp, (size_t)n * 4, hs)) return r;
+    if (int r = stage(c, c->h_out, blob_bytes, blob, blob_bytes, hs)) return r;   // keep untouched gaps
+    if (int r = stage(c, c->h_aux, (size_t)n * 8, pcm_offs, (size_t)n * 8, hs)) return r;
+    if (int r = ensure(c, c->h_status, (size_t)n * 4)) return r;
+    if (int r = amvhip_adpcm_encode_trellis_stream_dev(c, (const int16_t*)c->h_in.p, (const uint64_t*)c->h_aux.p, (const uint32_t*)c->h_lens.p, n,
+                                                       first_step_index, trellis, (uint8_t*)c->h_out.p, (const uint64_t*)c->h_offs.p,
+                                                       step_out ? (int32_t*)c->h_status.p : nullptr, hs))
+        return r;
+    HIP_TRY(c, hipMemcpyAsync(blob, c->h_out.p, blob_bytes, hipMemcpyDeviceToHost, hs));
+    if (step_out) HIP_TRY(c, hipMemcpyAsync(step_out, c->h_status.p, (size_t)n * 4, hipMemcpyDeviceToHost, hs));
+    HIP_TRY(c, hipStreamSynchronize(hs));
+    return AMVHIP_OK;
+}
+
 // One AMV audio chunk with the step index handed in and out: what adpcm_encode_frame (adpcm.c:461-498) does per
 // call with the index it keeps in its context.  The end index is read off a decode of the fresh chunk (the decoder
 // walks the same index chain), one synchronisation for both kernels.

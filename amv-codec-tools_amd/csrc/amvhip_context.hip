@@ -104,6 +104,8 @@ static void read_knobs(amvhip_ctx* c) {
             c->adpcm_sweeps = strcmp(e, "map") == 0 ? -1 : (atoi(e) < 0 ? 0 : (atoi(e) > 60 ? 60 : atoi(e)));
         }
     }
+    if (const char* e = getenv("AMVHIP_ADPCM_TRELLIS_SWEEPS"))   // test knob: "map" = the fall-back at once, or a sweep count (0: none)
+        c->trellis_sweeps = strcmp(e, "map") == 0 ? -1 : (atoi(e) < 0 ? 0 : (atoi(e) > (int)kTrellisSweepsMost ? (int)kTrellisSweepsMost : atoi(e)));
 }
 
 extern "C" int amvhip_create(amvhip_ctx** out, int device) {

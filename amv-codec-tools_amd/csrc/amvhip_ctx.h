@@ -49,7 +49,7 @@ struct amvhip_ctx {
     std::string err;
     DevBuf d_dec, d_enc;   // HuffDecodeImage, HuffEncodeImage
     // workspace
-    DevBuf coef, tmp, flag, map, start, enc_retry, stats, ws, ws_line, layout, ws_bytes, scaled, trellis_ws, chain, split;
+    DevBuf coef, tmp, flag, map, start, enc_retry, stats, ws, ws_line, layout, ws_bytes, scaled, trellis_ws, trellis_chain, chain, split;
     // the shim around the rescaler: the source as YUV420P, the rescaled YUV420P ahead of a last conversion, the decoder's planes
     DevBuf pix_in, pix_out, pix_dec;
     // the video front end: the deinterlaced (and cropped) source ahead of the shim
@@ -77,6 +77,8 @@ struct amvhip_ctx {
     bool adpcm_sweeps_set = false;   // false: by stream length
     bool adpcm_settle = true;        // "nosettle": the chain stops after its launched sweeps (test knob: its check must notice)
     uint32_t chain_n = 0;            // chunks of the last chained ADPCM encode (where its counters are in `chain`)
+    int trellis_sweeps = (int)amv::kTrellisSweeps;   // AMVHIP_ADPCM_TRELLIS_SWEEPS: sweeps of the trellis stream (-1: its fall-back at once)
+    uint32_t trellis_chain_n = 0;    // chunks of the last trellis stream (where its counters are in `trellis_chain`)
     // host-pointer staging (one in-order stream of the context's own carries every host-buffer entry point)
     DevBuf h_in, h_offs, h_lens, h_out, h_status, h_aux, a_in, a_tab, a_out, r_in, r_tab, r_out;
     hipStream_t hstream = nullptr;

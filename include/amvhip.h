@@ -725,6 +725,27 @@ int amvhip_adpcm_encode_trellis_batch_dev(amvhip_ctx *ctx, const int16_t *d_pcm,
                                           uint8_t *d_blob, const uint64_t *d_offs, int32_t *d_step_out, void *stream);
 int amvhip_adpcm_encode_frame_trellis(amvhip_ctx *ctx, const int16_t *samples, uint32_t nsamp, int32_t *step_index,
                                       uint32_t trellis, uint8_t *chunk, uint32_t cap);
+/* `-trellis N` for a whole stream: the chunks of one call are one stream, in order.  Chunk 0 starts from
+ * first_step_index (clipped to 0..88; 0 is a fresh encoder context, a track coded in windows hands in the previous
+ * call's last end index), chunk i > 0 from the index chunk i - 1 ends on: byte for byte and index for index what a loop
+ * over amvhip_adpcm_encode_frame_trellis gives.  Chunk layout, the nsamp & ~1 rule and the nsamp == 0 chunk (eight header
+ * bytes, its end is its start) as in amvhip_adpcm_encode_trellis_batch_dev; no byte of d_blob outside the chunks'
+ * 8 + nsamp/2 bytes is written.  d_step_out (optional) receives the n end indices.  The chain is resolved on the device
+ * (guessed starts, a fixed number of sweeps that code again whoever guessed wrong, a check, and an 89-start map behind
+ * it for a stream that does not settle): the device form only enqueues on `stream` -- no host synchronisation, no launch
+ * per chunk, the same launches whatever n and the samples.  Calls of one context are ordered on the device by the
+ * caller (one stream at a time), as for every _dev entry point. */
+int amvhip_adpcm_encode_trellis_stream_dev(amvhip_ctx *ctx, const int16_t *d_pcm, const uint64_t *d_pcm_offs,
+                                           const uint32_t *d_nsamp, uint32_t n, int32_t first_step_index, uint32_t trellis,
+                                           uint8_t *d_blob, const uint64_t *d_offs, int32_t *d_step_out, void *stream);
+/* host-buffer form (H2D, kernels, D2H, synchronous) */
+int amvhip_adpcm_encode_trellis_stream(amvhip_ctx *ctx, const int16_t *pcm, uint64_t pcm_samples, const uint64_t *pcm_offs,
+                                       const uint32_t *nsamp, uint32_t n, int32_t first_step_index, uint32_t trellis,
+                                       uint8_t *blob, uint64_t blob_bytes, const uint64_t *offs, int32_t *step_out);
+/* Diagnostic of the last trellis stream call (waits for the device), laid out as amvhip_adpcm_chain_stats: out[0] = 1 if
+ * the stream took the fall-back route, out[1..] = chunks coded again in sweep 1, 2, ... (0-terminated).  Returns
+ * AMVHIP_OK, or AMVHIP_ERR_ARG when no such call has been made. */
+int amvhip_adpcm_trellis_chain_stats(amvhip_ctx *ctx, uint32_t out[64]);
 /* The framing the reference's AMV audio encoder and muxer apply around the kernel (host arithmetic only):
  * amvhip_amv_audio_pairs      adpcm.c:469-477,497: sample pairs of the next chunk for a nominal frame_size (odd sizes
  *                             alternate, a chunk that would straddle a whole second is stretched to end on it);
