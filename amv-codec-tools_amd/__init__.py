@@ -115,6 +115,11 @@ SYMBOLS = {
     "amvhip_encode_yuv422_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "amvhip_encode_yuv420_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp]),
     "amvhip_encode_yuv422_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp]),
+    "amvhip_encode_nr_max": (_u32, [_u32, _u32]),
+    "amvhip_encode_yuv420_nr_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_encode_yuv420_nr_stream": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp]),
+    "amvhip_encode_nr_stream_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_encode_nr_stream": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp]),
     "amvhip_resample_yuv420_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
     "amvhip_encode_yuv420_scaled_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "amvhip_img_convert_supported": (_int, [_int, _int, _u32, _u32]),
@@ -312,6 +317,35 @@ class Context:
         return self._check(self.lib.amvhip_encode_yuv420_batch_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride,
                                                                    y_frame, c_frame, n, w, h, qbias, _ptr(blob), blob_cap,
                                                                    _ptr(offs), _ptr(lens), stream), "encode_yuv420_batch_dev")
+
+    def encode_nr_max(self, w, h):
+        """the largest `nr` the -nr entries take at this frame size (0: none but 0)"""
+        return self.lib.amvhip_encode_nr_max(w, h)
+
+    def encode_yuv420_nr_stream_dev(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, qbias, nr, state, blob, blob_cap,
+                                    offs, lens, stream=None):
+        """the reference's -nr over a stream coded in calls of any size; state: int32[65] on the device (64 sums, the
+        count), read at entry and written at exit, all zeros at the start of a stream"""
+        return self._check(self.lib.amvhip_encode_yuv420_nr_stream_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride,
+                                                                       y_frame, c_frame, n, w, h, qbias, nr, _ptr(state), _ptr(blob),
+                                                                       blob_cap, _ptr(offs), _ptr(lens), stream),
+                           "encode_yuv420_nr_stream_dev")
+
+    def encode_yuv420_nr_stream(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, qbias, nr, state, blob, blob_cap, offs,
+                                lens):
+        return self._check(self.lib.amvhip_encode_yuv420_nr_stream(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride,
+                                                                   y_frame, c_frame, n, w, h, qbias, nr, _ptr(state), _ptr(blob),
+                                                                   blob_cap, _ptr(offs), _ptr(lens)), "encode_yuv420_nr_stream")
+
+    def encode_nr_stream_dev(self, pix, pix_stride, is_bgr, n, w, h, qbias, nr, state, blob, blob_cap, offs, lens, stream=None):
+        return self._check(self.lib.amvhip_encode_nr_stream_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, qbias, nr,
+                                                                _ptr(state), _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), stream),
+                           "encode_nr_stream_dev")
+
+    def encode_nr_stream(self, pix, pix_stride, is_bgr, n, w, h, qbias, nr, state, blob, blob_cap, offs, lens):
+        return self._check(self.lib.amvhip_encode_nr_stream(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, qbias, nr,
+                                                            _ptr(state), _ptr(blob), blob_cap, _ptr(offs), _ptr(lens)),
+                           "encode_nr_stream")
 
     def encode_yuv422_batch_dev(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, qbias, blob, blob_cap, offs,
                                 lens, stream=None):

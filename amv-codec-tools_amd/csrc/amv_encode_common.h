@@ -10,6 +10,7 @@
 // fixed tables (AmvJpeg.c:30-61) and a true -128 level shift so that amvlib and the patched FFmpeg both decode it.
 #pragma once
 #include "amv_kernels.h"
+#include "amv_nr_plan.h"
 #include "amv_segment.h"
 
 namespace amv {
@@ -346,8 +347,13 @@ __device__ __forceinline__ uint32_t interleave_halves(uint32_t x) {
 // of a pair reduced to 0 / 1 by one packed minimum, sixteen pairs shifted into one word -- even scan positions in its low
 // half, odd ones in its high half -- and the halves interleaved by four exchange steps.
 // s_qmul: the workgroup's copy of kQuantMul (load_quant_mul).
+// kNr: denoise_dct_c (mpegvideo_enc.c:2937-2959; amv_nr_plan.h) between the column pass and the quantiser, with the
+// frame's 64 offsets in s_nr_off (LDS, 16-byte aligned, entry c * 8 + r for row r of column c: a column's eight are one
+// 16-byte read).  The sums that denoise_dct_c also takes are amv_nr_sums_kernel's (amv_encode_nr.hip).
+template <bool kNr = false>
 __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_t* s_cb, const int16_t* s_cr, const uint32_t* s_qmul,
-                                                uint32_t lane, uint32_t qbias, uint32_t (&out)[32], uint32_t& nz_lo, uint32_t& nz_hi) {
+                                                uint32_t lane, uint32_t qbias, uint32_t (&out)[32], uint32_t& nz_lo, uint32_t& nz_hi,
+                                                const uint16_t* s_nr_off = nullptr) {
     const uint32_t m = lane / 6u, k6 = lane - 6u * m;
     const bool is_c = k6 >= 4u;
     const int16_t* in = is_c ? (k6 == 4u ? s_cb : s_cr) + m * 8u
@@ -374,6 +380,15 @@ __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_
         const uint4 ma = qm[2 * c], mb = qm[2 * c + 1];            // this column's multipliers (on their way during the pass)
         const uint32_t mul[8] = {ma.x, ma.y, ma.z, ma.w, mb.x, mb.y, mb.z, mb.w};
         fdct8<1>(col);
+        if (kNr) {
+            const uint4 o = reinterpret_cast<const uint4*>(s_nr_off)[c];
+            const uint32_t ow[4] = {o.x, o.y, o.z, o.w};
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const uint32_t off = (ow[r >> 1] >> (16 * (r & 1))) & 0xffffu;
+                col[r] = (r == 0 && c == 0) ? nr_denoise_dc(col[r], off) : nr_denoise(col[r], off);
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
             const int scan = kScanOfNatural[r * 8 + c];
@@ -404,6 +419,10 @@ __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_
     nz_lo = interleave_halves(even_odd_lo) & ~1u;                  // (the DC is not in the mask)
     nz_hi = interleave_halves(even_odd_hi);
 }
+
+// the one optional trailing argument of the encoder kernels (`class... Nr`): the frames' noise-reduction offsets, or nothing
+__device__ __forceinline__ const uint16_t* nr_offsets_of() { return nullptr; }
+__device__ __forceinline__ const uint16_t* nr_offsets_of(const uint16_t* offs) { return offs; }
 
 // coefficient k of lane `lane`'s 128-byte line in an LDS region of 64 lines: 16-byte granules XOR-swizzled by lane, so
 // that lanes reading the same granule of their own lines do not meet on banks

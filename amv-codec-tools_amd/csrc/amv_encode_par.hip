@@ -215,11 +215,16 @@ __device__ __forceinline__ Cursor seek_symbol(uint32_t j, uint32_t nb, const uin
 
 }  // namespace
 
-template <bool kYuv>
+// Nr: nothing (the plain encoder, its signature and code as they always were), or one `const uint16_t*` -- the frames'
+// noise-reduction offsets (64 uint16 per frame, amv_nr_plan.h): the frame's 128 bytes go to LDS and transform_block
+// denoises with them between the column pass and the quantiser.
+template <bool kYuv, class... Nr>
 __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
     Source in, uint32_t n, FrameGeom g, uint32_t nseg, uint32_t per_seg, uint32_t qbias, const HuffEncodeImage* __restrict__ img,
     uint8_t* __restrict__ tmp, uint32_t bound, uint32_t* __restrict__ lens, uint32_t* __restrict__ retry_list,
-    uint32_t* __restrict__ retry_count) {
+    uint32_t* __restrict__ retry_count, Nr... nr) {
+    constexpr bool kNr = sizeof...(Nr) != 0;
+    static_assert(sizeof...(Nr) <= 1, "the offsets, or nothing");
     __shared__ __attribute__((aligned(16))) uint8_t s_region[kWaves][kRegionBytes];
     __shared__ uint32_t s_own[kOwnWords * kLanes];
     __shared__ uint32_t s_bits[kWindowWords];
@@ -234,6 +239,12 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
     for (uint32_t i = tl; i < 1024u; i += kLanes) s_book[i] = (&img->code[0][0])[i];
     for (uint32_t i = tl; i < kWindowWords; i += kLanes) s_bits[i] = 0u;
     load_quant_mul(s_qmul, tl, kLanes);
+    const uint16_t* s_nr = nullptr;
+    if constexpr (kNr) {
+        __shared__ __attribute__((aligned(16))) uint32_t s_nr_off[32];
+        if (tl < 32u) s_nr_off[tl] = reinterpret_cast<const uint32_t*>(nr_offsets_of(nr...) + (uint64_t)f * 64u)[tl];
+        s_nr = reinterpret_cast<const uint16_t*>(s_nr_off);
+    }
     uint8_t* const region = s_region[wave];
     int16_t* const s_y = reinterpret_cast<int16_t*>(region);
     int16_t* const s_cb = s_y + 16 * kPitchY;
@@ -303,7 +314,7 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
             convert_segment<kYuv>(in, f, g, my, m0, cnt, lane, s_y, s_cb, s_cr);
             wave_sync();
             uint32_t line[32];
-            if (live) transform_block(s_y, s_cb, s_cr, s_qmul, lane, qbias, line, nz_lo, nz_hi);
+            if (live) transform_block<kNr>(s_y, s_cb, s_cr, s_qmul, lane, qbias, line, nz_lo, nz_hi, s_nr);
             wave_sync();                                          // every lane has its samples: the planes become the lines
             if (live) {
                 dc = (int)(int16_t)(line[0] & 0xffffu);
@@ -405,11 +416,17 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
 
 void launch_encode_frames(const uint8_t* pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n, const FrameGeom& g,
                           uint32_t qbias, const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens,
-                          uint32_t* retry_list, uint32_t* retry_count, hipStream_t s) {
+                          uint32_t* retry_list, uint32_t* retry_count, hipStream_t s, const uint16_t* nr_offs) {
     if (n == 0) return;
     const uint32_t nseg = segs_per_row(g);
     const uint32_t per_seg = (g.mcu_cols + nseg - 1) / nseg;      // balanced: 11 columns -> 6 + 5
-    if (yuv)
+    if (nr_offs && yuv)
+        hipLaunchKernelGGL((amv_encode_frame_kernel<true, const uint16_t*>), dim3(n), dim3(kLanes), 0, s, Source{nullptr, 0u, 0, *yuv}, n, g, nseg, per_seg,
+                           qbias, d_img, tmp, bound, lens, retry_list, retry_count, nr_offs);
+    else if (nr_offs)
+        hipLaunchKernelGGL((amv_encode_frame_kernel<false, const uint16_t*>), dim3(n), dim3(kLanes), 0, s, Source{pix, pix_stride, is_bgr, YuvSource{}}, n, g,
+                           nseg, per_seg, qbias, d_img, tmp, bound, lens, retry_list, retry_count, nr_offs);
+    else if (yuv)
         hipLaunchKernelGGL(amv_encode_frame_kernel<true>, dim3(n), dim3(kLanes), 0, s, Source{nullptr, 0u, 0, *yuv}, n, g, nseg, per_seg,
                            qbias, d_img, tmp, bound, lens, retry_list, retry_count);
     else

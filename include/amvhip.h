@@ -369,6 +369,43 @@ int amvhip_encode_yuv420_batch(amvhip_ctx *ctx, const uint8_t *y, const uint8_t 
                                uint64_t c_frame_stride, uint32_t n, uint32_t width, uint32_t height,
                                uint32_t qbias, uint8_t *blob, uint64_t blob_cap, uint64_t *offs, uint32_t *lens);
 /*
+ * The reference's -nr N noise reduction (denoise_dct_c, mpegvideo_enc.c:2937-2959; update_noise_reduction,
+ * mpegvideo.c:861-876) for a stream coded in calls of any size: a dead zone in the DCT domain, between fdct and
+ * quantiser, whose width adapts per coefficient position to the running mean magnitude of the stream.  The one lever
+ * on size against detail that works with AMV's fixed quantiser tables.  Arguments as amvhip_encode_yuv420_batch(_dev) /
+ * amvhip_encode_batch(_dev), and:
+ *   nr       : the reference's avctx->noise_reduction.  0: the bytes of the plain entry, the state left as it was (the
+ *              reference allocates nothing then, mpegvideo.c:318, :520).  More than amvhip_encode_nr_max(width, height)
+ *              is refused (AMVHIP_ERR_ARG): beyond it the reference's int arithmetic would wrap.
+ *   d_state  : int32[65] on the device (state: the same in host memory), 4-byte aligned: dct_error_sum[64] in the
+ *              reference's index order (the fdct output's row-major order; the six blocks of an MCU share the array), then
+ *              dct_count.  Read at entry, written at exit; all zeros starts a stream.  The layout is part of the contract:
+ *              a caller may save and restore it.  n frames in one call equal the same frames in any number of calls with
+ *              the state carried, byte for byte.  A state the caller made up (negative sums, a count no stream of this
+ *              frame size reaches) gives unspecified bytes and state, but no access out of range.
+ * The blob-capacity rule is the plain entries'.  The arithmetic is the reference's bit for bit, the offset's truncation to
+ * 16 bits included; this encoder's fdct runs on samples - 128, so the DC enters the sums and the dead zone as DC + 8192,
+ * which is the reference's DC exactly.
+ */
+uint32_t amvhip_encode_nr_max(uint32_t width, uint32_t height);   /* 0: no nr but 0 at this size (the frame is too large) */
+int amvhip_encode_yuv420_nr_stream_dev(amvhip_ctx *ctx, const uint8_t *d_y, const uint8_t *d_cb, const uint8_t *d_cr,
+                                       uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride,
+                                       uint64_t c_frame_stride, uint32_t n, uint32_t width, uint32_t height,
+                                       uint32_t qbias, uint32_t nr, int32_t *d_state, uint8_t *d_blob, uint64_t blob_cap,
+                                       uint64_t *d_offs, uint32_t *d_lens, void *stream);
+int amvhip_encode_yuv420_nr_stream(amvhip_ctx *ctx, const uint8_t *y, const uint8_t *cb, const uint8_t *cr,
+                                   uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride,
+                                   uint64_t c_frame_stride, uint32_t n, uint32_t width, uint32_t height,
+                                   uint32_t qbias, uint32_t nr, int32_t *state, uint8_t *blob, uint64_t blob_cap,
+                                   uint64_t *offs, uint32_t *lens);
+int amvhip_encode_nr_stream_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr,
+                                uint32_t n, uint32_t width, uint32_t height, uint32_t qbias, uint32_t nr,
+                                int32_t *d_state, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offs,
+                                uint32_t *d_lens, void *stream);
+int amvhip_encode_nr_stream(amvhip_ctx *ctx, const uint8_t *pix, uint32_t pix_stride, int is_bgr,
+                            uint32_t n, uint32_t width, uint32_t height, uint32_t qbias, uint32_t nr,
+                            int32_t *state, uint8_t *blob, uint64_t blob_cap, uint64_t *offs, uint32_t *lens);
+/*
  * ... and from planar YUVJ422P, the other pixel format amv_encoder declares (mjpegenc.c:493; chroma planes (w/2) x h,
  * mpegvideo_enc.c:534-543 h/v sampling 2x2 : 1x2).  The reference would code such a picture as MCUs of eight blocks
  * (ff_mjpeg_encode_mb, mjpegenc.c:437-450, the CHROMA_420 test failing) -- a scan no AMV decoder can read: the container
