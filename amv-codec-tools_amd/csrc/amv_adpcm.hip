@@ -16,39 +16,27 @@
 // tail of the chunk before arrives at: right for 59 % of the synthetic chunks) and notes the index
 // it ends with; a chunk whose predecessor ended elsewhere than it assumed is coded again, and so
 // on while ends keep changing (amv_adpcm_guess_kernel, amv_adpcm_sweep_kernel: the lists shrink
-// by 3.7x per sweep on the synthetic audio, 1.7 encodes of work in all instead of 89).  Chunk 0
-// starts from the true index, so after k sweeps the first k chunks are final whatever the data:
-// a stream whose chain does not settle within the sweeps given (amv_adpcm_settle_kernel raises a
-// flag on the device) takes the exhaustive route instead, which needs no guess because
-// step_index has only 89 values: amv_adpcm_map_kernel runs every chunk from all 89 starts (state
-// only, one lane per (chunk, start) pair), the amv_adpcm_chain_* kernels compose the 89-entry
-// maps (256 chunks per workgroup through LDS, then the workgroup maps, then back down), and the
-// encode runs one lane per chunk from its now-known start.  Those kernels are always queued
-// (the stream is never waited for) and leave at once when the flag is down.
-#include <atomic>
-
-#include "amv_host_plan.h"
-#include "amv_kernels.h"
+// by 3.7x per sweep on the synthetic audio, 1.7 encodes of work in all instead of 89; behind
+// them amv_adpcm_front_kernel, amv_adpcm_settle_kernel and amv_adpcm_check_kernel).  The scheme
+// and the pieces it shares with the trellis stream are in amv_adpcm_chain.h.  A stream whose
+// chain does not settle within the sweeps given (the settle and check kernels raise a flag on
+// the device) takes the exhaustive route instead: amv_adpcm_map_kernel runs every chunk from all
+// 89 starts (state only, one lane per (chunk, start) pair), amv_adpcm_chain_kernel composes the
+// 89-entry maps (256 chunks per workgroup through LDS; the workgroup that finishes last walks
+// the workgroups' maps), and amv_adpcm_encode_mapped_kernel walks down again and codes one lane
+// per chunk from its now-known start.  Those kernels are always queued (the stream is never
+// waited for) and leave at once when the flag is down.
+#include "amv_adpcm_chain.h"
 
 namespace amv {
 
 namespace {
-
-__device__ __forceinline__ int clip16(int v) { return min(max(v, -32768), 32767); }
-__device__ __forceinline__ int clip_index(int v) { return min(max(v, 0), 88); }
 
 // under-aligned wide accesses: gfx950 under HSA serves them in hardware, one instruction each
 struct __attribute__((packed, aligned(1))) Bytes16 { uint32_t w[4]; };
 struct __attribute__((packed, aligned(1))) Bytes8 { uint32_t w[2]; };
 struct __attribute__((packed, aligned(2))) Pcm8 { uint32_t w[4]; };
 struct __attribute__((packed, aligned(2))) Pcm32 { uint32_t w[16]; };
-
-// the step table in LDS (indexed per lane on the critical path; a constant-memory table would be a
-// dependent global load per sample)
-__device__ __forceinline__ void load_steps(uint32_t* s_step) {
-    for (uint32_t i = threadIdx.x; i < 89u; i += blockDim.x) s_step[i] = (uint32_t)kImaStep[i];
-    __syncthreads();
-}
 
 // kImaIndexAdjust[nibble] = {-1,-1,-1,-1,2,4,6,8} on the magnitude bits
 __device__ __forceinline__ int index_adjust(uint32_t mag3) {
@@ -401,8 +389,6 @@ __device__ __forceinline__ void encode_rows(const int16_t* __restrict__ x, uint3
     encode_run<kWrite>(x + done, m - done, s, kWrite ? d + (done >> 1) : d, l);
 }
 
-constexpr uint32_t kChainBlock = 256;   // chunks whose maps one workgroup composes through LDS (24 KB)
-
 }  // namespace
 
 // Decode, a wave per chunk.  Both chains of AdpcmImaExpandNibble (AdpcmIma.c:170-204) are compositions of "add a constant,
@@ -573,23 +559,11 @@ __global__ void amv_adpcm_wav_encode_kernel(const int16_t* __restrict__ x, int g
 }
 
 // ---- the guessed-start route ----------------------------------------------------------------------------------
-// device words with agent scope: what one lane stores another lane of the same launch may read (never torn, possibly
-// the value before -- the sweeps are written for that)
-__device__ __forceinline__ uint32_t peek(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void poke(uint32_t* p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// state[i] = {start the chunk's bytes were coded from, end reached from it}, replaced as ONE 64-bit word so that no reader
-// and no second writer ever sees one chunk's start beside another coding's end; returns the end that was there.  Whoever
-// changes a chunk's end lists its successor: that rule, and a listed chunk being coded again whenever its start is not its
-// predecessor's end, is all the sweeps rest on.  kPredicted in the start: the end is where the chunk WILL end from that
-// start (the front sweep's look-ahead), its bytes are not coded yet -- no real start equals it, so the chunk is coded
-// when its turn comes.
+// (the scheme, and peek / poke / swap_state, list_wrong, sweep_todo / sweep_publish, chain_broken / note_broken and
+// walk_maps: amv_adpcm_chain.h)
+// kPredicted in a state's start (the front sweep's look-ahead): the end is where the chunk WILL end from that start, its
+// bytes are not coded yet -- no real start equals it, so the chunk is coded when its turn comes.
 constexpr uint32_t kPredicted = 0x100u;
-__device__ __forceinline__ uint32_t swap_state(uint2* p, uint32_t start, uint32_t end) {
-    const uint64_t old = __hip_atomic_exchange(reinterpret_cast<uint64_t*>(p), (uint64_t)start | (uint64_t)end << 32, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT);
-    return (uint32_t)(old >> 32);
-}
 
 // the chunks of a wave's 64 lanes (live: this lane has one), each from its start index; returns the end index
 __device__ __forceinline__ int encode_chunk(const int16_t* __restrict__ x, uint32_t nsamp, int start, uint8_t* __restrict__ d,
@@ -654,20 +628,10 @@ __global__ __launch_bounds__(kEncodeBlock) void amv_adpcm_guess_kernel(
     __syncthreads();
     const uint32_t left = (uint32_t)__shfl_up(end, 1);          // (by every lane: lane 1 reads lane 0's)
     const uint32_t before = lane ? left : (wave ? s_end[wave - 1u] : ~0u);
-    const bool wrong = live && i > 0u && (uint32_t)start != before;
-    const uint64_t mask = __ballot(wrong);
-    if (mask) {
-        uint32_t base = 0;
-        if (lane == 0u) base = atomicAdd(count, (uint32_t)__popcll(mask));
-        base = (uint32_t)__shfl((int)base, 0);
-        if (wrong) list[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = i;
-    }
+    list_wrong(live && i > 0u && (uint32_t)start != before, i, list, count);
 }
 
-// One sweep over a list: a listed chunk whose predecessor's end is not the start it used is coded again from there; if
-// its own end moves, its successor is listed for the next sweep.  A chunk is listed by its predecessor only, so no list
-// holds it twice.  Predecessor and successor may be in the same list: whichever of the predecessor's ends the successor
-// reads, it is listed again when that end moved, and skips the work then if it had read the new one already.
+// One sweep over a list (sweep_todo, the coding, sweep_publish).
 template <bool kStaged>
 __device__ __forceinline__ void sweep_one(const int16_t* __restrict__ pcm, const uint64_t* __restrict__ pcm_offs,
                                           const uint32_t* __restrict__ nsamp, uint32_t n, uint8_t* __restrict__ blob,
@@ -676,13 +640,8 @@ __device__ __forceinline__ void sweep_one(const int16_t* __restrict__ pcm, const
                                           StageLds* st) {
     // (kStaged: all 64 lanes of the wave come here together, st = the wave's staging tile; `listed`: this lane has an entry i
     // of the list)
-    uint32_t* sw = reinterpret_cast<uint32_t*>(state);
     uint32_t start = 0u;
-    bool todo = false;
-    if (listed) {
-        start = peek(sw + 2u * (i - 1u) + 1u);
-        todo = start != peek(sw + 2u * i);
-    }
+    const bool todo = listed && sweep_todo(state, i, start);
     uint32_t end;
     if (kStaged) {
         end = (uint32_t)encode_chunk(todo ? pcm + pcm_offs[i] : pcm, todo ? nsamp[i] : 0u, (int)start, todo ? blob + offs[i] : blob, todo,
@@ -692,7 +651,7 @@ __device__ __forceinline__ void sweep_one(const int16_t* __restrict__ pcm, const
         if (!todo) return;
         end = (uint32_t)encode_chunk_alone(pcm + pcm_offs[i], nsamp[i], (int)start, blob + offs[i], s_tab);
     }
-    if (swap_state(state + i, start, end) != end && i + 1u < n) list_out[atomicAdd(count_out, 1u)] = i + 1u;
+    sweep_publish(state, n, i, start, end, list_out, count_out);
 }
 
 constexpr uint32_t kStagedAbove = 32768;   // list entries from which a sweep is bound by its memory accesses, not by one chunk's chain
@@ -764,8 +723,8 @@ __global__ __launch_bounds__(kFrontThreads) void amv_adpcm_front_kernel(
     for (uint32_t h = blockIdx.x; h < count; h += gridDim.x) {
         const uint32_t i = list_in[h];
         if (threadIdx.x == kFrontHead) {
-            const uint32_t start = peek(sw + 2u * (i - 1u) + 1u);
-            uint32_t what = start != peek(sw + 2u * i) ? 1u : 0u;
+            uint32_t start;
+            uint32_t what = sweep_todo(state, i, start) ? 1u : 0u;
             if (what) {
                 // a run of chunks whose starts are all about to move has ONE head, the first; the kFrontAhead chunks behind
                 // it are in its look-ahead, and coding them here from an end that is about to move would only write ends
@@ -850,22 +809,15 @@ __global__ __launch_bounds__(256) void amv_adpcm_settle_kernel(
     }
 }
 
-// The chain's own check, behind the last round: every chunk's bytes were coded from the start its state names (states are
-// replaced whole), so the stream is the sequential encoder's if and only if every chunk's start is its predecessor's end.
-// A chunk for which that does not hold -- none, unless the list handling above has a hole -- sends the stream down the
-// exhaustive route instead of out of the door.  And the BYTES are looked at, not only the states (round 5): the step index
-// in a chunk's header (adpcm.c:466, byte 2) is the start its nibbles were coded from by whichever lane wrote it last -- a chunk
-// two lanes coded at once from different readings of its predecessor's end (what the front sweep's `listed` bits are there
-// to prevent) can carry a header that is not its state's start, and a state still marked kPredicted has no bytes at all.
-// (every chunk has a header, also one of no samples: encode_chunk writes the eight bytes whenever the lane has a chunk)
+// The chain's own check, behind the last round (chain_broken: the states, and the bytes -- round 5).  A chunk it finds
+// wrong -- none, unless the list handling above has a hole, or the launched sweeps were all there was (the `nosettle`
+// knob) -- sends the stream down the exhaustive route instead of out of the door.  What a second coding of a chunk at the
+// same time would leave is what the front sweep's `listed` bits are there to prevent; a state still marked kPredicted
+// has no bytes at all.  (encode_chunk writes the eight header bytes whenever the lane has a chunk.)
 __global__ __launch_bounds__(256) void amv_adpcm_check_kernel(const uint2* __restrict__ state, uint32_t n, const uint8_t* __restrict__ blob,
                                                              const uint64_t* __restrict__ offs, uint32_t* __restrict__ need_map) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t start = state[i].x;
-    bool bad = i ? start != state[i - 1u].y : start != 0u;
-    bad = bad || (uint32_t)blob[offs[i] + 2u] != start;          // (start > 88 or kPredicted never equals a byte it wrote)
-    if (bad) *need_map = 1u;
+    note_broken(i < n && chain_broken(state, i, 0u, blob, offs), i, n, need_map);   // chunk 0: the encoder context starts zeroed
 }
 
 // ---- the exhaustive route (queued behind the other; every kernel of it leaves at once unless *need says otherwise) ---
@@ -897,19 +849,10 @@ __global__ __launch_bounds__(128) void amv_adpcm_chain_kernel(const uint8_t* __r
     __shared__ uint32_t s_map[kChainBlock * 24u];
     __shared__ uint32_t s_last;
     if (need && *need == 0u) return;
-    const uint32_t nb = gridDim.x;
-    {
-        const uint32_t c0 = blockIdx.x * kChainBlock, cnt = min(kChainBlock, n - c0);
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(map + (uint64_t)c0 * 96u);
-        for (uint32_t i = threadIdx.x; i < cnt * 24u; i += 128u) s_map[i] = src[i];
-        __syncthreads();
-        if (threadIdx.x < 89u) {
-            const uint8_t* m8 = reinterpret_cast<const uint8_t*>(s_map);
-            uint32_t v = threadIdx.x;
-            for (uint32_t c = 0; c < cnt; ++c) v = m8[c * 96u + v];
-            bmap[(uint64_t)blockIdx.x * 96u + threadIdx.x] = (uint8_t)v;
-        }
-    }
+    const uint32_t nb = gridDim.x, c0 = blockIdx.x * kChainBlock;
+    const uint32_t to = walk_maps<128u, false>(s_map, map + (uint64_t)c0 * 96u, min(kChainBlock, n - c0), 89u, threadIdx.x,
+                                               [](uint32_t, uint32_t, uint32_t) {});
+    if (threadIdx.x < 89u) bmap[(uint64_t)blockIdx.x * 96u + threadIdx.x] = (uint8_t)to;
     __threadfence();                                // this workgroup's map is out before it counts itself
     __syncthreads();
     if (threadIdx.x == 0) s_last = atomicAdd(done, 1u) + 1u == nb ? 1u : 0u;
@@ -917,20 +860,9 @@ __global__ __launch_bounds__(128) void amv_adpcm_chain_kernel(const uint8_t* __r
     if (!s_last) return;
     __threadfence();
     uint32_t v = 0;   // the encoder context starts zeroed
-    for (uint32_t t0 = 0; t0 < nb; t0 += kChainBlock) {
-        const uint32_t cnt = min(kChainBlock, nb - t0);
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(bmap + (uint64_t)t0 * 96u);
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < cnt * 24u; i += 128u) s_map[i] = peek(src + i);   // (other workgroups' stores: past this CU's L1)
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint8_t* m8 = reinterpret_cast<const uint8_t*>(s_map);
-            for (uint32_t c = 0; c < cnt; ++c) {
-                bstart[t0 + c] = (int32_t)v;
-                v = m8[c * 96u + v];
-            }
-        }
-    }
+    for (uint32_t t0 = 0; t0 < nb; t0 += kChainBlock)   // (other workgroups' stores: read past this CU's L1)
+        v = walk_maps<128u, true>(s_map, bmap + (uint64_t)t0 * 96u, min(kChainBlock, nb - t0), 1u, v,
+                                  [&](uint32_t c, uint32_t from, uint32_t) { bstart[t0 + c] = (int32_t)from; });
 }
 
 // Every chunk from the start index the maps give it: a workgroup walks from its block's start through the maps of the
@@ -945,21 +877,10 @@ __global__ __launch_bounds__(kEncodeBlock) void amv_adpcm_encode_mapped_kernel(
     __shared__ uint8_t s_start[kEncodeBlock];
     if (need && *need == 0u) return;
     const uint32_t c0 = blockIdx.x * kEncodeBlock, block = c0 / kChainBlock;
-    uint32_t v = (uint32_t)bstart[block];            // (thread 0's copy is the one that walks)
-    for (uint32_t t0 = block * kChainBlock; t0 <= c0; t0 += kEncodeBlock) {
-        const uint32_t cnt = min(kEncodeBlock, n - t0);
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(map + (uint64_t)t0 * 96u);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(s_raw);
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < cnt * 24u; i += kEncodeBlock) dst[i] = src[i];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (uint32_t c = 0; c < cnt; ++c) {
-                if (t0 == c0) s_start[c] = (uint8_t)v;
-                v = s_raw[c * 96u + v];
-            }
-        }
-    }
+    uint32_t v = (uint32_t)bstart[block];
+    for (uint32_t t0 = block * kChainBlock; t0 <= c0; t0 += kEncodeBlock)
+        v = walk_maps<kEncodeBlock, false>(reinterpret_cast<uint32_t*>(s_raw), map + (uint64_t)t0 * 96u, min(kEncodeBlock, n - t0), 1u, v,
+                                           [&](uint32_t c, uint32_t from, uint32_t) { if (t0 == c0) s_start[c] = (uint8_t)from; });
     __syncthreads();
     const uint32_t i = c0 + threadIdx.x;
     const bool live = i < n;
@@ -986,389 +907,6 @@ __global__ __launch_bounds__(kEncodeBlock) void amv_adpcm_encode_kernel(
                  s_tab, s_stage[threadIdx.x >> 6]);
 }
 
-// The reference's trellis search (adpcm_compress_trellis, adpcm.c:287-443, IMA branch; `-trellis N`): a beam of the
-// 2^N best decoder states (sorted by squared error, at most one per decoded sample value), three candidate nibbles
-// around the plain quantiser's choice for the better half of the beam and one for the rest (:333,373-385), the best
-// path frozen into the output every 128 samples (:405-417).  One lane per chunk; the beam lives in LDS
-// ([field][buffer][slot][lane]: a lane's accesses never meet another lane's bank), the back-pointers
-// (nibble | previous path << 4, 16 bits) in a workspace laid out [64 chunks][path][lane].
-//
-// trellis_chunk is the search of one chunk: cnt (even) samples at x from step index index0, the lane's beam at `beam`
-// (the workgroup's LDS + lane), its back-pointers at my_paths (entry e at my_paths[e * 64]).  kCode: the nibbles go to
-// d + 8 (the caller writes the header).  !kCode: the index the search ends on and nothing else -- that needs the
-// frontier alone, so no back-pointer is kept and no byte stored (d, my_paths unused).  Returns the end index.
-namespace {
-
-constexpr uint32_t trellis_lds_bytes(uint32_t trellis) { return 5u * 2u * (1u << trellis) * 64u * 4u; }
-
-// adpcm.c:465-466,479: le16 first sample, le16 step index, le32 sample count
-__device__ __forceinline__ void trellis_header(uint8_t* __restrict__ d, int first, int index0, uint32_t cnt) {
-    d[0] = (uint8_t)(first & 0xff); d[1] = (uint8_t)((first >> 8) & 0xff);
-    d[2] = (uint8_t)index0; d[3] = 0;
-    d[4] = (uint8_t)cnt; d[5] = (uint8_t)(cnt >> 8); d[6] = (uint8_t)(cnt >> 16); d[7] = (uint8_t)(cnt >> 24);
-}
-
-template <bool kCode>
-__device__ __forceinline__ int trellis_chunk(const int16_t* __restrict__ x, uint32_t cnt, int index0, uint8_t* __restrict__ d,
-                                             uint16_t* __restrict__ my_paths, uint32_t* __restrict__ beam, uint32_t F,
-                                             const uint32_t* __restrict__ s_step) {
-    // node fields: [field 0..3][buffer 0..1][slot][lane]; order of the two frontiers: [buffer][rank][lane]
-    uint32_t* const f_ssd = beam;
-    uint32_t* const f_smp = f_ssd + 2u * F * 64u;
-    uint32_t* const f_stp = f_smp + 2u * F * 64u;
-    uint32_t* const f_pth = f_stp + 2u * F * 64u;
-    uint32_t* const f_ord = f_pth + 2u * F * 64u;
-    auto at = [&](uint32_t* field, uint32_t buf, uint32_t slot) -> uint32_t& { return field[(buf * F + slot) * 64u]; };
-    constexpr uint32_t kNone = 0xffffffffu;
-    const int first = cnt ? x[0] : 0;
-    // nodes[0] = {ssd 0, path 0, step, sample1 = the chunk's first sample} in buffer 1 (:309-316)
-    at(f_ssd, 1, 0) = 0u; at(f_smp, 1, 0) = (uint32_t)first; at(f_stp, 1, 0) = (uint32_t)index0;
-    if (kCode) at(f_pth, 1, 0) = 0u;
-    for (uint32_t k = 0; k < F; ++k) { at(f_ord, 0, k) = k ? kNone : 0u; at(f_ord, 1, k) = kNone; }
-    uint32_t cur = 0;          // which order array holds the current frontier (its nodes live in buffer (i & 1) ^ 1)
-    uint32_t pathn = 0;
-    int froze = -1;
-    auto put_nibble = [&](uint32_t k, uint32_t nib) {   // sample k's nibble: high half of its byte first (:485-486)
-        uint8_t* b = d + 8u + (k >> 1);
-        *b = (k & 1u) ? (uint8_t)((*b & 0xf0u) | nib) : (uint8_t)((*b & 0x0fu) | (nib << 4));
-    };
-    for (uint32_t i = 0; i < cnt; ++i) {
-        const uint32_t nb = i & 1u, ob = nb ^ 1u, nxt = cur ^ 1u;
-        const int sample = x[i];
-        uint32_t made = 0, nn = 0;     // nodes allocated in buffer nb; entries of the next frontier
-        for (uint32_t k = 0; k < F; ++k) at(f_ord, nxt, k) = kNone;
-        for (uint32_t j = 0; j < F; ++j) {
-            const uint32_t src = at(f_ord, cur, j);
-            if (src == kNone) break;
-            const int range = j < F / 2u ? 1 : 0;                                   // :333
-            const int step = (int)at(f_stp, ob, src), st = (int)s_step[step];
-            const int predictor = (int)at(f_smp, ob, src);
-            const uint32_t base_ssd = at(f_ssd, ob, src), src_path = kCode ? at(f_pth, ob, src) : 0u;
-            const int div = (sample - predictor) * 4 / st;                         // :376
-            int nmin = min(max(div - range, -7), 6), nmax = min(max(div + range, -6), 7);
-            if (nmin <= 0) --nmin;                                                   // distinguish -0 from +0
-            if (nmax < 0) --nmax;
-            for (int nidx = nmin; nidx <= nmax; ++nidx) {
-                const uint32_t nibble = (uint32_t)(nidx < 0 ? 7 - nidx : nidx);
-                const int look = (nibble & 8u) ? -(int)(2u * (nibble & 7u) + 1u) : (int)(2u * (nibble & 7u) + 1u);
-                const int dec = clip16(predictor + (st * look) / 8);
-                const int diff = sample - dec;
-                const uint32_t ssd = base_ssd + (uint32_t)(diff * diff);
-                if (nn == F && ssd >= at(f_ssd, nb, at(f_ord, nxt, F - 1u))) continue;   // :342
-                bool dup = false;                                                    // one state per decoded value, :347-352
-                for (uint32_t k = 0; k < nn; ++k) dup = dup || (int)at(f_smp, nb, at(f_ord, nxt, k)) == dec;
-                if (dup) continue;
-                uint32_t k = 0;
-                while (k < nn && ssd >= at(f_ssd, nb, at(f_ord, nxt, k))) ++k;       // first rank it beats (:353-354)
-                uint32_t u;
-                if (nn == F) {
-                    u = at(f_ord, nxt, F - 1u);                                      // the worst one makes room, its path id stays
-                } else {
-                    u = made++;
-                    if (kCode) at(f_pth, nb, u) = pathn++;
-                    ++nn;
-                }
-                at(f_ssd, nb, u) = ssd;
-                at(f_stp, nb, u) = (uint32_t)clip_index(step + kImaIndexAdjust[nibble]);
-                at(f_smp, nb, u) = (uint32_t)dec;
-                if (kCode) my_paths[(uint64_t)at(f_pth, nb, u) * 64u] = (uint16_t)(nibble | (src_path << 4));
-                for (uint32_t m = nn - 1u; m > k; --m) at(f_ord, nxt, m) = at(f_ord, nxt, m - 1u);   // memmove, :365
-                at(f_ord, nxt, k) = u;
-            }
-        }
-        cur = nxt;
-        const uint32_t best = at(f_ord, cur, 0);
-        if (at(f_ssd, nb, best) > (1u << 28)) {                                     // :398-402
-            const uint32_t off = at(f_ssd, nb, best);
-            for (uint32_t j = 1; j < F; ++j) {
-                const uint32_t q = at(f_ord, cur, j);
-                if (q == kNone) break;
-                at(f_ssd, nb, q) -= off;
-            }
-            at(f_ssd, nb, best) = 0u;
-        }
-        if ((int)i == froze + 128) {                                                // :405-417
-            if (kCode) {
-                uint32_t p = at(f_pth, nb, best);
-                for (int k = (int)i; k > froze; --k) {
-                    const uint32_t e = my_paths[(uint64_t)p * 64u];
-                    put_nibble((uint32_t)k, e & 15u);
-                    p = e >> 4;
-                }
-            }
-            froze = (int)i;
-            pathn = 0;
-            for (uint32_t j = 1; j < F; ++j) at(f_ord, cur, j) = kNone;
-        }
-    }
-    if (cnt == 0u) return index0;
-    const uint32_t nb = (cnt - 1u) & 1u, best = at(f_ord, cur, 0);
-    if (kCode) {
-        uint32_t p = at(f_pth, nb, best);
-        for (int k = (int)cnt - 1; k > froze; --k) {
-            const uint32_t e = my_paths[(uint64_t)p * 64u];
-            put_nibble((uint32_t)k, e & 15u);
-            p = e >> 4;
-        }
-    }
-    return (int)at(f_stp, nb, best);                                                 // :429
-}
-
-// chunk i of a stream coded from `start` (0..88): header, nibbles; returns the end index
-__device__ __forceinline__ int trellis_code(const int16_t* __restrict__ pcm, const uint64_t* __restrict__ pcm_offs,
-                                            const uint32_t* __restrict__ nsamp, uint8_t* __restrict__ blob,
-                                            const uint64_t* __restrict__ offs, uint32_t i, int start, uint16_t* __restrict__ my_paths,
-                                            uint32_t* __restrict__ beam, uint32_t F, const uint32_t* __restrict__ s_step) {
-    const int16_t* x = pcm + pcm_offs[i];
-    const uint32_t cnt = nsamp[i] & ~1u;
-    uint8_t* d = blob + offs[i];
-    trellis_header(d, cnt ? x[0] : 0, start, cnt);
-    return trellis_chunk<true>(x, cnt, start, d, my_paths, beam, F, s_step);
-}
-
-// the back-pointers of a workgroup's 64 lanes: [workgroup of the LAUNCH][path][lane] -- by position in the launch, not by
-// chunk, so a sweep over a short list needs the first workgroups' space only
-__device__ __forceinline__ uint16_t* trellis_paths(uint16_t* __restrict__ paths, uint32_t F) {
-    return paths + (uint64_t)blockIdx.x * (F * 128u) * 64u + threadIdx.x;
-}
-
-}  // namespace
-
-// Chunks are independent: the step index comes in per chunk and goes out per chunk.
-__global__ __launch_bounds__(64) void amv_adpcm_trellis_kernel(
-    const int16_t* __restrict__ pcm, const uint64_t* __restrict__ pcm_offs, const uint32_t* __restrict__ nsamp, uint32_t n,
-    const int32_t* __restrict__ step_in, uint32_t trellis, uint8_t* __restrict__ blob, const uint64_t* __restrict__ offs,
-    int32_t* __restrict__ step_out, uint16_t* __restrict__ paths) {
-    extern __shared__ uint32_t s_trellis[];
-    __shared__ uint32_t s_step[96];
-    load_steps(s_step);
-    const uint32_t F = 1u << trellis, lane = threadIdx.x;
-    const uint32_t i_chunk = blockIdx.x * 64u + lane;
-    if (i_chunk >= n) return;                         // (no barrier follows)
-    const int end = trellis_code(pcm, pcm_offs, nsamp, blob, offs, i_chunk, clip_index(step_in[i_chunk]), trellis_paths(paths, F),
-                                 s_trellis + lane, F, s_step);
-    if (step_out) step_out[i_chunk] = end;
-}
-
-// ---- the trellis stream: the step index chained on the device ---------------------------------------------------------
-// The chunks of a call are one stream (adpcm.c:461-498 with -trellis): chunk 0 starts from the index handed in, chunk i
-// from the index chunk i - 1 ends on; nothing else crosses a chunk boundary (:464 takes the predictor from the chunk's
-// first sample).  The plain chain's scheme, with launches as the only synchronisation -- a trellis chunk is milliseconds
-// of one lane's time, so what an in-launch hand-off could save does not show:
-//   guess   every chunk coded from a guessed start (chunk 0: the given index; the others: the ends-only search over the
-//           end of the chunk before, adpcm_trellis_tail), state[i] = {start used, end reached};
-//   link    lists the chunks whose predecessor ended elsewhere than they assumed;
-//   sweep   (a fixed number of launches) one lane per listed chunk: coded again from its predecessor's end if that is not
-//           the start it used; its successor is listed if its own end moved.  An empty list ends the launch at once;
-//   link    again, as the check: the first chunk whose start is not its predecessor's end -- everything before it is
-//           final, whatever the data -- sends the chunks from there on down the fall-back:
-//   map     the ends-only search of each of those chunks from all 89 starts (a lane per (chunk, start)),
-//   walk    one workgroup composes the maps along the stream from the last final end: state[i] = the true {start, end},
-//   recode  those chunks coded from their true starts.
-// A lane of a sweep reads its predecessor's end while another lane of the same launch may be replacing it: it gets the
-// old end or the new one, never waits, and is listed again by that lane if the end did move -- so it is coded from the
-// new end in the next sweep unless it already was.  A chunk is listed by its predecessor alone: no list holds it twice,
-// and only the lane that holds it writes its state and its bytes.
-__global__ __launch_bounds__(64) void amv_adpcm_trellis_guess_kernel(
-    const int16_t* __restrict__ pcm, const uint64_t* __restrict__ pcm_offs, const uint32_t* __restrict__ nsamp, uint32_t n,
-    uint32_t first_index, uint32_t trellis, uint8_t* __restrict__ blob, const uint64_t* __restrict__ offs, uint2* __restrict__ state,
-    uint16_t* __restrict__ paths) {
-    extern __shared__ uint32_t s_trellis[];
-    __shared__ uint32_t s_step[96];
-    load_steps(s_step);
-    const uint32_t F = 1u << trellis, lane = threadIdx.x;
-    const uint32_t i = blockIdx.x * 64u + lane;
-    if (i >= n) return;
-    int start = (int)first_index;
-    if (i > 0u) {
-        const uint32_t mp = nsamp[i - 1u] & ~1u, tail = adpcm_trellis_tail(mp);
-        start = trellis_chunk<false>(pcm + pcm_offs[i - 1u] + (mp - tail), tail, 0, nullptr, nullptr, s_trellis + lane, F, s_step);
-    }
-    const int end = trellis_code(pcm, pcm_offs, nsamp, blob, offs, i, start, trellis_paths(paths, F), s_trellis + lane, F, s_step);
-    state[i] = make_uint2((uint32_t)start, (uint32_t)end);
-}
-
-// The chunks whose start is not their predecessor's end (chunk 0: the index handed in): listed (list != nullptr), and
-// *need = n - the first of them (need != nullptr; zero before: the stream is the sequential encoder's).  force: the
-// test knob's fall-back at once -- nothing is coded yet, so all n chunks are the fall-back's.
-__global__ __launch_bounds__(256) void amv_adpcm_trellis_link_kernel(const uint2* __restrict__ state, uint32_t n, uint32_t first_index,
-                                                                    uint32_t* __restrict__ list, uint32_t* __restrict__ count,
-                                                                    uint32_t* __restrict__ need, uint32_t force) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (force) {
-        if (i == 0u) *need = n;
-        return;
-    }
-    const bool bad = i < n && state[i].x != (i ? state[i - 1u].y : first_index);
-    const uint64_t mask = __ballot(bad);
-    if (!mask) return;
-    const uint32_t lane = threadIdx.x & 63u;
-    if (list) {
-        uint32_t base = 0;
-        if (lane == 0u) base = atomicAdd(count, (uint32_t)__popcll(mask));
-        base = (uint32_t)__shfl((int)base, 0);
-        if (bad) list[base + (uint32_t)__popcll(mask & ((1ull << lane) - 1ull))] = i;
-    }
-    if (need && bad && (mask & ((1ull << lane) - 1ull)) == 0ull) atomicMax(need, n - i);   // the wave's first
-}
-
-__global__ __launch_bounds__(64) void amv_adpcm_trellis_sweep_kernel(
-    const int16_t* __restrict__ pcm, const uint64_t* __restrict__ pcm_offs, const uint32_t* __restrict__ nsamp, uint32_t n,
-    uint32_t trellis, uint8_t* __restrict__ blob, const uint64_t* __restrict__ offs, uint2* __restrict__ state,
-    const uint32_t* __restrict__ list_in, const uint32_t* __restrict__ count_in, uint32_t* __restrict__ list_out,
-    uint32_t* __restrict__ count_out, uint32_t* __restrict__ recoded, uint16_t* __restrict__ paths) {
-    extern __shared__ uint32_t s_trellis[];
-    __shared__ uint32_t s_step[96];
-    const uint32_t count = *count_in;
-    if (blockIdx.x * 64u >= count) return;
-    load_steps(s_step);
-    const uint32_t F = 1u << trellis, lane = threadIdx.x;
-    if (blockIdx.x * 64u + lane >= count) return;
-    const uint32_t i = list_in[blockIdx.x * 64u + lane];           // (never chunk 0: nobody lists it)
-    uint32_t* sw = reinterpret_cast<uint32_t*>(state);
-    const uint32_t start = peek(sw + 2u * (i - 1u) + 1u);
-    if (start == sw[2u * i]) return;                                // coded from there already
-    const uint32_t was = sw[2u * i + 1u];
-    const uint32_t end = (uint32_t)trellis_code(pcm, pcm_offs, nsamp, blob, offs, i, (int)start, trellis_paths(paths, F), s_trellis + lane,
-                                                F, s_step);
-    sw[2u * i] = start;
-    poke(sw + 2u * i + 1u, end);
-    atomicAdd(recoded, 1u);
-    if (end != was && i + 1u < n) list_out[atomicAdd(count_out, 1u)] = i + 1u;
-}
-
-// the fall-back (every kernel of it leaves at once while *need is zero): chunks n - *need .. n - 1
-__global__ __launch_bounds__(64) void amv_adpcm_trellis_map_kernel(
-    const int16_t* __restrict__ pcm, const uint64_t* __restrict__ pcm_offs, const uint32_t* __restrict__ nsamp, uint32_t n,
-    uint32_t trellis, uint8_t* __restrict__ map /* [n][96] */, const uint32_t* __restrict__ need) {
-    extern __shared__ uint32_t s_trellis[];
-    __shared__ uint32_t s_step[96];
-    const uint32_t left = *need;
-    if (left == 0u) return;
-    load_steps(s_step);
-    const uint32_t F = 1u << trellis, lo = n - left;
-    const uint64_t pairs = (uint64_t)left * 89u;
-    for (uint64_t pair = (uint64_t)blockIdx.x * 64u + threadIdx.x; pair < pairs; pair += (uint64_t)gridDim.x * 64u) {
-        const uint32_t i = lo + (uint32_t)(pair / 89u), s = (uint32_t)(pair % 89u);
-        const int end = trellis_chunk<false>(pcm + pcm_offs[i], nsamp[i] & ~1u, (int)s, nullptr, nullptr, s_trellis + threadIdx.x, F, s_step);
-        map[(uint64_t)i * 96u + s] = (uint8_t)end;
-    }
-}
-
-// one workgroup: the maps of kChainBlock chunks at a time into LDS, one lane walks them
-__global__ __launch_bounds__(128) void amv_adpcm_trellis_walk_kernel(const uint8_t* __restrict__ map, uint32_t n, uint32_t first_index,
-                                                                    uint2* __restrict__ state, const uint32_t* __restrict__ need) {
-    __shared__ uint32_t s_map[kChainBlock * 24u];
-    const uint32_t left = *need;
-    if (left == 0u) return;
-    const uint32_t lo = n - left;
-    uint32_t v = lo ? state[lo - 1u].y : first_index;   // (thread 0's copy is the one that walks)
-    for (uint32_t t0 = lo; t0 < n; t0 += kChainBlock) {
-        const uint32_t cnt = min(kChainBlock, n - t0);
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(map + (uint64_t)t0 * 96u);
-        __syncthreads();
-        for (uint32_t k = threadIdx.x; k < cnt * 24u; k += 128u) s_map[k] = src[k];
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint8_t* m8 = reinterpret_cast<const uint8_t*>(s_map);
-            for (uint32_t c = 0; c < cnt; ++c) {
-                const uint32_t e = m8[c * 96u + v];
-                state[t0 + c] = make_uint2(v, e);
-                v = e;
-            }
-        }
-    }
-}
-
-__global__ __launch_bounds__(64) void amv_adpcm_trellis_recode_kernel(
-    const int16_t* __restrict__ pcm, const uint64_t* __restrict__ pcm_offs, const uint32_t* __restrict__ nsamp, uint32_t n,
-    uint32_t trellis, uint8_t* __restrict__ blob, const uint64_t* __restrict__ offs, const uint2* __restrict__ state,
-    const uint32_t* __restrict__ need, uint16_t* __restrict__ paths) {
-    extern __shared__ uint32_t s_trellis[];
-    __shared__ uint32_t s_step[96];
-    const uint32_t left = *need;
-    if (blockIdx.x * 64u >= left) return;
-    load_steps(s_step);
-    const uint32_t F = 1u << trellis, lane = threadIdx.x;
-    if (blockIdx.x * 64u + lane >= left) return;
-    const uint32_t i = n - left + blockIdx.x * 64u + lane;
-    trellis_code(pcm, pcm_offs, nsamp, blob, offs, i, (int)state[i].x, trellis_paths(paths, F), s_trellis + lane, F, s_step);
-}
-
-__global__ __launch_bounds__(256) void amv_adpcm_trellis_ends_kernel(const uint2* __restrict__ state, uint32_t n, int32_t* __restrict__ step_out) {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    if (i < n) step_out[i] = (int32_t)state[i].y;
-}
-
-// workspace of launch_adpcm_trellis: bytes for n chunks
-uint64_t adpcm_trellis_workspace(uint32_t n, uint32_t trellis) {
-    return (uint64_t)((n + 63u) / 64u) * 64u * ((1u << trellis) * 128u) * sizeof(uint16_t);
-}
-
-// the search kernels' LDS is dynamic and above the 64 KB a kernel gets unasked at N = 5: raised once per device and kernel
-template <typename K>
-static bool trellis_lds_raised(K kernel, std::atomic<uint64_t>& raised) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (raised.load() & (1ull << (dev & 63))) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)trellis_lds_bytes(5)) !=
-        hipSuccess)
-        return false;
-    raised.fetch_or(1ull << (dev & 63));
-    return true;
-}
-
-bool launch_adpcm_trellis(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, const int32_t* step_in,
-                          uint32_t trellis, uint8_t* blob, const uint64_t* offs, int32_t* step_out, uint16_t* paths, hipStream_t s) {
-    if (n == 0) return true;
-    static std::atomic<uint64_t> raised{0};
-    if (!trellis_lds_raised(amv_adpcm_trellis_kernel, raised)) return false;
-    hipLaunchKernelGGL(amv_adpcm_trellis_kernel, dim3((n + 63) / 64), dim3(64), trellis_lds_bytes(trellis), s, pcm, pcm_offs, nsamp, n,
-                       step_in, trellis, blob, offs, step_out, paths);
-    return true;
-}
-
-// The trellis stream.  paths: adpcm_trellis_workspace(n, trellis) bytes; work: adpcm_trellis_chain_plan(n).bytes.
-// sweeps < 0: the fall-back at once.  The launches are the same whatever n and the samples: a memset, guess, link,
-// `sweeps` sweeps, link, map, walk, recode (and the copy of the ends when step_out is given).
-bool launch_adpcm_trellis_stream(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, uint32_t first_index,
-                                 uint32_t trellis, uint8_t* blob, const uint64_t* offs, int32_t* step_out, uint16_t* paths, void* work,
-                                 int sweeps, hipStream_t s) {
-    if (n == 0) return true;
-    static std::atomic<uint64_t> raised[4];
-    if (!trellis_lds_raised(amv_adpcm_trellis_guess_kernel, raised[0]) || !trellis_lds_raised(amv_adpcm_trellis_sweep_kernel, raised[1]) ||
-        !trellis_lds_raised(amv_adpcm_trellis_map_kernel, raised[2]) || !trellis_lds_raised(amv_adpcm_trellis_recode_kernel, raised[3]))
-        return false;
-    const TrellisChainPlan p = adpcm_trellis_chain_plan(n);
-    uint8_t* w = static_cast<uint8_t*>(work);
-    uint2* state = reinterpret_cast<uint2*>(w + p.state);
-    uint32_t* list[2] = {reinterpret_cast<uint32_t*>(w + p.list[0]), reinterpret_cast<uint32_t*>(w + p.list[1])};
-    uint32_t* count = reinterpret_cast<uint32_t*>(w + p.counters);
-    uint32_t* recoded = count + 64, *need = count + kTrellisNeedWord;
-    uint8_t* map = w + p.map;
-    if (hipMemsetAsync(count, 0, kTrellisCounterWords * 4u, s) != hipSuccess) return false;   // (nothing has been queued)
-    const uint32_t lds = trellis_lds_bytes(trellis), groups = (n + 63u) / 64u, links = (n + 255u) / 256u;
-    if (sweeps >= 0) {
-        if ((uint32_t)sweeps > kTrellisSweepsMost) sweeps = (int)kTrellisSweepsMost;
-        hipLaunchKernelGGL(amv_adpcm_trellis_guess_kernel, dim3(groups), dim3(64), lds, s, pcm, pcm_offs, nsamp, n, first_index, trellis, blob,
-                           offs, state, paths);
-        hipLaunchKernelGGL(amv_adpcm_trellis_link_kernel, dim3(links), dim3(256), 0, s, state, n, first_index, list[0], count, nullptr, 0u);
-        for (uint32_t k = 0; k < (uint32_t)sweeps; ++k)
-            hipLaunchKernelGGL(amv_adpcm_trellis_sweep_kernel, dim3(groups), dim3(64), lds, s, pcm, pcm_offs, nsamp, n, trellis, blob, offs,
-                               state, list[k & 1u], count + k, list[(k + 1u) & 1u], count + k + 1u, recoded + k, paths);
-    }
-    hipLaunchKernelGGL(amv_adpcm_trellis_link_kernel, dim3(links), dim3(256), 0, s, state, n, first_index, nullptr, nullptr, need,
-                       sweeps < 0 ? 1u : 0u);
-    const uint64_t map_groups = ((uint64_t)n * 89u + 63u) / 64u;
-    hipLaunchKernelGGL(amv_adpcm_trellis_map_kernel, dim3((uint32_t)(map_groups < 8192u ? map_groups : 8192u)), dim3(64), lds, s, pcm, pcm_offs,
-                       nsamp, n, trellis, map, need);
-    hipLaunchKernelGGL(amv_adpcm_trellis_walk_kernel, dim3(1), dim3(128), 0, s, map, n, first_index, state, need);
-    hipLaunchKernelGGL(amv_adpcm_trellis_recode_kernel, dim3(groups), dim3(64), lds, s, pcm, pcm_offs, nsamp, n, trellis, blob, offs, state,
-                       need, paths);
-    if (step_out) hipLaunchKernelGGL(amv_adpcm_trellis_ends_kernel, dim3(links), dim3(256), 0, s, state, n, step_out);
-    return true;
-}
-
 void launch_adpcm_decode(const uint8_t* blob, uint64_t blob_bytes, const uint64_t* offs,
                          const uint32_t* lens, uint32_t n, int16_t* pcm, const uint64_t* pcm_offs,
                          int32_t* final_state, hipStream_t s) {
@@ -1380,27 +918,6 @@ void launch_adpcm_decode(const uint8_t* blob, uint64_t blob_bytes, const uint64_
 void launch_adpcm_wav_encode(const int16_t* samples, int groups, int32_t* state, uint8_t* frame, hipStream_t s) {
     hipLaunchKernelGGL(amv_adpcm_wav_encode_kernel, dim3(1), dim3(64), 0, s, samples, groups, state, frame);
 }
-
-void launch_adpcm_map(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n,
-                      uint8_t* map, int32_t* bstart, uint32_t* done, const uint32_t* need, hipStream_t s) {
-    // map: (n + nb) * 96 bytes, bstart: nb words, nb = adpcm_chain_blocks(n); *done == 0
-    if (n == 0) return;
-    const uint32_t nb = adpcm_chain_blocks(n);
-    uint8_t* bmap = map + (uint64_t)n * 96u;
-    const uint64_t groups = ((uint64_t)n * 89u + kEncodeBlock - 1u) / kEncodeBlock;
-    hipLaunchKernelGGL(amv_adpcm_map_kernel, dim3((uint32_t)(groups < 4096u ? groups : 4096u)), dim3(kEncodeBlock), 0, s, pcm, pcm_offs,
-                       nsamp, n, map, need);
-    hipLaunchKernelGGL(amv_adpcm_chain_kernel, dim3(nb), dim3(128), 0, s, map, n, bmap, bstart, done, need);
-}
-
-void launch_adpcm_encode_mapped(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, const uint8_t* map,
-                                const int32_t* bstart, uint8_t* blob, const uint64_t* offs, const uint32_t* need, hipStream_t s) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(amv_adpcm_encode_mapped_kernel, dim3((n + kEncodeBlock - 1u) / kEncodeBlock), dim3(kEncodeBlock), 0, s, pcm,
-                       pcm_offs, nsamp, n, map, bstart, blob, offs, need);
-}
-
-uint32_t adpcm_chain_blocks(uint32_t n) { return (n + kChainBlock - 1u) / kChainBlock; }
 
 void adpcm_quotient_table(float out[89]) {
     for (int i = 0; i < 89; ++i) out[i] = kAdpcmHost.rcp[i];
@@ -1414,41 +931,56 @@ void launch_adpcm_encode(const int16_t* pcm, const uint64_t* pcm_offs, const uin
                        nsamp, n, step_in, blob, offs, need);
 }
 
-// The guessed-start route.  work: adpcm_chain_workspace(n) bytes = state[n] (uint2), two lists of n words, 64 words of
-// counters (word 63 is the flag launch_adpcm_map / launch_adpcm_encode are given as `need`) and a bit per chunk for the
-// front sweep; counters and bits are zeroed here.
-static uint64_t chain_zeroed_bytes(uint32_t n) { return 256u + (((uint64_t)n + 31u) / 32u) * 4u; }
-uint64_t adpcm_chain_workspace(uint32_t n) { return (uint64_t)n * 16u + chain_zeroed_bytes(n); }
-
-const uint32_t* launch_adpcm_chain(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, uint8_t* blob,
-                                   const uint64_t* offs, void* work, uint32_t sweeps, bool settle, hipStream_t s) {
-    uint2* state = static_cast<uint2*>(work);
-    uint32_t* list[2] = {reinterpret_cast<uint32_t*>(state + n), reinterpret_cast<uint32_t*>(state + n) + n};
-    uint32_t* count = list[1] + n;                   // [0 .. sweeps + 2]: one per list generation; [62]: launch_adpcm_map's `done`; [63]: the flag
-    if (sweeps > 59u) sweeps = 59u;
-    if (hipMemsetAsync(count, 0, chain_zeroed_bytes(n), s) != hipSuccess) return nullptr;   // (the caller reports it: nothing has been queued)
-    hipLaunchKernelGGL(amv_adpcm_guess_kernel, dim3((n + kEncodeBlock - 1u) / kEncodeBlock), dim3(kEncodeBlock), 0, s, pcm, pcm_offs, nsamp, n,
-                       blob, offs, state, list[0], count);
-    if (n > 1u) {
-        // sweep k's list is a fraction of the one before; the grid is sized for the first and strides if it must
-        uint32_t grid = (n + kEncodeBlock - 1u) / kEncodeBlock;
-        for (uint32_t k = 0; k < sweeps; ++k) {
-            hipLaunchKernelGGL(amv_adpcm_sweep_kernel, dim3(grid), dim3(kEncodeBlock), 0, s, pcm, pcm_offs, nsamp, n, blob, offs, state,
-                               list[k & 1u], count + k, list[(k + 1u) & 1u], count + k + 1u);
-            grid = grid > 256u ? (grid + 1u) / 2u : grid;
+// The plain encoder's stream: the step index carried from chunk to chunk.  work: adpcm_plain_chain_plan(n).bytes.
+// sweeps < 0: the exhaustive route at once; settle == false: a test knob -- the chain is left where its launched sweeps
+// got it, and the check has to notice.  The launches: the memset of the plan's zero span; guess, `sweeps` sweeps, front,
+// settle, check (sweeps >= 0); map, chain, encode_mapped -- which leave at once unless the chain's flag is up (or
+// sweeps < 0).  Only enqueues; false: refused before anything was queued.
+bool launch_adpcm_stream(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, uint8_t* blob, const uint64_t* offs,
+                         void* work, int sweeps, bool settle, hipStream_t s) {
+    if (n == 0) return true;
+    const ChainPlan p = adpcm_plain_chain_plan(n);
+    uint8_t* w = static_cast<uint8_t*>(work);
+    uint2* state = reinterpret_cast<uint2*>(w + p.state);
+    uint32_t* list[2] = {reinterpret_cast<uint32_t*>(w + p.list[0]), reinterpret_cast<uint32_t*>(w + p.list[1])};
+    uint32_t* count = reinterpret_cast<uint32_t*>(w + p.counters);
+    uint32_t* flag = count + kChainWordNeed;
+    if (hipMemsetAsync(w + p.zero, 0, p.zero_bytes, s) != hipSuccess) return false;   // (nothing has been queued)
+    const uint32_t groups = (n + kEncodeBlock - 1u) / kEncodeBlock;
+    if (sweeps >= 0) {
+        const uint32_t k_front = (uint32_t)sweeps > kAdpcmSweepsMost ? kAdpcmSweepsMost : (uint32_t)sweeps;
+        hipLaunchKernelGGL(amv_adpcm_guess_kernel, dim3(groups), dim3(kEncodeBlock), 0, s, pcm, pcm_offs, nsamp, n, blob, offs, state, list[0],
+                           count + chain_word_list(0));
+        if (n > 1u) {
+            // sweep k's list is a fraction of the one before; the grid is sized for the first and strides if it must
+            uint32_t grid = groups;
+            for (uint32_t k = 0; k < k_front; ++k) {
+                hipLaunchKernelGGL(amv_adpcm_sweep_kernel, dim3(grid), dim3(kEncodeBlock), 0, s, pcm, pcm_offs, nsamp, n, blob, offs, state,
+                                   list[k & 1u], count + chain_word_list(k), list[(k + 1u) & 1u], count + chain_word_list(k + 1u));
+                grid = grid > 256u ? (grid + 1u) / 2u : grid;
+            }
+            // one sweep that looks four chunks ahead of every head (a plain sweep while the list is still long), then the rest
+            if (settle) {
+                hipLaunchKernelGGL(amv_adpcm_front_kernel, dim3(kFrontMost), dim3(kFrontThreads), 0, s, pcm, pcm_offs, nsamp, n, blob, offs,
+                                   state, list[k_front & 1u], count + chain_word_list(k_front), list[(k_front + 1u) & 1u],
+                                   count + chain_word_list(k_front + 1u), reinterpret_cast<uint32_t*>(w + p.bits), flag);
+                hipLaunchKernelGGL(amv_adpcm_settle_kernel, dim3(1), dim3(256), 0, s, pcm, pcm_offs, nsamp, n, blob, offs, state,
+                                   list[(k_front + 1u) & 1u], count + chain_word_list(k_front + 1u), list[k_front & 1u],
+                                   count + chain_word_list(k_front + 2u), flag);
+            }
+            hipLaunchKernelGGL(amv_adpcm_check_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, state, n, blob, offs, flag);
         }
-        // one sweep that looks four chunks ahead of every head (a plain sweep while the list is still long), then the rest
-        if (settle) {
-            hipLaunchKernelGGL(amv_adpcm_front_kernel, dim3(kFrontMost), dim3(kFrontThreads), 0, s, pcm, pcm_offs, nsamp, n, blob, offs,
-                               state, list[sweeps & 1u], count + sweeps, list[(sweeps + 1u) & 1u], count + sweeps + 1u, count + 64,
-                               count + 63);
-            hipLaunchKernelGGL(amv_adpcm_settle_kernel, dim3(1), dim3(256), 0, s, pcm, pcm_offs, nsamp, n, blob, offs, state,
-                               list[(sweeps + 1u) & 1u], count + sweeps + 1u, list[sweeps & 1u], count + sweeps + 2u, count + 63);
-        }
-        // (settle == false: a test knob -- the chain is left where its launched sweeps got it, and the check has to notice)
-        hipLaunchKernelGGL(amv_adpcm_check_kernel, dim3((n + 255u) / 256u), dim3(256), 0, s, state, n, blob, offs, count + 63);
     }
-    return count + 63;
+    const uint32_t* need = sweeps >= 0 ? flag : nullptr;   // (nullptr: run)
+    uint8_t* map = w + p.map;
+    int32_t* bstart = reinterpret_cast<int32_t*>(w + p.bstart);
+    const uint64_t pairs = ((uint64_t)n * 89u + kEncodeBlock - 1u) / kEncodeBlock;
+    hipLaunchKernelGGL(amv_adpcm_map_kernel, dim3((uint32_t)(pairs < 4096u ? pairs : 4096u)), dim3(kEncodeBlock), 0, s, pcm, pcm_offs, nsamp, n,
+                       map, need);
+    hipLaunchKernelGGL(amv_adpcm_chain_kernel, dim3(p.blocks), dim3(128), 0, s, map, n, w + p.bmap, bstart, count + kChainWordDone, need);
+    hipLaunchKernelGGL(amv_adpcm_encode_mapped_kernel, dim3(groups), dim3(kEncodeBlock), 0, s, pcm, pcm_offs, nsamp, n, map, bstart, blob, offs,
+                       need);
+    return true;
 }
 
 }  // namespace amv

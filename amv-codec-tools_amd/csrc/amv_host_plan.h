@@ -497,24 +497,54 @@ AMV_HD inline uint32_t adpcm_trellis_tail(uint32_t m) { return m <= 256u ? m : m
 // takes k sweeps more, and streams with a quarter of their chunks that short needed up to 11.  A sweep over an empty
 // list is a launch that leaves at once, so the count is generous; past it the fall-back writes the bytes.
 constexpr uint32_t kTrellisSweeps = 16;
-constexpr uint32_t kTrellisSweepsMost = 60;
 
-// its chain workspace for n chunks: state[n] = {start, end}, two lists of n chunk numbers, 192 words of counters
-// ([0..63]: entries of list generation k, [64..127]: chunks coded again by sweep k, [128]: chunks the fall-back takes
-// on, counted from the stream's end) and the fall-back's maps [n][96]: where each of the 89 starts ends
-constexpr uint32_t kTrellisCounterWords = 192, kTrellisNeedWord = 128;
-struct TrellisChainPlan {
-    uint64_t state, list[2], counters, map, bytes;   // byte offsets, and the whole
+// The chain workspace of both encoders (launch_adpcm_stream, launch_adpcm_trellis_stream), n chunks:
+//   state[n]       {start the chunk's bytes were coded from, end reached}, exchanged as one 64-bit word;
+//   list[2][n]     chunk numbers, the two generations in turn;
+//   counters       kChainCounterWords words, named below;
+//   bits           (plain route) a bit per chunk: listed already by the front sweep;
+//   map[n][96]     the exhaustive route's maps: where each of the 89 starts of a chunk ends;
+//   bmap, bstart   (plain route) the composed map and the start index of every block of kChainBlock chunks.
+// Counters and bits are what a call zeroes, and they lie together: [zero, zero + zero_bytes), whole 16-byte pieces from
+// a 16-byte boundary of the buffer, so that the memset is one fill.
+constexpr uint32_t kChainBlock = 256;        // chunks whose maps one workgroup composes through LDS (24 KB)
+constexpr uint32_t kChainGenerations = 64;   // list generations (and sweeps) that have a counter word of their own
+constexpr uint32_t kChainCounterWords = 2u * kChainGenerations + 4u;   // (need, done and two spare words)
+constexpr uint32_t chain_word_list(uint32_t k) { return k; }                           // entries of list generation k
+constexpr uint32_t chain_word_recoded(uint32_t k) { return kChainGenerations + k; }    // chunks coded again by sweep k (trellis)
+// not zero: the stream is not the sequential encoder's yet, the exhaustive route runs (the chunks it takes on, counted
+// from the stream's end -- the trellis fall-back recodes those alone)
+constexpr uint32_t kChainWordNeed = 2u * kChainGenerations;
+constexpr uint32_t kChainWordDone = kChainWordNeed + 1u;   // workgroups of the plain route's chain kernel that have written their map
+// most launched sweeps.  Sweep k reads generation k and appends to k + 1; the plain route's front and settle kernels
+// behind its sweeps take two generations more
+constexpr uint32_t kAdpcmSweepsMost = 59, kTrellisSweepsMost = 60;
+static_assert(kAdpcmSweepsMost + 2u < kChainGenerations && kTrellisSweepsMost + 1u < kChainGenerations, "a counter word per generation");
+static_assert(kTrellisSweeps <= kTrellisSweepsMost, "the default is a permitted count");
+
+struct ChainPlan {
+    uint64_t state, list[2], counters, bits, map, bmap, bstart;   // byte offsets
+    uint64_t zero, zero_bytes;                                    // the span a call zeroes
+    uint64_t bytes;                                               // the whole
+    uint32_t blocks;                                              // blocks of kChainBlock chunks (0: the trellis route)
 };
-inline TrellisChainPlan adpcm_trellis_chain_plan(uint32_t n) {
-    TrellisChainPlan p;
+inline ChainPlan adpcm_chain_plan(uint32_t n, bool blocked) {
+    ChainPlan p;
+    p.blocks = blocked ? (uint32_t)(((uint64_t)n + kChainBlock - 1u) / kChainBlock) : 0u;
     p.state = 0;
     p.list[0] = (uint64_t)n * 8u;
     p.list[1] = p.list[0] + (uint64_t)n * 4u;
     p.counters = p.list[1] + (uint64_t)n * 4u;
-    p.map = p.counters + kTrellisCounterWords * 4u;
-    p.bytes = p.map + (uint64_t)n * 96u;
+    p.bits = p.counters + kChainCounterWords * 4u;
+    p.map = p.bits + (blocked ? (((uint64_t)n + 127u) / 128u) * 16u : 0u);
+    p.bmap = p.map + (uint64_t)n * 96u;
+    p.bstart = p.bmap + (uint64_t)p.blocks * 96u;
+    p.bytes = p.bstart + (uint64_t)p.blocks * 4u;
+    p.zero = p.counters;
+    p.zero_bytes = p.map - p.counters;
     return p;
 }
+inline ChainPlan adpcm_plain_chain_plan(uint32_t n) { return adpcm_chain_plan(n, true); }
+inline ChainPlan adpcm_trellis_chain_plan(uint32_t n) { return adpcm_chain_plan(n, false); }
 
 }  // namespace amv

@@ -261,21 +261,15 @@ void launch_audio_resample(const AudioResampleArgs& a, uint32_t blocks, hipStrea
 void launch_adpcm_decode(const uint8_t* blob, uint64_t blob_bytes, const uint64_t* offs,
                          const uint32_t* lens, uint32_t n, int16_t* pcm, const uint64_t* pcm_offs,
                          int32_t* final_state, hipStream_t s);
-// The reference's step_index carry (adpcm.c:461-498) without a serial pass over the stream.  launch_adpcm_chain: every
-// chunk coded from a guessed start, then `sweeps` launches + one settling workgroup that code again what started wrong;
-// returns the device word that is 1 when the stream did not settle (the word before it is a zeroed counter for
-// launch_adpcm_map's `done`).  launch_adpcm_map (89-way state map of every chunk + composition of the maps -> the start of
-// every block of 256 chunks) and launch_adpcm_encode_mapped (every chunk coded from the start the maps give it) leave at once
-// when *need == 0 (need == nullptr: run).
-uint64_t adpcm_chain_workspace(uint32_t n);
-const uint32_t* launch_adpcm_chain(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, uint8_t* blob,
-                                   const uint64_t* offs, void* work, uint32_t sweeps, bool settle, hipStream_t s);
+// The reference's step_index carry (adpcm.c:461-498) without a serial pass over the stream: every chunk coded from a
+// guessed start, then `sweeps` launches, a front sweep and one settling workgroup (`settle`) that code again what started
+// wrong, a check, and behind it the exhaustive route (89-way state map of every chunk, composition of the maps, every
+// chunk coded from the start the maps give it), which leaves at once unless the chain did not settle; sweeps < 0: the
+// exhaustive route at once.  See amv_adpcm.hip and amv_adpcm_chain.h.  work: adpcm_plain_chain_plan(n).bytes
+// (amv_host_plan.h), whose zero span the launch zeroes.  Only enqueues; false: refused before anything was queued.
+bool launch_adpcm_stream(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, uint8_t* blob, const uint64_t* offs,
+                         void* work, int sweeps, bool settle, hipStream_t s);
 void adpcm_quotient_table(float out[89]);   // the encoder's quotient factors (see amv_adpcm.hip: compress)
-uint32_t adpcm_chain_blocks(uint32_t n);   // launch_adpcm_map needs map[(n + blocks) * 96] and bstart[blocks]
-void launch_adpcm_map(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n,
-                      uint8_t* map, int32_t* bstart, uint32_t* done, const uint32_t* need, hipStream_t s);
-void launch_adpcm_encode_mapped(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, const uint8_t* map,
-                                const int32_t* bstart, uint8_t* blob, const uint64_t* offs, const uint32_t* need, hipStream_t s);
 // amvlib's IMA-WAV-layout frame encoder (AdpcmIma.c:43-160), one lane
 void launch_adpcm_wav_encode(const int16_t* samples, int groups, int32_t* state, uint8_t* frame, hipStream_t s);
 void launch_adpcm_encode(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp,
@@ -288,10 +282,10 @@ uint64_t adpcm_trellis_workspace(uint32_t n, uint32_t trellis);
 bool launch_adpcm_trellis(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, const int32_t* step_in,
                           uint32_t trellis, uint8_t* blob, const uint64_t* offs, int32_t* step_out, uint16_t* paths, hipStream_t s);
 // ... and the chunks of a call as ONE stream, the step index carried from chunk to chunk on the device (guessed starts,
-// a fixed number of sweeps over device-built lists, a check, and the 89-start fall-back behind it: see amv_adpcm.hip).
-// first_index 0..88; paths: adpcm_trellis_workspace(n, trellis) bytes; work: adpcm_trellis_chain_plan(n).bytes
-// (amv_host_plan.h), whose counters the launch zeroes; sweeps < 0: the fall-back at once.  Only enqueues; false: refused
-// before anything was queued.
+// a fixed number of sweeps over device-built lists, a check, and the 89-start fall-back behind it: see
+// amv_adpcm_trellis.hip).  first_index 0..88; paths: adpcm_trellis_workspace(n, trellis) bytes; work:
+// adpcm_trellis_chain_plan(n).bytes (amv_host_plan.h), whose zero span the launch zeroes; sweeps < 0: the fall-back at
+// once.  Only enqueues; false: refused before anything was queued.
 bool launch_adpcm_trellis_stream(const int16_t* pcm, const uint64_t* pcm_offs, const uint32_t* nsamp, uint32_t n, uint32_t first_index,
                                  uint32_t trellis, uint8_t* blob, const uint64_t* offs, int32_t* step_out, uint16_t* paths, void* work,
                                  int sweeps, hipStream_t s);

@@ -235,28 +235,18 @@ extern "C" int amvhip_adpcm_encode_batch_dev(amvhip_ctx* c, const int16_t* d_pcm
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
     Timed t(c, AMVHIP_K_ADPCM_ENC, (hipStream_t)stream);
-    const uint32_t* need = nullptr;
     if (!d_step_in) {  // the reference's behaviour: step_index runs through the whole stream
-        const size_t nb = adpcm_chain_blocks(n);
-        if (int r = ensure(c, c->map, ((size_t)n + nb) * 96)) return r;
-        if (int r = ensure(c, c->start, (nb + 1) * 4)) return r;    // the blocks' starts + a counter for the exhaustive route alone
-        uint32_t* done = (uint32_t*)c->start.p + nb;
-        if (c->adpcm_sweeps >= 0) {   // guessed starts + sweeps; the exhaustive route behind it runs only if they do not settle
-            if (int r = ensure(c, c->chain, adpcm_chain_workspace(n))) return r;
-            uint32_t sweeps = (uint32_t)c->adpcm_sweeps;
-            if (!c->adpcm_sweeps_set) sweeps = adpcm_default_sweeps(n);
-            c->chain_n = n;
-            // (state, lists, counters and the flag live in the context's `chain` buffer: chained encodes of ONE context
-            // must be ordered on the device -- one stream at a time, as for every _dev entry point; see amvhip.h)
-            need = launch_adpcm_chain(d_pcm, d_pcm_offs, d_nsamp, n, d_blob, d_offs, c->chain.p, sweeps, c->adpcm_settle, (hipStream_t)stream);
-            if (!need) return fail(c, AMVHIP_ERR_DEVICE, "adpcm_encode: clearing the chain counters failed");
-            done = const_cast<uint32_t*>(need) - 1;   // zeroed with the flag
-        } else {
-            HIP_TRY(c, hipMemsetAsync(done, 0, 4, (hipStream_t)stream));
-        }
-        launch_adpcm_map(d_pcm, d_pcm_offs, d_nsamp, n, (uint8_t*)c->map.p, (int32_t*)c->start.p, done, need, (hipStream_t)stream);
-        launch_adpcm_encode_mapped(d_pcm, d_pcm_offs, d_nsamp, n, (const uint8_t*)c->map.p, (const int32_t*)c->start.p, d_blob, d_offs, need,
-                                   (hipStream_t)stream);
+        if (int r = ensure(c, c->chain, adpcm_plain_chain_plan(n).bytes)) return r;
+        // guessed starts + sweeps, the exhaustive route behind them runs only if they do not settle (adpcm_sweeps < 0: it
+        // runs at once).  (state, lists, counters and maps live in the context's `chain` buffer: chained encodes of ONE
+        // context must be ordered on the device -- one stream at a time, as for every _dev entry point; see amvhip.h)
+        const int sweeps = c->adpcm_sweeps_set ? c->adpcm_sweeps : (int)adpcm_default_sweeps(n);
+        if (!launch_adpcm_stream(d_pcm, d_pcm_offs, d_nsamp, n, d_blob, d_offs, c->chain.p, sweeps, c->adpcm_settle, (hipStream_t)stream))
+            return fail(c, AMVHIP_ERR_DEVICE, "adpcm_encode: clearing the chain counters failed");
+        // chain_n != 0: `chain` holds the counters of a chained encode of chain_n chunks (amvhip_adpcm_chain_stats).  The
+        // forced exhaustive route counts nothing and leaves it alone: its knob is fixed when the context is made, so such
+        // a context never has statistics, as before
+        if (sweeps >= 0) c->chain_n = n;
         return check_launch(c, "adpcm_encode");
     }
     launch_adpcm_encode(d_pcm, d_pcm_offs, d_nsamp, n, d_step_in, d_blob, d_offs, nullptr, (hipStream_t)stream);
@@ -267,18 +257,24 @@ extern "C" void amvhip_adpcm_quotient_table(float out[89]) {
     if (out) adpcm_quotient_table(out);
 }
 
+// what both chains' statistics are: out[0] = the exhaustive route ran, out[1 + k] = the counter word first + k of the
+// last call's plan p in buffer b.  Caller holds c->mu.
+static int chain_stats(amvhip_ctx* c, const DevBuf& b, const ChainPlan& p, uint32_t first, uint32_t out[64]) {
+    uint32_t w[kChainCounterWords];
+    HIP_TRY(c, hipDeviceSynchronize());
+    HIP_TRY(c, hipMemcpy(w, (const uint8_t*)b.p + p.counters, sizeof w, hipMemcpyDeviceToHost));
+    out[0] = w[kChainWordNeed] ? 1u : 0u;
+    for (uint32_t k = 0; k < 62u; ++k) out[k + 1u] = w[first + k];
+    out[63] = 0;
+    return AMVHIP_OK;
+}
+
 extern "C" int amvhip_adpcm_chain_stats(amvhip_ctx* c, uint32_t out[64]) {
     if (!c || !out) return AMVHIP_ERR_ARG;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->chain_n) return fail(c, AMVHIP_ERR_ARG, "adpcm_chain_stats: no chained encode has run");
-    uint32_t w[64];
-    HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(w, (const uint8_t*)c->chain.p + (size_t)c->chain_n * 16, sizeof w, hipMemcpyDeviceToHost));
-    out[0] = w[63];
-    for (int k = 0; k < 62; ++k) out[k + 1] = w[k];
-    out[63] = 0;
-    return AMVHIP_OK;
+    return chain_stats(c, c->chain, adpcm_plain_chain_plan(c->chain_n), chain_word_list(0), out);
 }
 
 extern "C" int amvhip_adpcm_decode_batch_async(amvhip_ctx* c, const uint8_t* blob, uint64_t blob_bytes,
@@ -397,14 +393,7 @@ extern "C" int amvhip_adpcm_trellis_chain_stats(amvhip_ctx* c, uint32_t out[64])
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
     if (!c->trellis_chain_n) return fail(c, AMVHIP_ERR_ARG, "adpcm_trellis_chain_stats: no trellis stream has been coded");
-    uint32_t w[kTrellisCounterWords];
-    HIP_TRY(c, hipDeviceSynchronize());
-    HIP_TRY(c, hipMemcpy(w, (const uint8_t*)c->trellis_chain.p + adpcm_trellis_chain_plan(c->trellis_chain_n).counters, sizeof w,
-                         hipMemcpyDeviceToHost));
-    out[0] = w[kTrellisNeedWord] ? 1u : 0u;
-    for (int k = 0; k < 62; ++k) out[k + 1] = w[64 + k];
-    out[63] = 0;
-    return AMVHIP_OK;
+    return chain_stats(c, c->trellis_chain, adpcm_trellis_chain_plan(c->trellis_chain_n), chain_word_recoded(0), out);
 }
 
 extern "C" int amvhip_adpcm_encode_trellis_stream(amvhip_ctx* c, const int16_t* pcm, uint64_t pcm_samples, const uint64_t* pcm_offs,

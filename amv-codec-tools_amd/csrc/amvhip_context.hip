@@ -101,7 +101,7 @@ static void read_knobs(amvhip_ctx* c) {
             c->adpcm_settle = false;   // sweeps by stream length, then nothing: the chain's check sends the stream down the exhaustive route
         } else {
             c->adpcm_sweeps_set = true;
-            c->adpcm_sweeps = strcmp(e, "map") == 0 ? -1 : (atoi(e) < 0 ? 0 : (atoi(e) > 60 ? 60 : atoi(e)));
+            c->adpcm_sweeps = strcmp(e, "map") == 0 ? -1 : (atoi(e) < 0 ? 0 : (atoi(e) > (int)kAdpcmSweepsMost ? (int)kAdpcmSweepsMost : atoi(e)));
         }
     }
     if (const char* e = getenv("AMVHIP_ADPCM_TRELLIS_SWEEPS"))   // test knob: "map" = the fall-back at once, or a sweep count (0: none)

@@ -50,7 +50,7 @@ struct amvhip_ctx {
     std::string err;
     DevBuf d_dec, d_enc;   // HuffDecodeImage, HuffEncodeImage
     // workspace
-    DevBuf coef, tmp, flag, map, start, enc_retry, stats, ws, ws_line, layout, ws_bytes, scaled, trellis_ws, trellis_chain, chain, split;
+    DevBuf coef, tmp, flag, enc_retry, stats, ws, ws_line, layout, ws_bytes, scaled, trellis_ws, trellis_chain, chain, split;
     // the -nr entries: the frames' sums and offsets (nr_plan of amv_nr_plan.h); the host-buffer forms' copy of the state
     DevBuf nr_ws, nr_state;
     // the shim around the rescaler: the source as YUV420P, the rescaled YUV420P ahead of a last conversion, the decoder's planes

@@ -51,11 +51,11 @@ def test_null_context_is_refused(pkg):
 
 
 def test_host_arithmetic(tmp_path):
-    """adpcm_trellis_tail and adpcm_trellis_chain_plan of amv_host_plan.h, walked by tests/c/trellis_plan_test.cc under the
-    address and undefined-behaviour sanitizers"""
-    exe = str(tmp_path / "trellis_plan_test")
+    """adpcm_trellis_tail and the chain plan of both ADPCM encoders (amv_host_plan.h), walked by
+    tests/c/adpcm_chain_plan_test.cc under the address and undefined-behaviour sanitizers"""
+    exe = str(tmp_path / "adpcm_chain_plan_test")
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    "-I", os.path.join(ROOT, "amv-codec-tools_amd", "csrc"), os.path.join(ROOT, "tests", "c", "trellis_plan_test.cc"), "-o", exe],
+                    "-I", os.path.join(ROOT, "amv-codec-tools_amd", "csrc"), os.path.join(ROOT, "tests", "c", "adpcm_chain_plan_test.cc"), "-o", exe],
                    check=True)
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.startswith("ok ") and not out.stderr, out.stdout + out.stderr

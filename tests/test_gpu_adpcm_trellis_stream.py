@@ -29,7 +29,7 @@ class Stream:
         self._want = {}
 
     def want(self, orc, trellis, first=0):
-        """(chunks, starts, ends) of the sequential encoder; computed once per (trellis, first)"""
+        """(chunks, starts, ends) of the sequential encoder (trellis 0: the plain one); computed once per (trellis, first)"""
         key = (trellis, first)
         if key not in self._want:
             chunks, starts, ends, idx = [], [], [], min(max(first, 0), 88)
@@ -37,7 +37,8 @@ class Stream:
                 starts.append(idx)
                 o, m = int(self.pcm_offs[i]), int(self.sizes[i])
                 if m:
-                    chunk, idx = orc.adpcm_encode_chunk_trellis(self.pcm[o:o + m], idx, trellis)
+                    seg = self.pcm[o:o + m]
+                    chunk, idx = orc.adpcm_encode_chunk_trellis(seg, idx, trellis) if trellis else orc.adpcm_encode_chunk(seg, idx)
                 else:
                     chunk = bytes([0, 0, idx, 0, 0, 0, 0, 0])
                 chunks.append(chunk)
@@ -290,5 +291,62 @@ def test_several_streams_on_one_context(pkg, orc, trellis):
     try:
         for seed, n in ((21, 50), (22, 400), (23, 130), (24, 257)):
             check(c, orc, _ragged(orc, seed, n, 1, [s for s in SIZES if s <= 640]), trellis)
+    finally:
+        c.close()
+
+
+def run_plain_dev(ctx, s, fill=0xEE):
+    """the plain encoder's chained device form (no start indices: the step index runs through the stream) -> blob"""
+    import torch
+    d_pcm, d_po, d_ns, d_co = _dev(s.pcm), _dev(s.pcm_offs), _dev(s.sizes), _dev(s.offs)
+    d_blob = torch.full((s.blob_bytes + 1,), fill, dtype=torch.uint8, device="cuda:0")
+    ctx.adpcm_encode_batch_dev(d_pcm, d_po, d_ns, s.n, None, d_blob, d_co, None)
+    torch.cuda.synchronize()
+    blob = d_blob.cpu().numpy()
+    assert blob[-1] == fill
+    return blob[:-1]
+
+
+def test_both_encoders_alternate_on_one_context(pkg, orc, walks):
+    """The plain chain and the trellis stream share one workspace plan and one set of device pieces: the two in turn on ONE
+    context, n shrinking between calls.  300 chunks: more than one 256-chunk map block and more than two 128-lane workgroups;
+    70: a wave and a partial wave; 130: a workgroup and two lanes.  After every call every byte is the sequential encoder's,
+    the bytes between and behind the chunks are untouched, and each encoder's statistics are what a fresh context reports
+    after making only that encoder's last call: one encoder's run moves neither the other's counters nor where they are read."""
+    gap = 3
+    w300, w70 = (Stream(walks[n].pcm, walks[n].sizes.tolist(), gap) for n in (300, 70))
+    r130 = _ragged(orc, 31, 130, gap)
+    assert (w300.n, w70.n, r130.n) == (300, 70, 130) and 0 in r130.sizes and 2048 in r130.sizes
+
+    def call(c, kind, s):
+        if kind == "plain":
+            blob, trellis = run_plain_dev(c, s), 0
+        else:
+            (blob, so), trellis = run_dev(c, s, 1), 1
+            assert so.tolist() == s.want(orc, 1)[2], (kind, s.n)
+        bad = np.flatnonzero(blob != s.want_blob(orc, trellis))      # (the gaps and what lies behind are 0xEE in both)
+        assert bad.size == 0, (kind, s.n, "first differing byte", int(bad[0]), "chunk", int(np.searchsorted(s.offs, bad[0], "right")) - 1)
+
+    def stats(c, kind):
+        return c.adpcm_chain_stats() if kind == "plain" else c.adpcm_trellis_chain_stats()
+
+    def fresh(kind, s):
+        c = pkg.Context(0)
+        try:
+            call(c, kind, s)
+            return stats(c, kind)
+        finally:
+            c.close()
+
+    c = pkg.Context(0)
+    try:
+        last = {}
+        for kind, s in (("plain", w300), ("trellis", w70), ("plain", r130), ("trellis", w300)):
+            call(c, kind, s)
+            last[kind] = fresh(kind, s)
+            for k, want in last.items():
+                got = stats(c, k)
+                print("after %s of %d chunks: %s %s (fresh context: %s)" % (kind, s.n, k, got, want))
+                assert got == want, (kind, s.n, k)
     finally:
         c.close()
