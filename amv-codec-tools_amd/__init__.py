@@ -120,6 +120,12 @@ SYMBOLS = {
     "amvhip_encode_yuv420_nr_stream": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp]),
     "amvhip_encode_nr_stream_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "amvhip_encode_nr_stream": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp]),
+    "amvhip_encode_trellis_lambda_max": (_u32, []),
+    "amvhip_encode_trellis_lambda": (_u32, [_u32]),
+    "amvhip_encode_trellis_batch_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_encode_trellis_batch": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp]),
+    "amvhip_encode_yuv420_trellis_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_encode_yuv420_trellis_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp]),
     "amvhip_resample_yuv420_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
     "amvhip_encode_yuv420_scaled_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "amvhip_img_convert_supported": (_int, [_int, _int, _u32, _u32]),
@@ -147,6 +153,7 @@ SYMBOLS = {
     "amvhip_audio_resample": (_int, [_vp, _vp, _vp, _int]),
     "amvhip_audio_resample_close": (None, [_vp]),
     "amvhip_encode_coefs_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "amvhip_encode_trellis_coefs_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _u32, _vp, _vp]),
     "amvhip_adpcm_decode_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "amvhip_adpcm_encode_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
     "amvhip_adpcm_decode_batch": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _vp, _u64, _vp, _vp]),
@@ -347,6 +354,37 @@ class Context:
                                                             _ptr(state), _ptr(blob), blob_cap, _ptr(offs), _ptr(lens)),
                            "encode_nr_stream")
 
+    def encode_trellis_lambda_max(self):
+        """the largest `lambda` the trellis entries take"""
+        return self.lib.amvhip_encode_trellis_lambda_max()
+
+    def encode_trellis_lambda(self, qscale):
+        """the reference's trellis lambda for a -qscale (3481 at 8); 0 where it is above encode_trellis_lambda_max()"""
+        return self.lib.amvhip_encode_trellis_lambda(qscale)
+
+    def encode_trellis_batch_dev(self, pix, pix_stride, is_bgr, n, w, h, qbias, lam, blob, blob_cap, offs, lens, stream=None):
+        """encode_batch_dev with the trellis quantiser: per block the AC levels of least distortion + lam * bits"""
+        return self._check(self.lib.amvhip_encode_trellis_batch_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, qbias, lam,
+                                                                    _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), stream),
+                           "encode_trellis_batch_dev")
+
+    def encode_trellis_batch(self, pix, pix_stride, is_bgr, n, w, h, qbias, lam, blob, blob_cap, offs, lens):
+        return self._check(self.lib.amvhip_encode_trellis_batch(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, qbias, lam,
+                                                                _ptr(blob), blob_cap, _ptr(offs), _ptr(lens)), "encode_trellis_batch")
+
+    def encode_yuv420_trellis_batch_dev(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, qbias, lam, blob, blob_cap,
+                                        offs, lens, stream=None):
+        return self._check(self.lib.amvhip_encode_yuv420_trellis_batch_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride,
+                                                                           y_frame, c_frame, n, w, h, qbias, lam, _ptr(blob),
+                                                                           blob_cap, _ptr(offs), _ptr(lens), stream),
+                           "encode_yuv420_trellis_batch_dev")
+
+    def encode_yuv420_trellis_batch(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, qbias, lam, blob, blob_cap, offs,
+                                    lens):
+        return self._check(self.lib.amvhip_encode_yuv420_trellis_batch(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride,
+                                                                       y_frame, c_frame, n, w, h, qbias, lam, _ptr(blob),
+                                                                       blob_cap, _ptr(offs), _ptr(lens)), "encode_yuv420_trellis_batch")
+
     def encode_yuv422_batch_dev(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, qbias, blob, blob_cap, offs,
                                 lens, stream=None):
         return self._check(self.lib.amvhip_encode_yuv422_batch_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride,
@@ -366,6 +404,10 @@ class Context:
     def encode_coefs_dev(self, pix, pix_stride, is_bgr, n, w, h, qbias, coef, stream=None):
         return self._check(self.lib.amvhip_encode_coefs_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, qbias,
                                                             _ptr(coef), stream), "encode_coefs_dev")
+
+    def encode_trellis_coefs_dev(self, pix, pix_stride, is_bgr, n, w, h, qbias, lam, coef, stream=None):
+        return self._check(self.lib.amvhip_encode_trellis_coefs_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, qbias, lam,
+                                                                    _ptr(coef), stream), "encode_trellis_coefs_dev")
 
     def adpcm_decode_batch_dev(self, blob, blob_bytes, offs, lens, n, pcm, pcm_offs, final_state=None, stream=None):
         return self._check(self.lib.amvhip_adpcm_decode_batch_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens),

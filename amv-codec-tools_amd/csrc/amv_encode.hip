@@ -30,18 +30,25 @@ using namespace enc;
 // amv_encode_frame_kernel hands back go through here; sel: which frames (FrameSel, as in the decoder's rounds).
 // Nr: nothing (the plain kernel, its signature and code as they always were), or one `const uint16_t*` -- the noise-reduction
 // offsets of the call's frames (64 uint16 per frame, amv_nr_plan.h): a frame's 128 bytes go to LDS and transform_block
-// denoises with them between the column pass and the quantiser.
+// denoises with them between the column pass and the quantiser; or one TrellisArg -- the AC outputs leave transform_block
+// un-quantised, go to the lane's line in the planes' space, and trellis_lane makes the levels there.
 template <bool kYuv, class... Nr>
 __global__ __launch_bounds__(kWave) void amv_forward_kernel(Source in, uint32_t n, FrameSel sel, FrameGeom g, uint32_t nseg, uint32_t per_seg,
                                                             uint32_t qbias, int16_t* __restrict__ coef, Nr... nr) {
-    constexpr bool kNr = sizeof...(Nr) != 0;
-    static_assert(sizeof...(Nr) <= 1, "the offsets, or nothing");
+    constexpr bool kNr = OptKind<Nr...>::kNr, kTrellis = OptKind<Nr...>::kTrellis;
+    static_assert(sizeof...(Nr) == 0 || kNr || kTrellis, "the offsets, lambda, or nothing");
     __shared__ __attribute__((aligned(16))) int16_t s_planes[kPlaneSamples];
     __shared__ __attribute__((aligned(16))) uint32_t s_qmul[kQuantMulWords];
     uint32_t* s_nr_off = nullptr;
     if constexpr (kNr) {
         __shared__ __attribute__((aligned(16))) uint32_t s_off[32];
         s_nr_off = s_off;
+    }
+    const TrellisTables* s_trellis = nullptr;
+    if constexpr (kTrellis) {
+        __shared__ __attribute__((aligned(16))) TrellisTables s_tab;
+        load_trellis_tables(&s_tab, threadIdx.x, kWave);
+        s_trellis = &s_tab;
     }
     load_quant_mul(s_qmul, threadIdx.x, kWave);
     int16_t* const s_y = s_planes;
@@ -70,7 +77,21 @@ __global__ __launch_bounds__(kWave) void amv_forward_kernel(Source in, uint32_t 
         convert_segment<kYuv>(in, f, g, my, m0, cnt, lane, s_y, s_cb, s_cr);
         if (kNr && lane < 32u) s_nr_off[lane] = reinterpret_cast<const uint32_t*>(nr_offsets_of(nr...) + (uint64_t)f * 64u)[lane];
         __syncthreads();
-        if (lane < nb) {
+        if constexpr (kTrellis) {
+            uint32_t out[32], nz_lo, nz_hi;
+            if (lane < nb) transform_block<false, true>(s_y, s_cb, s_cr, s_qmul, lane, qbias, out, nz_lo, nz_hi);
+            __syncthreads();               // every lane has its samples: the planes become the lines
+            if (lane < nb) {
+                uint8_t* const region = reinterpret_cast<uint8_t*>(s_planes);
+#pragma unroll
+                for (uint32_t i = 0; i < 8; ++i)
+                    *reinterpret_cast<uint4*>(region + lane * 128u + ((i ^ (lane & 7u)) << 4)) = make_uint4(out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]);
+                trellis_lane(region, lane, *s_trellis, qbias, trellis_lambda_of(nr...), nz_lo, nz_hi);
+                uint4* dst = reinterpret_cast<uint4*>(coef + ((uint64_t)slot * g.mcus + (uint64_t)my * g.mcu_cols + m0) * 384u + lane * 64u);
+#pragma unroll
+                for (uint32_t i = 0; i < 8; ++i) dst[i] = *reinterpret_cast<const uint4*>(region + lane * 128u + ((i ^ (lane & 7u)) << 4));
+            }
+        } else if (lane < nb) {
             uint32_t out[32], nz_lo, nz_hi;
             transform_block<kNr>(s_y, s_cb, s_cr, s_qmul, lane, qbias, out, nz_lo, nz_hi, reinterpret_cast<const uint16_t*>(s_nr_off));
             uint4* dst = reinterpret_cast<uint4*>(coef + ((uint64_t)slot * g.mcus + (uint64_t)my * g.mcu_cols + m0) * 384u + lane * 64u);
@@ -82,12 +103,16 @@ __global__ __launch_bounds__(kWave) void amv_forward_kernel(Source in, uint32_t 
 }
 
 static void launch_forward_any(const Source& in, bool yuv, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g,
-                               uint32_t qbias, int16_t* coef, const uint16_t* nr_offs, hipStream_t s) {
+                               uint32_t qbias, int16_t* coef, const uint16_t* nr_offs, const TrellisArg* trellis, hipStream_t s) {
     if (items == 0) return;
     const uint32_t nseg = segs_per_row(g);
     const uint32_t per_seg = (g.mcu_cols + nseg - 1) / nseg;      // balanced: 11 columns -> 6 + 5
     const uint64_t grid = (uint64_t)(sel.round && items > 64u ? 64u : items) * g.mcu_rows * nseg;
-    if (nr_offs && yuv)
+    if (trellis && yuv)
+        hipLaunchKernelGGL((amv_forward_kernel<true, TrellisArg>), dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g, nseg, per_seg, qbias, coef, *trellis);
+    else if (trellis)
+        hipLaunchKernelGGL((amv_forward_kernel<false, TrellisArg>), dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g, nseg, per_seg, qbias, coef, *trellis);
+    else if (nr_offs && yuv)
         hipLaunchKernelGGL((amv_forward_kernel<true, const uint16_t*>), dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g, nseg, per_seg, qbias, coef, nr_offs);
     else if (nr_offs)
         hipLaunchKernelGGL((amv_forward_kernel<false, const uint16_t*>), dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g, nseg, per_seg, qbias, coef, nr_offs);
@@ -98,13 +123,13 @@ static void launch_forward_any(const Source& in, bool yuv, uint32_t n, const Fra
 }
 
 void launch_forward(const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, const FrameSel& sel, uint32_t items,
-                    const FrameGeom& g, uint32_t qbias, int16_t* coef, hipStream_t s, const uint16_t* nr_offs) {
-    launch_forward_any(Source{pix, pix_stride, is_bgr, YuvSource{}}, false, n, sel, items, g, qbias, coef, nr_offs, s);
+                    const FrameGeom& g, uint32_t qbias, int16_t* coef, hipStream_t s, const uint16_t* nr_offs, const TrellisArg* trellis) {
+    launch_forward_any(Source{pix, pix_stride, is_bgr, YuvSource{}}, false, n, sel, items, g, qbias, coef, nr_offs, trellis, s);
 }
 
 void launch_forward_yuv(const YuvSource& src, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, uint32_t qbias,
-                        int16_t* coef, hipStream_t s, const uint16_t* nr_offs) {
-    launch_forward_any(Source{nullptr, 0u, 0, src}, true, n, sel, items, g, qbias, coef, nr_offs, s);
+                        int16_t* coef, hipStream_t s, const uint16_t* nr_offs, const TrellisArg* trellis) {
+    launch_forward_any(Source{nullptr, 0u, 0, src}, true, n, sel, items, g, qbias, coef, nr_offs, trellis, s);
 }
 
 // ============================================================================================

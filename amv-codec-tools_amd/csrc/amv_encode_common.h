@@ -12,6 +12,7 @@
 #include "amv_kernels.h"
 #include "amv_nr_plan.h"
 #include "amv_segment.h"
+#include "amv_trellis_plan.h"
 
 namespace amv {
 namespace enc {
@@ -350,7 +351,9 @@ __device__ __forceinline__ uint32_t interleave_halves(uint32_t x) {
 // kNr: denoise_dct_c (mpegvideo_enc.c:2937-2959; amv_nr_plan.h) between the column pass and the quantiser, with the
 // frame's 64 offsets in s_nr_off (LDS, 16-byte aligned, entry c * 8 + r for row r of column c: a column's eight are one
 // 16-byte read).  The sums that denoise_dct_c also takes are amv_nr_sums_kernel's (amv_encode_nr.hip).
-template <bool kNr = false>
+// kTrellis: the AC outputs leave un-quantised (they fit 16 bits, see above), in the same pairs -- trellis_lane, below, turns
+// the line they make into levels; the DC is quantised here as ever, and the mask that comes back is not the levels'.
+template <bool kNr = false, bool kTrellis = false>
 __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_t* s_cb, const int16_t* s_cr, const uint32_t* s_qmul,
                                                 uint32_t lane, uint32_t qbias, uint32_t (&out)[32], uint32_t& nz_lo, uint32_t& nz_hi,
                                                 const uint16_t* s_nr_off = nullptr) {
@@ -399,6 +402,8 @@ __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_
                 const int ax = abs(x);
                 const int a = is_c ? (ax + (qc >> 1)) / qc : (ax + (ql >> 1)) / ql;
                 q = x < 0 ? -a : a;
+            } else if (kTrellis) {
+                q = x;
             } else {
                 const int sign = x >> 31;
                 q = mad24v(x, mul[r], bias ^ (sign & 0x3fffff)) >> 22;
@@ -420,14 +425,51 @@ __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_
     nz_hi = interleave_halves(even_odd_hi);
 }
 
-// the one optional trailing argument of the encoder kernels (`class... Nr`): the frames' noise-reduction offsets, or nothing
+// the one optional trailing argument of the encoder kernels (`class... Opt`): nothing, the frames' noise-reduction offsets
+// (const uint16_t*), or the trellis quantiser's lambda (TrellisArg)
+template <class... Opt> struct OptKind { static constexpr bool kNr = false, kTrellis = false; };
+template <> struct OptKind<const uint16_t*> { static constexpr bool kNr = true, kTrellis = false; };
+template <> struct OptKind<TrellisArg> { static constexpr bool kNr = false, kTrellis = true; };
 __device__ __forceinline__ const uint16_t* nr_offsets_of() { return nullptr; }
 __device__ __forceinline__ const uint16_t* nr_offsets_of(const uint16_t* offs) { return offs; }
+__device__ __forceinline__ const uint16_t* nr_offsets_of(TrellisArg) { return nullptr; }
+__device__ __forceinline__ uint32_t trellis_lambda_of() { return 0u; }
+__device__ __forceinline__ uint32_t trellis_lambda_of(const uint16_t*) { return 0u; }
+__device__ __forceinline__ uint32_t trellis_lambda_of(TrellisArg t) { return t.lambda; }
 
 // coefficient k of lane `lane`'s 128-byte line in an LDS region of 64 lines: 16-byte granules XOR-swizzled by lane, so
 // that lanes reading the same granule of their own lines do not meet on banks
 __device__ __forceinline__ uint32_t line_offset(uint32_t lane, uint32_t k) {
     return lane * 128u + ((((k >> 3) ^ lane) & 7u) << 4) + ((k & 7u) << 1);
+}
+
+// ---- the trellis quantiser (amv_trellis_plan.h), a block per lane -------------------------------------------------------
+// Its tables (code lengths, steps, multipliers: 1 152 bytes) are copied to LDS once per workgroup, as the plain
+// quantiser's multipliers are.
+__device__ const TrellisTables kTrellisTab = make_trellis_tables();
+static_assert(sizeof(TrellisTables) % 4 == 0, "copied by words");
+__device__ __forceinline__ void load_trellis_tables(TrellisTables* s_tab, uint32_t tid, uint32_t nthreads) {
+    for (uint32_t i = tid; i < sizeof(TrellisTables) / 4u; i += nthreads)
+        reinterpret_cast<uint32_t*>(s_tab)[i] = reinterpret_cast<const uint32_t*>(&kTrellisTab)[i];
+}
+struct LdsLine {          // lane's line of a region of 64, as transform_block's pairs were stored there (line_offset)
+    uint8_t* region;
+    uint32_t lane;
+    __device__ __forceinline__ int32_t get(uint32_t k) const { return *reinterpret_cast<const int16_t*>(region + line_offset(lane, k)); }
+    __device__ __forceinline__ void set(uint32_t k, int32_t v) { *reinterpret_cast<int16_t*>(region + line_offset(lane, k)) = (int16_t)v; }
+};
+// The lane's line holds transform_block<.., true>'s outputs (scan order, the DC quantised); its AC values become the
+// levels of the cheapest path, and their mask comes back.  The walk's state -- scores, survivors, the way back: 392 bytes,
+// indexed as the walk goes -- is a private array, i.e. scratch memory: in LDS it would be 98 KB for the one-kernel encoder's
+// 256 lanes on top of its 51.9 KB, one workgroup a CU instead of three.
+__device__ __forceinline__ void trellis_lane(uint8_t* region, uint32_t lane, const TrellisTables& s_tab, uint32_t qbias, uint32_t lambda,
+                                             uint32_t& nz_lo, uint32_t& nz_hi) {
+    const uint32_t k6 = lane % 6u;
+    LdsLine line{region, lane};
+    TrellisLane ws;
+    const uint64_t mask = trellis_block(line, s_tab, k6 >= 4u ? 1u : 0u, qbias, lambda, ws);
+    nz_lo = (uint32_t)mask;
+    nz_hi = (uint32_t)(mask >> 32);
 }
 
 }  // namespace enc

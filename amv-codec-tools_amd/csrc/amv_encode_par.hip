@@ -217,14 +217,17 @@ __device__ __forceinline__ Cursor seek_symbol(uint32_t j, uint32_t nb, const uin
 
 // Nr: nothing (the plain encoder, its signature and code as they always were), or one `const uint16_t*` -- the frames'
 // noise-reduction offsets (64 uint16 per frame, amv_nr_plan.h): the frame's 128 bytes go to LDS and transform_block
-// denoises with them between the column pass and the quantiser.
+// denoises with them between the column pass and the quantiser; or one TrellisArg -- transform_block leaves the AC outputs
+// un-quantised and trellis_lane makes the levels in the lane's line, once that is written (stage 1's end); the mask of the
+// non-zero ones is its result.  The walk's state is private (scratch), so the LDS grows by the tables alone (1 152 bytes)
+// and three workgroups still fit a CU.
 template <bool kYuv, class... Nr>
 __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
     Source in, uint32_t n, FrameGeom g, uint32_t nseg, uint32_t per_seg, uint32_t qbias, const HuffEncodeImage* __restrict__ img,
     uint8_t* __restrict__ tmp, uint32_t bound, uint32_t* __restrict__ lens, uint32_t* __restrict__ retry_list,
     uint32_t* __restrict__ retry_count, Nr... nr) {
-    constexpr bool kNr = sizeof...(Nr) != 0;
-    static_assert(sizeof...(Nr) <= 1, "the offsets, or nothing");
+    constexpr bool kNr = OptKind<Nr...>::kNr, kTrellis = OptKind<Nr...>::kTrellis;
+    static_assert(sizeof...(Nr) == 0 || kNr || kTrellis, "the offsets, lambda, or nothing");
     __shared__ __attribute__((aligned(16))) uint8_t s_region[kWaves][kRegionBytes];
     __shared__ uint32_t s_own[kOwnWords * kLanes];
     __shared__ uint32_t s_bits[kWindowWords];
@@ -244,6 +247,12 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
         __shared__ __attribute__((aligned(16))) uint32_t s_nr_off[32];
         if (tl < 32u) s_nr_off[tl] = reinterpret_cast<const uint32_t*>(nr_offsets_of(nr...) + (uint64_t)f * 64u)[tl];
         s_nr = reinterpret_cast<const uint16_t*>(s_nr_off);
+    }
+    const TrellisTables* s_trellis = nullptr;
+    if constexpr (kTrellis) {
+        __shared__ __attribute__((aligned(16))) TrellisTables s_tab;
+        load_trellis_tables(&s_tab, tl, kLanes);
+        s_trellis = &s_tab;
     }
     uint8_t* const region = s_region[wave];
     int16_t* const s_y = reinterpret_cast<int16_t*>(region);
@@ -314,7 +323,7 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
             convert_segment<kYuv>(in, f, g, my, m0, cnt, lane, s_y, s_cb, s_cr);
             wave_sync();
             uint32_t line[32];
-            if (live) transform_block<kNr>(s_y, s_cb, s_cr, s_qmul, lane, qbias, line, nz_lo, nz_hi, s_nr);
+            if (live) transform_block<kNr, kTrellis>(s_y, s_cb, s_cr, s_qmul, lane, qbias, line, nz_lo, nz_hi, s_nr);
             wave_sync();                                          // every lane has its samples: the planes become the lines
             if (live) {
                 dc = (int)(int16_t)(line[0] & 0xffffu);
@@ -322,6 +331,7 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
                 for (uint32_t i = 0; i < 8; ++i)
                     *reinterpret_cast<uint4*>(region + lane * 128u + ((i ^ (lane & 7u)) << 4)) =
                         make_uint4(line[4 * i], line[4 * i + 1], line[4 * i + 2], line[4 * i + 3]);
+                if constexpr (kTrellis) trellis_lane(region, lane, *s_trellis, qbias, trellis_lambda_of(nr...), nz_lo, nz_hi);
                 if (lane + 3u >= nb) s_lastdc[round & 1u][wave][lane + 3u - nb] = dc;   // Y3, Cb, Cr of the last MCU
             }
         }
@@ -416,11 +426,17 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
 
 void launch_encode_frames(const uint8_t* pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n, const FrameGeom& g,
                           uint32_t qbias, const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens,
-                          uint32_t* retry_list, uint32_t* retry_count, hipStream_t s, const uint16_t* nr_offs) {
+                          uint32_t* retry_list, uint32_t* retry_count, hipStream_t s, const uint16_t* nr_offs, const TrellisArg* trellis) {
     if (n == 0) return;
     const uint32_t nseg = segs_per_row(g);
     const uint32_t per_seg = (g.mcu_cols + nseg - 1) / nseg;      // balanced: 11 columns -> 6 + 5
-    if (nr_offs && yuv)
+    if (trellis && yuv)
+        hipLaunchKernelGGL((amv_encode_frame_kernel<true, TrellisArg>), dim3(n), dim3(kLanes), 0, s, Source{nullptr, 0u, 0, *yuv}, n, g, nseg, per_seg,
+                           qbias, d_img, tmp, bound, lens, retry_list, retry_count, *trellis);
+    else if (trellis)
+        hipLaunchKernelGGL((amv_encode_frame_kernel<false, TrellisArg>), dim3(n), dim3(kLanes), 0, s, Source{pix, pix_stride, is_bgr, YuvSource{}}, n, g,
+                           nseg, per_seg, qbias, d_img, tmp, bound, lens, retry_list, retry_count, *trellis);
+    else if (nr_offs && yuv)
         hipLaunchKernelGGL((amv_encode_frame_kernel<true, const uint16_t*>), dim3(n), dim3(kLanes), 0, s, Source{nullptr, 0u, 0, *yuv}, n, g, nseg, per_seg,
                            qbias, d_img, tmp, bound, lens, retry_list, retry_count, nr_offs);
     else if (nr_offs)

@@ -128,9 +128,13 @@ struct YuvSource {
 // appended to retry_list / *retry_count for launch_forward + launch_pack (rounds).
 // nr_offs (here and in launch_forward / _yuv): null, or the noise-reduction offsets of the call's frames (uint16 [n][64],
 // amv_nr_plan.h: launch_nr_chain writes them) -- the kernels' second instantiation denoises with them before it quantises.
+// trellis (the same three launchers): null, or the trellis quantiser's lambda (amv_trellis_plan.h) -- the kernels' third
+// instantiation searches the AC levels of every block instead of rounding them (nr_offs is then not looked at).
+struct TrellisArg { uint32_t lambda; };
 void launch_encode_frames(const uint8_t* pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n, const FrameGeom& g,
                           uint32_t qbias, const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens,
-                          uint32_t* retry_list, uint32_t* retry_count, hipStream_t s, const uint16_t* nr_offs = nullptr);
+                          uint32_t* retry_list, uint32_t* retry_count, hipStream_t s, const uint16_t* nr_offs = nullptr,
+                          const TrellisArg* trellis = nullptr);
 // The reference's -nr (amv_encode_nr.hip, arithmetic in amv_nr_plan.h).  launch_nr_sums: per frame, the sum of the fdct
 // outputs' magnitudes per position over the encoder's own blocks -> sums uint32 [n][64] (position 0: the sum of DC + 8192).
 // launch_nr_chain: one wave walks the n frames -- halve if due, the frame's offsets -> offs uint16 [n][64] (entry c * 8 + r),
@@ -143,9 +147,10 @@ void launch_nr_chain(const uint32_t* sums, uint32_t n, uint32_t blocks, uint32_t
 // sel: default (round == 0) = frames 0 .. n with lines at the frame's own place; round = items base .. base + round,
 // item p = frame list[p] (p < *count), lines in slot p - base.  items: upper bound of the work (grid size).
 void launch_forward(const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, const FrameSel& sel, uint32_t items,
-                    const FrameGeom& g, uint32_t qbias, int16_t* coef, hipStream_t s, const uint16_t* nr_offs = nullptr);
+                    const FrameGeom& g, uint32_t qbias, int16_t* coef, hipStream_t s, const uint16_t* nr_offs = nullptr,
+                    const TrellisArg* trellis = nullptr);
 void launch_forward_yuv(const YuvSource& src, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, uint32_t qbias,
-                        int16_t* coef, hipStream_t s, const uint16_t* nr_offs = nullptr);
+                        int16_t* coef, hipStream_t s, const uint16_t* nr_offs = nullptr, const TrellisArg* trellis = nullptr);
 void launch_pack(const int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g,
                  const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens, hipStream_t s);
 // exclusive scan of lens -> offs (single workgroup), then gather tmp -> blob.  A chunk that would end past

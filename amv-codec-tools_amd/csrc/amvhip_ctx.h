@@ -16,6 +16,7 @@
 #include "amv_host_plan.h"
 #include "amv_kernels.h"
 #include "amv_nr_plan.h"
+#include "amv_trellis_plan.h"
 
 namespace amv {
 

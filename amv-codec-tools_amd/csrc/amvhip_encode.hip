@@ -22,10 +22,11 @@ extern "C" int amvhip_encode_coefs_dev(amvhip_ctx* c, const uint8_t* d_pix, uint
 // encoder takes the batch; what it hands back -- and the whole batch in AMVHIP_ENTROPY_SERIAL mode -- goes through
 // amv_forward_kernel + amv_pack_kernel a round of dense lines at a time (with a list the count is on the device: the
 // rounds past it find nothing to do and leave at once -- usually all of them).  nr_offs: null, or the frames'
-// noise-reduction offsets (encode_nr_core): both routes then run their denoising instantiation.
+// noise-reduction offsets (encode_nr_core): both routes then run their denoising instantiation.  trellis: null, or the
+// trellis quantiser's lambda: both routes then run their searching instantiation.
 static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n,
                        const FrameGeom& g, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
-                       hipStream_t stream, const uint16_t* nr_offs = nullptr) {
+                       hipStream_t stream, const uint16_t* nr_offs = nullptr, const TrellisArg* trellis = nullptr) {
     const uint32_t bound = amvhip_encode_bound(g.width, g.height);
     const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
     const uint32_t round = fallback_round(n, g, 1024u, 2u);
@@ -40,7 +41,7 @@ static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride,
     if (fused) {
         Timed t(c, AMVHIP_K_PACK, stream);
         launch_encode_frames(d_pix, pix_stride, is_bgr, yuv, n, g, qbias, book, (uint8_t*)c->tmp.p, bound, d_lens, retry_list,
-                             retry_count, stream, nr_offs);
+                             retry_count, stream, nr_offs, trellis);
     }
     if (int r = check_launch(c, "encode_frames")) return r;
     for (uint32_t base = 0; base < n; base += round) {
@@ -48,8 +49,8 @@ static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride,
         const FrameSel sel{fused ? retry_list : nullptr, fused ? retry_count : nullptr, base, items};
         {
             Timed t(c, AMVHIP_K_FDCT, stream);
-            if (yuv) launch_forward_yuv(*yuv, n, sel, items, g, qbias, (int16_t*)c->coef.p, stream, nr_offs);
-            else launch_forward(d_pix, pix_stride, is_bgr, n, sel, items, g, qbias, (int16_t*)c->coef.p, stream, nr_offs);
+            if (yuv) launch_forward_yuv(*yuv, n, sel, items, g, qbias, (int16_t*)c->coef.p, stream, nr_offs, trellis);
+            else launch_forward(d_pix, pix_stride, is_bgr, n, sel, items, g, qbias, (int16_t*)c->coef.p, stream, nr_offs, trellis);
         }
         {
             Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
@@ -174,6 +175,68 @@ extern "C" int amvhip_encode_yuv420_nr_stream_dev(amvhip_ctx* c, const uint8_t* 
                           (hipStream_t)stream);
 }
 
+// ---- trellis quantisation (amv_trellis_plan.h; trellis_lane in amv_encode_common.h) ------------------------------------------
+
+extern "C" uint32_t amvhip_encode_trellis_lambda_max(void) { return trellis_lambda_max(); }
+extern "C" uint32_t amvhip_encode_trellis_lambda(uint32_t qscale) { return trellis_lambda_of_qscale(qscale); }
+
+static int trellis_args_ok(amvhip_ctx* c, uint32_t lambda) {
+    if (lambda > trellis_lambda_max())
+        return fail(c, AMVHIP_ERR_ARG, "encode_trellis: lambda %u is more than amvhip_encode_trellis_lambda_max() = %u", lambda, trellis_lambda_max());
+    return AMVHIP_OK;
+}
+
+extern "C" int amvhip_encode_trellis_coefs_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
+                                               uint32_t h, uint32_t qbias, uint32_t lambda, int16_t* d_coef, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!encode_size_ok(w, h, qbias) || pix_stride < w * 3 || (n && (!d_pix || !d_coef)))
+        return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
+    if ((uintptr_t)d_coef & 15u) return fail(c, AMVHIP_ERR_ARG, "encode: coef must be 16-byte aligned");
+    if (int r = trellis_args_ok(c, lambda)) return r;
+    if (int r = use_device(c)) return r;
+    const FrameGeom g = make_geom(w, h);
+    const TrellisArg trellis{lambda};
+    {
+        Timed t(c, AMVHIP_K_FDCT, (hipStream_t)stream);
+        launch_forward(d_pix, pix_stride, is_bgr, n, kAllFrames, n, g, qbias, d_coef, (hipStream_t)stream, nullptr, &trellis);
+    }
+    return check_launch(c, "forward (trellis)");
+}
+
+extern "C" int amvhip_encode_trellis_batch_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
+                                               uint32_t h, uint32_t qbias, uint32_t lambda, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs,
+                                               uint32_t* d_lens, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!encode_size_ok(w, h, qbias) || pix_stride < w * 3 || (n && !d_pix))
+        return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
+    if (n && (!d_blob || !d_offs || !d_lens)) return fail(c, AMVHIP_ERR_ARG, "encode: null output");
+    if (int r = trellis_args_ok(c, lambda)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const TrellisArg trellis{lambda};
+    return encode_core(c, d_pix, pix_stride, is_bgr, nullptr, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens,
+                       (hipStream_t)stream, nullptr, &trellis);
+}
+
+extern "C" int amvhip_encode_yuv420_trellis_batch_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr,
+                                                      uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                                      uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, uint32_t lambda, uint8_t* d_blob,
+                                                      uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!encode_size_ok(w, h, qbias) || y_stride < w || c_stride < w / 2 ||
+        (n && (!d_y || !d_cb || !d_cr || !d_blob || !d_offs || !d_lens)))
+        return fail(c, AMVHIP_ERR_ARG, "encode_yuv: bad argument (width/height must be even)");
+    if (int r = trellis_args_ok(c, lambda)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    const YuvSource yuv{d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u};
+    const TrellisArg trellis{lambda};
+    return encode_core(c, nullptr, 0u, 0, &yuv, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream, nullptr,
+                       &trellis);
+}
+
 // the host-buffer forms' state: up to the device before the call, back after it (the caller holds c->hmu)
 static int nr_state_up(amvhip_ctx* c, uint32_t nr, const int32_t* state, hipStream_t hs) {
     if (nr == 0u) return AMVHIP_OK;
@@ -203,10 +266,13 @@ static int encode_fetch(amvhip_ctx* c, hipStream_t hs, uint32_t n, uint8_t* blob
 
 // state: null for the plain entry; otherwise the nr entry's (with nr == 0 it goes through the plain route and stays as it was)
 static int encode_rgb_host(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
-                           uint32_t qbias, uint32_t nr, int32_t* state, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
+                           uint32_t qbias, uint32_t nr, int32_t* state, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens,
+                           const uint32_t* lambda = nullptr) {
     if (!c) return AMVHIP_ERR_ARG;
     if (n && (!pix || !blob || !offs || !lens)) return fail(c, AMVHIP_ERR_ARG, "encode: null argument");
     if (int r = nr_args_ok(c, n, w, h, nr, state)) return r;
+    if (lambda)
+        if (int r = trellis_args_ok(c, *lambda)) return r;
     if (n == 0) return AMVHIP_OK;
     hipStream_t hs;
     if (int r = host_stream(c, &hs)) return r;
@@ -217,8 +283,10 @@ static int encode_rgb_host(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_strid
     if (int r = ensure(c, c->h_offs, (size_t)n * 8)) return r;
     if (int r = ensure(c, c->h_lens, (size_t)n * 4)) return r;
     if (int r = nr_state_up(c, nr, state, hs)) return r;
-    if (int r = nr ? amvhip_encode_nr_stream_dev(c, (const uint8_t*)c->h_in.p, pix_stride, is_bgr, n, w, h, qbias, nr, (int32_t*)c->nr_state.p,
-                                                 (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs)
+    if (int r = lambda ? amvhip_encode_trellis_batch_dev(c, (const uint8_t*)c->h_in.p, pix_stride, is_bgr, n, w, h, qbias, *lambda,
+                                                         (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs)
+                : nr   ? amvhip_encode_nr_stream_dev(c, (const uint8_t*)c->h_in.p, pix_stride, is_bgr, n, w, h, qbias, nr, (int32_t*)c->nr_state.p,
+                                                     (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs)
                    : amvhip_encode_batch_dev(c, (const uint8_t*)c->h_in.p, pix_stride, is_bgr, n, w, h, qbias,
                                              (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p,
                                              (uint32_t*)c->h_lens.p, hs))
@@ -238,13 +306,21 @@ extern "C" int amvhip_encode_nr_stream(amvhip_ctx* c, const uint8_t* pix, uint32
     return encode_rgb_host(c, pix, pix_stride, is_bgr, n, w, h, qbias, nr, state, blob, blob_cap, offs, lens);
 }
 
+extern "C" int amvhip_encode_trellis_batch(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                                           uint32_t qbias, uint32_t lambda, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
+    return encode_rgb_host(c, pix, pix_stride, is_bgr, n, w, h, qbias, 0u, nullptr, blob, blob_cap, offs, lens, &lambda);
+}
+
 static int encode_yuv_host(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride, uint32_t c_stride,
                            uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t rows422, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias,
-                           uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens, uint32_t nr = 0u, int32_t* state = nullptr) {
+                           uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens, uint32_t nr = 0u, int32_t* state = nullptr,
+                           const uint32_t* lambda = nullptr) {
     if (!c) return AMVHIP_ERR_ARG;
     if (!size_ok(w, h) || (w & 1) || (h & 1) || y_stride < w || c_stride < w / 2 || (n && (!y || !cb || !cr || !blob || !offs || !lens)))
         return fail(c, AMVHIP_ERR_ARG, "encode_yuv420: bad argument");
     if (int r = nr_args_ok(c, n, w, h, nr, state)) return r;
+    if (lambda)
+        if (int r = trellis_args_ok(c, *lambda)) return r;
     if (n == 0) return AMVHIP_OK;
     hipStream_t hs;
     if (int r = host_stream(c, &hs)) return r;
@@ -263,7 +339,10 @@ static int encode_yuv_host(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, c
         HIP_TRY(c, hipMemcpy2DAsync(d + i * fb + (uint64_t)w * h + (uint64_t)cw * chh, cw, cr + i * c_frame_stride, c_stride, cw, chh, hipMemcpyHostToDevice, hs));
     }
     if (int r = nr_state_up(c, nr, state, hs)) return r;
-    if (int r = nr ? amvhip_encode_yuv420_nr_stream_dev(c, d, d + (uint64_t)w * h, d + (uint64_t)w * h + (uint64_t)cw * chh, w, cw, fb, fb, n, w, h,
+    if (int r = lambda ? amvhip_encode_yuv420_trellis_batch_dev(c, d, d + (uint64_t)w * h, d + (uint64_t)w * h + (uint64_t)cw * chh, w, cw, fb, fb, n,
+                                                                w, h, qbias, *lambda, (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p,
+                                                                (uint32_t*)c->h_lens.p, hs)
+                : nr   ? amvhip_encode_yuv420_nr_stream_dev(c, d, d + (uint64_t)w * h, d + (uint64_t)w * h + (uint64_t)cw * chh, w, cw, fb, fb, n, w, h,
                                                         qbias, nr, (int32_t*)c->nr_state.p, (uint8_t*)c->h_out.p, blob_cap,
                                                         (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs)
                    : encode_yuv_dev(c, d, d + (uint64_t)w * h, d + (uint64_t)w * h + (uint64_t)cw * chh, w, cw, fb, fb, rows422, n, w, h, qbias,
@@ -279,6 +358,14 @@ extern "C" int amvhip_encode_yuv420_nr_stream(amvhip_ctx* c, const uint8_t* y, c
                                               uint64_t* offs, uint32_t* lens) {
     return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, blob, blob_cap, offs, lens, nr,
                            state);
+}
+
+extern "C" int amvhip_encode_yuv420_trellis_batch(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride,
+                                                  uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
+                                                  uint32_t h, uint32_t qbias, uint32_t lambda, uint8_t* blob, uint64_t blob_cap, uint64_t* offs,
+                                                  uint32_t* lens) {
+    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, blob, blob_cap, offs, lens, 0u,
+                           nullptr, &lambda);
 }
 
 extern "C" int amvhip_encode_yuv420_batch(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride,

@@ -369,6 +369,40 @@ int amvhip_encode_yuv420_batch(amvhip_ctx *ctx, const uint8_t *y, const uint8_t 
                                uint64_t c_frame_stride, uint32_t n, uint32_t width, uint32_t height,
                                uint32_t qbias, uint8_t *blob, uint64_t blob_cap, uint64_t *offs, uint32_t *lens);
 /*
+ * Trellis quantisation, the video side of the reference's -trellis / -flags trell (dct_quantize_trellis_c,
+ * mpegvideo_enc.c:2961-3247): per 8x8 block, the AC levels that minimise distortion + lambda * bits, where the bits are
+ * those of AMV's fixed AC code itself (run/size code, magnitude bits, ZRL, and the end-of-block code when one is written)
+ * and the distortion is measured against what every AMV decoder reconstructs (level * Q).  The candidates per
+ * coefficient are the plain quantiser's level and the one below it (the level 1 for a coefficient under the threshold
+ * that lies below the block's last one above it).  The DC is quantised as ever; entropy coding is unchanged, so every
+ * decoder of the plain entries' chunks decodes these.  Arguments and the blob-capacity rule are those of
+ * amvhip_encode_batch(_dev) / amvhip_encode_yuv420_batch(_dev), and:
+ *   lambda : the weight of a bit against squared error in the fdct's scale (8 x the sample's).  0 is legal (distortion
+ *            alone decides; not the plain quantiser: it still may code a 1 under the threshold, or the level below).
+ *            amvhip_encode_trellis_lambda(qscale) is the reference's value for a -qscale (3481 at 8, the scale AMV's
+ *            tables correspond to; 0 where that is above the bound).  More than amvhip_encode_trellis_lambda_max() is
+ *            refused (AMVHIP_ERR_ARG): beyond it the search's int scores could wrap.
+ * Both entropy modes give the same bytes.
+ */
+uint32_t amvhip_encode_trellis_lambda_max(void);
+uint32_t amvhip_encode_trellis_lambda(uint32_t qscale);
+int amvhip_encode_trellis_batch_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr,
+                                    uint32_t n, uint32_t width, uint32_t height, uint32_t qbias, uint32_t lambda,
+                                    uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens, void *stream);
+int amvhip_encode_trellis_batch(amvhip_ctx *ctx, const uint8_t *pix, uint32_t pix_stride, int is_bgr,
+                                uint32_t n, uint32_t width, uint32_t height, uint32_t qbias, uint32_t lambda,
+                                uint8_t *blob, uint64_t blob_cap, uint64_t *offs, uint32_t *lens);
+int amvhip_encode_yuv420_trellis_batch_dev(amvhip_ctx *ctx, const uint8_t *d_y, const uint8_t *d_cb, const uint8_t *d_cr,
+                                           uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride,
+                                           uint64_t c_frame_stride, uint32_t n, uint32_t width, uint32_t height,
+                                           uint32_t qbias, uint32_t lambda, uint8_t *d_blob, uint64_t blob_cap,
+                                           uint64_t *d_offs, uint32_t *d_lens, void *stream);
+int amvhip_encode_yuv420_trellis_batch(amvhip_ctx *ctx, const uint8_t *y, const uint8_t *cb, const uint8_t *cr,
+                                       uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride,
+                                       uint64_t c_frame_stride, uint32_t n, uint32_t width, uint32_t height,
+                                       uint32_t qbias, uint32_t lambda, uint8_t *blob, uint64_t blob_cap, uint64_t *offs,
+                                       uint32_t *lens);
+/*
  * The reference's -nr N noise reduction (denoise_dct_c, mpegvideo_enc.c:2937-2959; update_noise_reduction,
  * mpegvideo.c:861-876) for a stream coded in calls of any size: a dead zone in the DCT domain, between fdct and
  * quantiser, whose width adapts per coefficient position to the running mean magnitude of the stream.  The one lever
@@ -706,6 +740,10 @@ void amvhip_audio_resample_close(amvhip_audio_resampler *r);
 int amvhip_encode_coefs_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr,
                             uint32_t n, uint32_t width, uint32_t height, uint32_t qbias,
                             int16_t *d_coef, void *stream);
+/* ... and what the trellis quantiser makes of them (see amvhip_encode_trellis_batch_dev) */
+int amvhip_encode_trellis_coefs_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr,
+                                    uint32_t n, uint32_t width, uint32_t height, uint32_t qbias, uint32_t lambda,
+                                    int16_t *d_coef, void *stream);
 
 /*
  * IMA ADPCM, AMV chunk layout (AMVDec.c:312-320 + AdpcmIma.c:206-242; adpcm.c:461-498).
