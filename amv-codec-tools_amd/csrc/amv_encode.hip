@@ -56,45 +56,34 @@ __global__ __launch_bounds__(kWave) void amv_forward_kernel(Source in, uint32_t 
     int16_t* const s_cr = s_cb + 8 * kPitchC;
 
     const uint32_t lane = threadIdx.x;
-    uint32_t bid = blockIdx.x;
-    const uint32_t seg = bid % nseg;
-    bid /= nseg;
-    const uint32_t my = bid % g.mcu_rows;
-    const uint32_t m0 = seg * per_seg;
-    if (m0 >= g.mcu_cols) return;          // very wide pictures: the balanced split can leave the last segment empty
-    const uint32_t cnt = min(per_seg, g.mcu_cols - m0);
+    const uint32_t segs = g.mcu_rows * nseg;
+    uint32_t my, m0, cnt;
+    if (!seg_place(SegSplit{nseg, per_seg}, g, blockIdx.x % segs, my, m0, cnt)) return;
     const uint32_t nb = cnt * 6;
     // default: one frame per workgroup column.  A round: the launch is small (the round usually has nothing to do and
     // the host cannot know) and its workgroups walk the round's items: item i = frame list[base + i], lines in slot i.
-    const uint32_t first = bid / g.mcu_rows, stride = gridDim.x / (g.mcu_rows * nseg);
-    uint32_t items = n;
-    if (sel.round) {
-        const uint32_t have = sel.count ? *sel.count : n;
-        items = have > sel.base ? min(sel.round, have - sel.base) : 0u;
-    }
+    const uint32_t first = blockIdx.x / segs, stride = gridDim.x / segs;
+    const uint32_t items = sel_items(sel, n);
     for (uint32_t slot = first; slot < items; slot += stride) {
-        const uint32_t f = sel.round ? (sel.list ? sel.list[sel.base + slot] : sel.base + slot) : slot;
+        const uint32_t f = sel_frame(sel, slot);
         convert_segment<kYuv>(in, f, g, my, m0, cnt, lane, s_y, s_cb, s_cr);
         if (kNr && lane < 32u) s_nr_off[lane] = reinterpret_cast<const uint32_t*>(nr_offsets_of(nr...) + (uint64_t)f * 64u)[lane];
         __syncthreads();
+        uint4* const dst = reinterpret_cast<uint4*>(coef + ((uint64_t)slot * g.mcus + (uint64_t)my * g.mcu_cols + m0) * 384u + lane * 64u);
         if constexpr (kTrellis) {
             uint32_t out[32], nz_lo, nz_hi;
             if (lane < nb) transform_block<false, true>(s_y, s_cb, s_cr, s_qmul, lane, qbias, out, nz_lo, nz_hi);
             __syncthreads();               // every lane has its samples: the planes become the lines
             if (lane < nb) {
                 uint8_t* const region = reinterpret_cast<uint8_t*>(s_planes);
-#pragma unroll
-                for (uint32_t i = 0; i < 8; ++i)
-                    *reinterpret_cast<uint4*>(region + lane * 128u + ((i ^ (lane & 7u)) << 4)) = make_uint4(out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]);
+                store_line(region, lane, out);
                 trellis_lane(region, lane, *s_trellis, qbias, trellis_lambda_of(nr...), nz_lo, nz_hi);
-                uint4* dst = reinterpret_cast<uint4*>(coef + ((uint64_t)slot * g.mcus + (uint64_t)my * g.mcu_cols + m0) * 384u + lane * 64u);
 #pragma unroll
-                for (uint32_t i = 0; i < 8; ++i) dst[i] = *reinterpret_cast<const uint4*>(region + lane * 128u + ((i ^ (lane & 7u)) << 4));
+                for (uint32_t i = 0; i < 8; ++i) dst[i] = load_line_granule(region, lane, i);
             }
         } else if (lane < nb) {
             uint32_t out[32], nz_lo, nz_hi;
             transform_block<kNr>(s_y, s_cb, s_cr, s_qmul, lane, qbias, out, nz_lo, nz_hi, reinterpret_cast<const uint16_t*>(s_nr_off));
-            uint4* dst = reinterpret_cast<uint4*>(coef + ((uint64_t)slot * g.mcus + (uint64_t)my * g.mcu_cols + m0) * 384u + lane * 64u);
 #pragma unroll
             for (int i = 0; i < 8; ++i) dst[i] = make_uint4(out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3]);
         }
@@ -102,34 +91,15 @@ __global__ __launch_bounds__(kWave) void amv_forward_kernel(Source in, uint32_t 
     }
 }
 
-static void launch_forward_any(const Source& in, bool yuv, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g,
-                               uint32_t qbias, int16_t* coef, const uint16_t* nr_offs, const TrellisArg* trellis, hipStream_t s) {
+void launch_forward(const Source& in, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, uint32_t qbias,
+                    const Quantiser& quant, int16_t* coef, hipStream_t s) {
     if (items == 0) return;
-    const uint32_t nseg = segs_per_row(g);
-    const uint32_t per_seg = (g.mcu_cols + nseg - 1) / nseg;      // balanced: 11 columns -> 6 + 5
-    const uint64_t grid = (uint64_t)(sel.round && items > 64u ? 64u : items) * g.mcu_rows * nseg;
-    if (trellis && yuv)
-        hipLaunchKernelGGL((amv_forward_kernel<true, TrellisArg>), dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g, nseg, per_seg, qbias, coef, *trellis);
-    else if (trellis)
-        hipLaunchKernelGGL((amv_forward_kernel<false, TrellisArg>), dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g, nseg, per_seg, qbias, coef, *trellis);
-    else if (nr_offs && yuv)
-        hipLaunchKernelGGL((amv_forward_kernel<true, const uint16_t*>), dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g, nseg, per_seg, qbias, coef, nr_offs);
-    else if (nr_offs)
-        hipLaunchKernelGGL((amv_forward_kernel<false, const uint16_t*>), dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g, nseg, per_seg, qbias, coef, nr_offs);
-    else if (yuv)
-        hipLaunchKernelGGL(amv_forward_kernel<true>, dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g, nseg, per_seg, qbias, coef);
-    else
-        hipLaunchKernelGGL(amv_forward_kernel<false>, dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g, nseg, per_seg, qbias, coef);
-}
-
-void launch_forward(const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, const FrameSel& sel, uint32_t items,
-                    const FrameGeom& g, uint32_t qbias, int16_t* coef, hipStream_t s, const uint16_t* nr_offs, const TrellisArg* trellis) {
-    launch_forward_any(Source{pix, pix_stride, is_bgr, YuvSource{}}, false, n, sel, items, g, qbias, coef, nr_offs, trellis, s);
-}
-
-void launch_forward_yuv(const YuvSource& src, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, uint32_t qbias,
-                        int16_t* coef, hipStream_t s, const uint16_t* nr_offs, const TrellisArg* trellis) {
-    launch_forward_any(Source{nullptr, 0u, 0, src}, true, n, sel, items, g, qbias, coef, nr_offs, trellis, s);
+    const SegSplit sp = seg_split(g);
+    const uint64_t grid = (uint64_t)(sel.round && items > 64u ? 64u : items) * g.mcu_rows * sp.nseg;
+    with_instantiation(in, quant, [&](auto yuv, auto... opt) {
+        hipLaunchKernelGGL((amv_forward_kernel<decltype(yuv)::value, decltype(opt)...>), dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, sel, g,
+                           sp.nseg, sp.per_seg, qbias, coef, opt...);
+    });
 }
 
 // ============================================================================================
@@ -185,10 +155,10 @@ __global__ __launch_bounds__(kWave) void amv_pack_kernel(
     // items base .. base + round, item p = frame list[p] (p < *count), lines in slot p - base.
     const uint32_t lane = threadIdx.x;
     const uint32_t f0 = blockIdx.x * kWave;
-    const uint32_t items = sel.round ? min(sel.round, (sel.count ? *sel.count : n) > sel.base ? (sel.count ? *sel.count : n) - sel.base : 0u) : n;
+    const uint32_t items = sel_items(sel, n);
     if (f0 >= items) return;
     const uint32_t slot = f0 + lane;
-    const uint32_t frame = slot < items ? (sel.round ? (sel.list ? sel.list[sel.base + slot] : sel.base + slot) : slot) : 0xffffffffu;
+    const uint32_t frame = slot < items ? sel_frame(sel, slot) : 0xffffffffu;
     s_frame[lane] = slot < items ? slot : 0xffffffffu;
     const bool live = frame != 0xffffffffu;
     for (int i = lane; i < 4 * 256; i += kWave) (&s_book[0][0])[i] = (&img->code[0][0])[i];

@@ -9,6 +9,8 @@
 // The reference encoder quantises with a matrix no AMV decoder uses; this one uses amvlib's
 // fixed tables (AmvJpeg.c:30-61) and a true -128 level shift so that amvlib and the patched FFmpeg both decode it.
 #pragma once
+#include <type_traits>
+
 #include "amv_kernels.h"
 #include "amv_nr_plan.h"
 #include "amv_segment.h"
@@ -121,6 +123,15 @@ constexpr uint32_t kPitchY = kSegMcus * 16 + 8, kPitchC = kSegMcus * 8 + 8;
 // a segment's planes: Y (16 rows), Cb, Cr (8 rows each), int16 -- 8 192 bytes, which is also 64 coefficient lines
 constexpr uint32_t kPlaneSamples = 16 * kPitchY + 2 * 8 * kPitchC;
 static_assert(kPlaneSamples * 2 == 64 * 128, "a segment's planes and its 64 coefficient lines share one LDS region");
+// the kernels whose workgroup is several waves (amv_encode_frame_kernel, amv_nr_sums_kernel): a wave takes a segment at a
+// time in an LDS region of its own -- its planes, then its lines -- and synchronises by itself
+constexpr uint32_t kWaves = 4;
+constexpr uint32_t kLanes = kWave * kWaves;
+constexpr uint32_t kRegionBytes = kPlaneSamples * 2;
+__device__ __forceinline__ void wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
 
 // RGB_TO_Y / RGB_TO_U / RGB_TO_V of colorspace.h:78-88 with the channel order folded into the weights
 struct Weights { int y0, y2, u0, u2, v0, v2; };
@@ -140,13 +151,6 @@ __device__ __forceinline__ void unpack12(const Px12& v, int (&b)[12]) {
 #pragma unroll
     for (int i = 0; i < 12; ++i) b[i] = (int)((v.w[i >> 2] >> (8 * (i & 3))) & 0xffu);
 }
-
-struct Source {           // where a frame's pixels are
-    const uint8_t* pix;   // RGB24 / BGR24 frames, rows pix_stride apart (kYuv == false)
-    uint32_t pix_stride;
-    int is_bgr;
-    YuvSource yuv;        // planar YUVJ420P (kYuv == true)
-};
 
 // Stage 1 of a segment (MCU row `my`, MCUs m0 .. m0 + cnt) of frame f: colour conversion of 4x2-pixel patches (two
 // unaligned 12-byte loads each) into the LDS planes -- 8 luma and 2 + 2 chroma samples per patch.  Bitstream row k is
@@ -335,7 +339,27 @@ __device__ __forceinline__ uint32_t interleave_halves(uint32_t x) {
     return x;
 }
 
-// Stage 2: lane's block (lane = 6 * MCU in segment + block in MCU) out of the planes, in registers: 8 row passes,
+// The head of stage 2, which amv_nr_sums_kernel runs too: lane's block (lane = 6 * MCU in segment + block in MCU) out of
+// the planes through its eight row passes (get_pixels + row_fdct).  true: a chroma block.
+__device__ __forceinline__ bool block_row_passes(const int16_t* s_y, const int16_t* s_cb, const int16_t* s_cr, uint32_t lane, int (&d)[8][8]) {
+    const uint32_t m = lane / 6u, k6 = lane - 6u * m;
+    const bool is_c = k6 >= 4u;
+    const int16_t* in = is_c ? (k6 == 4u ? s_cb : s_cr) + m * 8u
+                             : s_y + ((k6 >> 1) * 8u) * kPitchY + m * 16u + (k6 & 1u) * 8u;
+    const uint32_t pitch = is_c ? kPitchC : kPitchY;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const uint4 q = *reinterpret_cast<const uint4*>(in + r * pitch);
+        fdct_row_packed(q.x, q.y, q.z, q.w, d[r]);
+        // DCTELEM is 16 bit (dsputil.h:38): nothing to truncate -- the planes hold samples of -128..127 (luma / chroma_u /
+        // chroma_v, the level-shifted bytes of a YUVJ420P source), for which every row-pass output is inside +-16385
+        // (the sum of |weight| * 128 over its eight inputs: 16384 for d[0], d[4], under 15138 for the others), and a
+        // column-pass output inside +-8193 (tests/test_oracle_pin.py::test_fdct_outputs_fit_dctelem)
+    }
+    return is_c;
+}
+
+// Stage 2: lane's block out of the planes, in registers: 8 row passes (block_row_passes),
 // DCTELEM truncation, 8 column passes, dct_quantize_c.  out: the 64 quantised coefficients, scan order, int16 pairs;
 // nz_lo / nz_hi: bit k set where coefficient k (scan order, k >= 1) is not zero.  Pairs are put together
 // as the columns come out: holding all 64 values for a pass in scan order cost registers, spills and 8 % of the
@@ -357,22 +381,9 @@ template <bool kNr = false, bool kTrellis = false>
 __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_t* s_cb, const int16_t* s_cr, const uint32_t* s_qmul,
                                                 uint32_t lane, uint32_t qbias, uint32_t (&out)[32], uint32_t& nz_lo, uint32_t& nz_hi,
                                                 const uint16_t* s_nr_off = nullptr) {
-    const uint32_t m = lane / 6u, k6 = lane - 6u * m;
-    const bool is_c = k6 >= 4u;
-    const int16_t* in = is_c ? (k6 == 4u ? s_cb : s_cr) + m * 8u
-                             : s_y + ((k6 >> 1) * 8u) * kPitchY + m * 16u + (k6 & 1u) * 8u;
-    const uint32_t pitch = is_c ? kPitchC : kPitchY;
-    const uint4* const qm = reinterpret_cast<const uint4*>(s_qmul + (is_c ? 64u : 0u));
     int d[8][8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {                                  // get_pixels + row_fdct
-        const uint4 q = *reinterpret_cast<const uint4*>(in + r * pitch);
-        fdct_row_packed(q.x, q.y, q.z, q.w, d[r]);
-        // DCTELEM is 16 bit (dsputil.h:38): nothing to truncate -- the planes hold samples of -128..127 (luma / chroma_u /
-        // chroma_v, the level-shifted bytes of a YUVJ420P source), for which every row-pass output is inside +-16385
-        // (the sum of |weight| * 128 over its eight inputs: 16384 for d[0], d[4], under 15138 for the others), and a
-        // column-pass output inside +-8193 (tests/test_oracle_pin.py::test_fdct_outputs_fit_dctelem)
-    }
+    const bool is_c = block_row_passes(s_y, s_cb, s_cr, lane, d);
+    const uint4* const qm = reinterpret_cast<const uint4*>(s_qmul + (is_c ? 64u : 0u));
     const int bias = (int)(qbias << 14);   // intra_quant_bias << (QMAT_SHIFT - QUANT_BIAS_SHIFT), :3679
     int held[64];                          // a coefficient waiting for the other half of its pair (the scan's neighbours sit a column apart at most)
 #pragma unroll
@@ -425,8 +436,8 @@ __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_
     nz_hi = interleave_halves(even_odd_hi);
 }
 
-// the one optional trailing argument of the encoder kernels (`class... Opt`): nothing, the frames' noise-reduction offsets
-// (const uint16_t*), or the trellis quantiser's lambda (TrellisArg)
+// the one optional trailing argument of the encoder kernels (`class... Opt`), by Quantiser's alternative: nothing, the
+// frames' noise-reduction offsets (const uint16_t*), or the trellis quantiser's lambda (TrellisArg)
 template <class... Opt> struct OptKind { static constexpr bool kNr = false, kTrellis = false; };
 template <> struct OptKind<const uint16_t*> { static constexpr bool kNr = true, kTrellis = false; };
 template <> struct OptKind<TrellisArg> { static constexpr bool kNr = false, kTrellis = true; };
@@ -437,10 +448,37 @@ __device__ __forceinline__ uint32_t trellis_lambda_of() { return 0u; }
 __device__ __forceinline__ uint32_t trellis_lambda_of(const uint16_t*) { return 0u; }
 __device__ __forceinline__ uint32_t trellis_lambda_of(TrellisArg t) { return t.lambda; }
 
+// From what a launcher was handed to the kernels' template arguments: launch(std::bool_constant<kYuv>, opt...) is called
+// once, opt... being the instantiation's trailing argument -- `kernel<decltype(yuv)::value, decltype(opt)...>` with
+// `opt...` behind its other arguments.  A further source kind or quantiser is a further case here and nowhere else.
+template <class Launch>
+void with_source_kind(const Source& in, Launch&& launch) {
+    if (in.planar) launch(std::true_type{});
+    else launch(std::false_type{});
+}
+template <class Launch>
+void with_instantiation(const Source& in, const Quantiser& quant, Launch&& launch) {
+    with_source_kind(in, [&](auto yuv) {
+        std::visit([&](auto opt) {
+            if constexpr (std::is_same_v<decltype(opt), PlainQuant>) launch(yuv);
+            else launch(yuv, opt);
+        }, quant);
+    });
+}
+
 // coefficient k of lane `lane`'s 128-byte line in an LDS region of 64 lines: 16-byte granules XOR-swizzled by lane, so
 // that lanes reading the same granule of their own lines do not meet on banks
 __device__ __forceinline__ uint32_t line_offset(uint32_t lane, uint32_t k) {
     return lane * 128u + ((((k >> 3) ^ lane) & 7u) << 4) + ((k & 7u) << 1);
+}
+// the line whole: its eight granules (granule i = coefficients 8 i .. 8 i + 7) out of 32 dwords of pairs; one granule back
+__device__ __forceinline__ void store_line(uint8_t* region, uint32_t lane, const uint32_t (&v)[32]) {
+#pragma unroll
+    for (uint32_t i = 0; i < 8; ++i)
+        *reinterpret_cast<uint4*>(region + lane * 128u + ((i ^ (lane & 7u)) << 4)) = make_uint4(v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
+}
+__device__ __forceinline__ uint4 load_line_granule(const uint8_t* region, uint32_t lane, uint32_t i) {
+    return *reinterpret_cast<const uint4*>(region + lane * 128u + ((i ^ (lane & 7u)) << 4));
 }
 
 // ---- the trellis quantiser (amv_trellis_plan.h), a block per lane -------------------------------------------------------

@@ -22,19 +22,6 @@ namespace amv {
 
 using namespace enc;
 
-namespace {
-
-constexpr uint32_t kWaves = 4;
-constexpr uint32_t kLanes = kWave * kWaves;
-constexpr uint32_t kRegionBytes = kPlaneSamples * 2;   // a wave's planes, then its 64 lines of magnitudes
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-}  // namespace
-
 template <bool kYuv>
 __global__ __launch_bounds__(kLanes) void amv_nr_sums_kernel(Source in, FrameGeom g, uint32_t nseg, uint32_t per_seg,
                                                              uint32_t* __restrict__ sums) {
@@ -51,25 +38,15 @@ __global__ __launch_bounds__(kLanes) void amv_nr_sums_kernel(Source in, FrameGeo
     const uint32_t segs = g.mcu_rows * nseg;
     uint32_t acc = 0;                                  // position `lane` over this wave's segments (<= blocks x 16320 < 2^31)
     for (uint32_t s = wave; s < segs; s += kWaves) {   // (a wave's own region: no workgroup barrier inside)
-        const uint32_t my = s / nseg, m0 = (s - my * nseg) * per_seg;
-        if (m0 >= g.mcu_cols) continue;                // very wide pictures: the balanced split can leave the last segment empty
-        const uint32_t cnt = min(per_seg, g.mcu_cols - m0);
+        uint32_t my, m0, cnt;
+        if (!seg_place(SegSplit{nseg, per_seg}, g, s, my, m0, cnt)) continue;
         const uint32_t nb = cnt * 6u;
         convert_segment<kYuv>(in, f, g, my, m0, cnt, lane, s_y, s_cb, s_cr);
         wave_sync();
         uint32_t line[32];                             // the block's magnitudes, position order, uint16 pairs
-        if (lane < nb) {                               // as transform_block finds its block and runs the two passes
-            const uint32_t m = lane / 6u, k6 = lane - 6u * m;
-            const bool is_c = k6 >= 4u;
-            const int16_t* src = is_c ? (k6 == 4u ? s_cb : s_cr) + m * 8u
-                                      : s_y + ((k6 >> 1) * 8u) * kPitchY + m * 16u + (k6 & 1u) * 8u;
-            const uint32_t pitch = is_c ? kPitchC : kPitchY;
+        if (lane < nb) {
             int d[8][8];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const uint4 q = *reinterpret_cast<const uint4*>(src + r * pitch);
-                fdct_row_packed(q.x, q.y, q.z, q.w, d[r]);
-            }
+            block_row_passes(s_y, s_cb, s_cr, lane, d);
 #pragma unroll
             for (int c = 0; c < 8; ++c) {
                 int col[8];
@@ -85,12 +62,7 @@ __global__ __launch_bounds__(kLanes) void amv_nr_sums_kernel(Source in, FrameGeo
                 for (int c = 0; c < 8; c += 2) line[r * 4 + (c >> 1)] = pack16(d[r][c], d[r][c + 1]);
         }
         wave_sync();                                   // every lane has its samples: the planes become the lines
-        if (lane < nb) {
-#pragma unroll
-            for (uint32_t i = 0; i < 8; ++i)           // granule i = positions 8 i .. 8 i + 7, where line_offset puts them
-                *reinterpret_cast<uint4*>(region + lane * 128u + ((i ^ (lane & 7u)) << 4)) =
-                    make_uint4(line[4 * i], line[4 * i + 1], line[4 * i + 2], line[4 * i + 3]);
-        }
+        if (lane < nb) store_line(region, lane, line);
         wave_sync();
         for (uint32_t l = 0; l < nb; ++l)              // the 64 lanes read one line's 128 bytes: two lanes a bank, the same word
             acc += *reinterpret_cast<const uint16_t*>(region + line_offset(l, lane));
@@ -101,16 +73,12 @@ __global__ __launch_bounds__(kLanes) void amv_nr_sums_kernel(Source in, FrameGeo
     if (wave == 0u) sums[(uint64_t)f * 64u + lane] = s_part[0][lane] + s_part[1][lane] + s_part[2][lane] + s_part[3][lane];
 }
 
-void launch_nr_sums(const uint8_t* pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n, const FrameGeom& g,
-                    uint32_t* sums, hipStream_t s) {
+void launch_nr_sums(const Source& in, uint32_t n, const FrameGeom& g, uint32_t* sums, hipStream_t s) {
     if (n == 0) return;
-    const uint32_t nseg = segs_per_row(g);
-    const uint32_t per_seg = (g.mcu_cols + nseg - 1) / nseg;      // the encoder's split: 11 columns -> 6 + 5
-    if (yuv)
-        hipLaunchKernelGGL(amv_nr_sums_kernel<true>, dim3(n), dim3(kLanes), 0, s, Source{nullptr, 0u, 0, *yuv}, g, nseg, per_seg, sums);
-    else
-        hipLaunchKernelGGL(amv_nr_sums_kernel<false>, dim3(n), dim3(kLanes), 0, s, Source{pix, pix_stride, is_bgr, YuvSource{}}, g, nseg,
-                           per_seg, sums);
+    const SegSplit sp = seg_split(g);                  // the encoder's split
+    with_source_kind(in, [&](auto yuv) {
+        hipLaunchKernelGGL(amv_nr_sums_kernel<decltype(yuv)::value>, dim3(n), dim3(kLanes), 0, s, in, g, sp.nseg, sp.per_seg, sums);
+    });
 }
 
 // Serial in n, one integer division per frame and lane.  Between two halvings it is a plain prefix sum over the frames'

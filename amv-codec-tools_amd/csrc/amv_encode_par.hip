@@ -35,18 +35,10 @@ using namespace enc;
 
 namespace {
 
-constexpr uint32_t kWaves = 4;                    // waves (segments in flight) per frame
-constexpr uint32_t kLanes = kWave * kWaves;
 constexpr uint32_t kOwnWords = 8;                 // a lane's scratch: 256 bits (a block takes ~41 on the bench stream)
 constexpr uint32_t kWindowWords = 1280;           // the round's bit string: 5 KB
 // LDS: four regions of planes / lines (32 KB), the scratch (8 KB), the window (5 KB), the code book (4 KB), the
 // symbol numbers (1 KB), the quantiser's multipliers (0.5 KB): 50.5 KB, three workgroups per CU
-constexpr uint32_t kRegionBytes = kPlaneSamples * 2;
-
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
 
 __device__ __forceinline__ uint32_t wave_excl_sum(uint32_t v, uint32_t lane, uint32_t& total) {
     uint32_t x = v;
@@ -264,14 +256,6 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
     uint32_t out_pos = 2;                             // bytes of the chunk written so far (FF D8 first)
     __syncthreads();
 
-    // where segment s lies, and whether there is one (very wide pictures: the balanced split can leave the last segment empty)
-    auto place = [&](uint32_t s, uint32_t& my, uint32_t& m0, uint32_t& cnt) {
-        my = s / nseg;
-        m0 = (s - my * nseg) * per_seg;
-        const bool has = s < segs && m0 < g.mcu_cols;
-        cnt = has ? min(per_seg, g.mcu_cols - m0) : 0u;
-        return has;
-    };
     // Whole bytes of the window's first `bits` bits leave for memory, 00 after every FF (escape_FF :282-336); after the
     // frame's last round the tail is padded with ones first (ff_mjpeg_encode_stuffing :338-343).  The unfinished byte moves
     // to the head of a cleared window; returns the bits it holds.  The whole workgroup calls it, behind a barrier.
@@ -311,7 +295,7 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
     for (uint32_t s0 = 0, round = 0; s0 < segs; s0 += kWaves, ++round) {
         const uint32_t s = s0 + wave;
         uint32_t my, m0, cnt;
-        const bool has_seg = place(s, my, m0, cnt);
+        const bool has_seg = seg_place(SegSplit{nseg, per_seg}, g, s, my, m0, cnt);
         const uint32_t nb = cnt * 6u;
         const bool live = lane < nb;
         const uint32_t k6 = lane % 6u;
@@ -327,6 +311,8 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
             wave_sync();                                          // every lane has its samples: the planes become the lines
             if (live) {
                 dc = (int)(int16_t)(line[0] & 0xffffu);
+                // store_line's loop, written out: through the helper this kernel's trellis instantiation came out a register
+                // short and 1 % slower (2.146 against 2.122 ms per 1 000 frames of 320x240)
 #pragma unroll
                 for (uint32_t i = 0; i < 8; ++i)
                     *reinterpret_cast<uint4*>(region + lane * 128u + ((i ^ (lane & 7u)) << 4)) =
@@ -424,30 +410,15 @@ __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
     }
 }
 
-void launch_encode_frames(const uint8_t* pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n, const FrameGeom& g,
-                          uint32_t qbias, const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens,
-                          uint32_t* retry_list, uint32_t* retry_count, hipStream_t s, const uint16_t* nr_offs, const TrellisArg* trellis) {
+void launch_encode_frames(const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, const Quantiser& quant,
+                          const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens, uint32_t* retry_list,
+                          uint32_t* retry_count, hipStream_t s) {
     if (n == 0) return;
-    const uint32_t nseg = segs_per_row(g);
-    const uint32_t per_seg = (g.mcu_cols + nseg - 1) / nseg;      // balanced: 11 columns -> 6 + 5
-    if (trellis && yuv)
-        hipLaunchKernelGGL((amv_encode_frame_kernel<true, TrellisArg>), dim3(n), dim3(kLanes), 0, s, Source{nullptr, 0u, 0, *yuv}, n, g, nseg, per_seg,
-                           qbias, d_img, tmp, bound, lens, retry_list, retry_count, *trellis);
-    else if (trellis)
-        hipLaunchKernelGGL((amv_encode_frame_kernel<false, TrellisArg>), dim3(n), dim3(kLanes), 0, s, Source{pix, pix_stride, is_bgr, YuvSource{}}, n, g,
-                           nseg, per_seg, qbias, d_img, tmp, bound, lens, retry_list, retry_count, *trellis);
-    else if (nr_offs && yuv)
-        hipLaunchKernelGGL((amv_encode_frame_kernel<true, const uint16_t*>), dim3(n), dim3(kLanes), 0, s, Source{nullptr, 0u, 0, *yuv}, n, g, nseg, per_seg,
-                           qbias, d_img, tmp, bound, lens, retry_list, retry_count, nr_offs);
-    else if (nr_offs)
-        hipLaunchKernelGGL((amv_encode_frame_kernel<false, const uint16_t*>), dim3(n), dim3(kLanes), 0, s, Source{pix, pix_stride, is_bgr, YuvSource{}}, n, g,
-                           nseg, per_seg, qbias, d_img, tmp, bound, lens, retry_list, retry_count, nr_offs);
-    else if (yuv)
-        hipLaunchKernelGGL(amv_encode_frame_kernel<true>, dim3(n), dim3(kLanes), 0, s, Source{nullptr, 0u, 0, *yuv}, n, g, nseg, per_seg,
-                           qbias, d_img, tmp, bound, lens, retry_list, retry_count);
-    else
-        hipLaunchKernelGGL(amv_encode_frame_kernel<false>, dim3(n), dim3(kLanes), 0, s, Source{pix, pix_stride, is_bgr, YuvSource{}}, n, g,
-                           nseg, per_seg, qbias, d_img, tmp, bound, lens, retry_list, retry_count);
+    const SegSplit sp = seg_split(g);
+    with_instantiation(in, quant, [&](auto yuv, auto... opt) {
+        hipLaunchKernelGGL((amv_encode_frame_kernel<decltype(yuv)::value, decltype(opt)...>), dim3(n), dim3(kLanes), 0, s, in, n, g, sp.nseg,
+                           sp.per_seg, qbias, d_img, tmp, bound, lens, retry_list, retry_count, opt...);
+    });
 }
 
 }  // namespace amv

@@ -2,6 +2,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <variant>
+
 #include "amv_tables.h"
 
 namespace amv {
@@ -89,6 +92,18 @@ struct FrameSel {
     uint32_t base;
     uint32_t round;   // items of this round; 0 = default launch
 };
+// The encoder's kernels read a FrameSel through these two: how many items the launch has (a round: what is left of the
+// list, or of the n frames, from base on, at most `round`), and the frame of item `item` (< sel_items); the item is also
+// the slot of the frame's dense lines.  (The reconstruction's select_frame, amv_block_load.h, has no count to give in a
+// default launch, where it trusts the grid: DESIGN.md 4.5.)
+__device__ __forceinline__ uint32_t sel_items(const FrameSel& sel, uint32_t n) {
+    if (!sel.round) return n;
+    const uint32_t have = sel.count ? *sel.count : n;
+    return have > sel.base ? min(sel.round, have - sel.base) : 0u;
+}
+__device__ __forceinline__ uint32_t sel_frame(const FrameSel& sel, uint32_t item) {
+    return sel.round ? (sel.list ? sel.list[sel.base + item] : sel.base + item) : item;
+}
 // records form -> dense lines coef[n][blocks][64] (amvhip_huffman_decode_dev): one wave per MCU-row segment, through the
 // reconstruction's reader (amv_block_load.h).  Frames whose rec_count is ~0 are left alone (the serial kernel writes them);
 // lines of blocks at or after a frame's first error are zeros.
@@ -123,34 +138,46 @@ struct YuvSource {
     uint64_t y_frame, c_frame;
     uint32_t c_rows422;
 };
-// The whole encoder, one workgroup per frame (amv_encode_par.hip): pixels (RGB24/BGR24, or *yuv when not null) ->
-// FF D8 + escaped scan + FF D9 in tmp[i*bound..], lens[i].  Frames whose bits do not fit the kernel's LDS window are
-// appended to retry_list / *retry_count for launch_forward + launch_pack (rounds).
-// nr_offs (here and in launch_forward / _yuv): null, or the noise-reduction offsets of the call's frames (uint16 [n][64],
-// amv_nr_plan.h: launch_nr_chain writes them) -- the kernels' second instantiation denoises with them before it quantises.
-// trellis (the same three launchers): null, or the trellis quantiser's lambda (amv_trellis_plan.h) -- the kernels' third
-// instantiation searches the AC levels of every block instead of rounding them (nr_offs is then not looked at).
+namespace enc {
+// Where a call's pixels are, as the encoder kernels take it: packed RGB24 / BGR24 frames, rows pix_stride apart (is_bgr: the
+// byte order), or the planes of yuv.  planar says which half is live: the entries check that half by it, the launchers
+// pick the kernels' kYuv by it (the kernels themselves do not read it).
+struct Source {
+    const uint8_t* pix;
+    uint32_t pix_stride;
+    int is_bgr;
+    YuvSource yuv;
+    uint32_t planar;
+};
+}  // namespace enc
+using enc::Source;
+inline Source rgb_source(const uint8_t* pix, uint32_t pix_stride, int is_bgr) { return Source{pix, pix_stride, is_bgr, YuvSource{}, 0u}; }
+inline Source yuv_source(const YuvSource& yuv) { return Source{nullptr, 0u, 0, yuv, 1u}; }
+// How the AC coefficients of a call become levels, one of three: rounded (dct_quantize_c); rounded after denoising with the
+// noise-reduction offsets of the call's frames (uint16 [n][64], amv_nr_plan.h: launch_nr_chain writes them); or searched per
+// block by the trellis quantiser with this lambda (amv_trellis_plan.h).  Each is an instantiation of the encoder kernels
+// (their one optional trailing argument: none, the offsets, the TrellisArg).
+struct PlainQuant {};
 struct TrellisArg { uint32_t lambda; };
-void launch_encode_frames(const uint8_t* pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n, const FrameGeom& g,
-                          uint32_t qbias, const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens,
-                          uint32_t* retry_list, uint32_t* retry_count, hipStream_t s, const uint16_t* nr_offs = nullptr,
-                          const TrellisArg* trellis = nullptr);
+using Quantiser = std::variant<PlainQuant, const uint16_t*, TrellisArg>;
+// The whole encoder, one workgroup per frame (amv_encode_par.hip): pixels -> FF D8 + escaped scan + FF D9 in
+// tmp[i*bound..], lens[i].  Frames whose bits do not fit the kernel's LDS window are appended to retry_list /
+// *retry_count for launch_forward + launch_pack (rounds).
+void launch_encode_frames(const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, const Quantiser& quant,
+                          const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens, uint32_t* retry_list,
+                          uint32_t* retry_count, hipStream_t s);
 // The reference's -nr (amv_encode_nr.hip, arithmetic in amv_nr_plan.h).  launch_nr_sums: per frame, the sum of the fdct
 // outputs' magnitudes per position over the encoder's own blocks -> sums uint32 [n][64] (position 0: the sum of DC + 8192).
 // launch_nr_chain: one wave walks the n frames -- halve if due, the frame's offsets -> offs uint16 [n][64] (entry c * 8 + r),
 // add the frame's sums and `blocks` -- from the caller's state (int32 [65] on the device) to the state after the last frame.
-void launch_nr_sums(const uint8_t* pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n, const FrameGeom& g,
-                    uint32_t* sums, hipStream_t s);
+void launch_nr_sums(const Source& in, uint32_t n, const FrameGeom& g, uint32_t* sums, hipStream_t s);
 void launch_nr_chain(const uint32_t* sums, uint32_t n, uint32_t blocks, uint32_t nr, int32_t* state, uint16_t* offs, hipStream_t s);
 // The two-stage route (amv_encode.hip).  colour conversion + level shift + forward DCT + quantise -> dense lines
 // coef [..][blocks][64] int16 scan order; entropy coder, one lane per frame -> tmp[frame*bound..], lens[frame].
 // sel: default (round == 0) = frames 0 .. n with lines at the frame's own place; round = items base .. base + round,
 // item p = frame list[p] (p < *count), lines in slot p - base.  items: upper bound of the work (grid size).
-void launch_forward(const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, const FrameSel& sel, uint32_t items,
-                    const FrameGeom& g, uint32_t qbias, int16_t* coef, hipStream_t s, const uint16_t* nr_offs = nullptr,
-                    const TrellisArg* trellis = nullptr);
-void launch_forward_yuv(const YuvSource& src, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, uint32_t qbias,
-                        int16_t* coef, hipStream_t s, const uint16_t* nr_offs = nullptr, const TrellisArg* trellis = nullptr);
+void launch_forward(const Source& in, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, uint32_t qbias,
+                    const Quantiser& quant, int16_t* coef, hipStream_t s);
 void launch_pack(const int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g,
                  const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens, hipStream_t s);
 // exclusive scan of lens -> offs (single workgroup), then gather tmp -> blob.  A chunk that would end past

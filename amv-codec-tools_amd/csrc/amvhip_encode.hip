@@ -3,30 +3,71 @@
 
 using namespace amv;
 
-extern "C" int amvhip_encode_coefs_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
-                                       uint32_t qbias, int16_t* d_coef, void* stream) {
+// What an entry asks of the AC quantiser, one of three: nothing; the reference's -nr for a stream (amv_encode_nr.hip,
+// amv_nr_plan.h) from the state the caller carries -- with nr == 0 the plain route, the state left alone; or the trellis
+// search (amv_trellis_plan.h; trellis_lane in amv_encode_common.h).
+struct NrRequest {
+    uint32_t nr;
+    int32_t* state;
+};
+using QuantRequest = std::variant<PlainQuant, NrRequest, TrellisArg>;
+
+extern "C" uint32_t amvhip_encode_nr_max(uint32_t w, uint32_t h) {
+    if (!encode_size_ok(w, h, 0u)) return 0u;
+    return nr_max(make_geom(w, h).blocks);
+}
+extern "C" uint32_t amvhip_encode_trellis_lambda_max(void) { return trellis_lambda_max(); }
+extern "C" uint32_t amvhip_encode_trellis_lambda(uint32_t qscale) { return trellis_lambda_of_qscale(qscale); }
+
+// what a request asks beyond the plain entries' checks; 0 = go on
+static int trellis_args_ok(amvhip_ctx* c, uint32_t lambda) {
+    if (lambda > trellis_lambda_max())
+        return fail(c, AMVHIP_ERR_ARG, "encode_trellis: lambda %u is more than amvhip_encode_trellis_lambda_max() = %u", lambda, trellis_lambda_max());
+    return AMVHIP_OK;
+}
+static int quant_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const QuantRequest& req) {
+    if (const TrellisArg* t = std::get_if<TrellisArg>(&req)) return trellis_args_ok(c, t->lambda);
+    const NrRequest* q = std::get_if<NrRequest>(&req);
+    if (!q) return AMVHIP_OK;
+    if (q->nr > amvhip_encode_nr_max(w, h))
+        return fail(c, AMVHIP_ERR_ARG, "encode_nr: nr %u is more than amvhip_encode_nr_max(%u, %u) = %u", q->nr, w, h, amvhip_encode_nr_max(w, h));
+    if (n && q->nr && (!q->state || ((uintptr_t)q->state & 3u))) return fail(c, AMVHIP_ERR_ARG, "encode_nr: the state is null or not 4-byte aligned");
+    return AMVHIP_OK;
+}
+
+// amvhip_encode_coefs_dev and its trellis form: amv_forward_kernel's lines for the caller (no workspace, so no lock)
+static int encode_coefs(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias,
+                        const Quantiser& quant, int16_t* d_coef, void* stream, const char* what) {
     if (!c) return AMVHIP_ERR_ARG;
     if (!encode_size_ok(w, h, qbias) || pix_stride < w * 3 || (n && (!d_pix || !d_coef)))
         return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
     if ((uintptr_t)d_coef & 15u) return fail(c, AMVHIP_ERR_ARG, "encode: coef must be 16-byte aligned");
+    if (const TrellisArg* t = std::get_if<TrellisArg>(&quant))
+        if (int r = trellis_args_ok(c, t->lambda)) return r;
     if (int r = use_device(c)) return r;
-    const FrameGeom g = make_geom(w, h);
     {
         Timed t(c, AMVHIP_K_FDCT, (hipStream_t)stream);
-        launch_forward(d_pix, pix_stride, is_bgr, n, kAllFrames, n, g, qbias, d_coef, (hipStream_t)stream);
+        launch_forward(rgb_source(d_pix, pix_stride, is_bgr), n, kAllFrames, n, make_geom(w, h), qbias, quant, d_coef, (hipStream_t)stream);
     }
-    return check_launch(c, "forward");
+    return check_launch(c, what);
 }
 
-// Pixels -> chunks for n frames, RGB (yuv == nullptr) or planar YUVJ420P (the context is locked).  The one-kernel
-// encoder takes the batch; what it hands back -- and the whole batch in AMVHIP_ENTROPY_SERIAL mode -- goes through
-// amv_forward_kernel + amv_pack_kernel a round of dense lines at a time (with a list the count is on the device: the
-// rounds past it find nothing to do and leave at once -- usually all of them).  nr_offs: null, or the frames'
-// noise-reduction offsets (encode_nr_core): both routes then run their denoising instantiation.  trellis: null, or the
-// trellis quantiser's lambda: both routes then run their searching instantiation.
-static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n,
-                       const FrameGeom& g, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
-                       hipStream_t stream, const uint16_t* nr_offs = nullptr, const TrellisArg* trellis = nullptr) {
+extern "C" int amvhip_encode_coefs_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                                       uint32_t qbias, int16_t* d_coef, void* stream) {
+    return encode_coefs(c, d_pix, pix_stride, is_bgr, n, w, h, qbias, PlainQuant{}, d_coef, stream, "forward");
+}
+
+extern "C" int amvhip_encode_trellis_coefs_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
+                                               uint32_t h, uint32_t qbias, uint32_t lambda, int16_t* d_coef, void* stream) {
+    return encode_coefs(c, d_pix, pix_stride, is_bgr, n, w, h, qbias, TrellisArg{lambda}, d_coef, stream, "forward (trellis)");
+}
+
+// Pixels -> chunks for n frames (the context is locked).  The one-kernel encoder takes the batch; what it hands back -- and
+// the whole batch in AMVHIP_ENTROPY_SERIAL mode -- goes through amv_forward_kernel + amv_pack_kernel a round of dense lines
+// at a time (with a list the count is on the device: the rounds past it find nothing to do and leave at once -- usually all
+// of them).  Both routes run the instantiation of `quant`.
+static int encode_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, const Quantiser& quant, uint8_t* d_blob,
+                       uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
     const uint32_t bound = amvhip_encode_bound(g.width, g.height);
     const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
     const uint32_t round = fallback_round(n, g, 1024u, 2u);
@@ -40,8 +81,7 @@ static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride,
     const bool fused = c->entropy_mode != AMVHIP_ENTROPY_SERIAL;
     if (fused) {
         Timed t(c, AMVHIP_K_PACK, stream);
-        launch_encode_frames(d_pix, pix_stride, is_bgr, yuv, n, g, qbias, book, (uint8_t*)c->tmp.p, bound, d_lens, retry_list,
-                             retry_count, stream, nr_offs, trellis);
+        launch_encode_frames(in, n, g, qbias, quant, book, (uint8_t*)c->tmp.p, bound, d_lens, retry_list, retry_count, stream);
     }
     if (int r = check_launch(c, "encode_frames")) return r;
     for (uint32_t base = 0; base < n; base += round) {
@@ -49,8 +89,7 @@ static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride,
         const FrameSel sel{fused ? retry_list : nullptr, fused ? retry_count : nullptr, base, items};
         {
             Timed t(c, AMVHIP_K_FDCT, stream);
-            if (yuv) launch_forward_yuv(*yuv, n, sel, items, g, qbias, (int16_t*)c->coef.p, stream, nr_offs, trellis);
-            else launch_forward(d_pix, pix_stride, is_bgr, n, sel, items, g, qbias, (int16_t*)c->coef.p, stream, nr_offs, trellis);
+            launch_forward(in, n, sel, items, g, qbias, quant, (int16_t*)c->coef.p, stream);
         }
         {
             Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
@@ -65,188 +104,92 @@ static int encode_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride,
     return check_launch(c, "compact");
 }
 
-extern "C" int amvhip_encode_batch_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
-                                       uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
-    if (!c) return AMVHIP_ERR_ARG;
-    if (!encode_size_ok(w, h, qbias) || pix_stride < w * 3 || (n && !d_pix))
-        return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
-    if (n && (!d_blob || !d_offs || !d_lens)) return fail(c, AMVHIP_ERR_ARG, "encode: null output");
-    if (n == 0) return AMVHIP_OK;
-    if (int r = use_device(c)) return r;
-    std::lock_guard<std::mutex> lk(c->mu);
-    return encode_core(c, d_pix, pix_stride, is_bgr, nullptr, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens,
-                       (hipStream_t)stream);
+// Passes A and B in front of encode_core (the context is locked; nr > 0): the frames' sums, the chain from d_state to
+// d_state, and the encoder with the offsets the chain wrote.
+static int encode_nr_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, uint32_t nr, int32_t* d_state,
+                          uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
+    const NrPlan plan = nr_plan(n);
+    if (int r = ensure(c, c->nr_ws, plan.bytes)) return r;
+    uint32_t* sums = (uint32_t*)((uint8_t*)c->nr_ws.p + plan.sums);
+    uint16_t* offsets = (uint16_t*)((uint8_t*)c->nr_ws.p + plan.offsets);
+    launch_nr_sums(in, n, g, sums, stream);
+    launch_nr_chain(sums, n, g.blocks, nr, d_state, offsets, stream);
+    if (int r = check_launch(c, "nr sums + chain")) return r;
+    return encode_core(c, in, n, g, qbias, offsets, d_blob, blob_cap, d_offs, d_lens, stream);
 }
 
-static int encode_yuv_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr, uint32_t y_stride, uint32_t c_stride,
-                          uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t rows422, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias,
-                          uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+// Every device-pointer encoder whole: the checks of the live half of `in`, of the outputs and of the request, n == 0, the
+// device, the lock (held from the workspace's allocation to the last launch), the request's core.  req's state is on the device.
+static int encode_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req,
+                      uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
     if (!c) return AMVHIP_ERR_ARG;
-    if (!encode_size_ok(w, h, qbias) || y_stride < w || c_stride < w / 2 ||
-        (n && (!d_y || !d_cb || !d_cr || !d_blob || !d_offs || !d_lens)))
-        return fail(c, AMVHIP_ERR_ARG, "encode_yuv: bad argument (width/height must be even)");
+    const bool no_out = n && (!d_blob || !d_offs || !d_lens);
+    if (in.planar) {
+        if (!encode_size_ok(w, h, qbias) || in.yuv.y_stride < w || in.yuv.c_stride < w / 2 || (n && (!in.yuv.y || !in.yuv.cb || !in.yuv.cr)) || no_out)
+            return fail(c, AMVHIP_ERR_ARG, "encode_yuv: bad argument (width/height must be even)");
+    } else {
+        if (!encode_size_ok(w, h, qbias) || in.pix_stride < w * 3 || (n && !in.pix))
+            return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
+        if (no_out) return fail(c, AMVHIP_ERR_ARG, "encode: null output");
+    }
+    if (int r = quant_args_ok(c, n, w, h, req)) return r;
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
-    const YuvSource yuv{d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, rows422};
-    return encode_core(c, nullptr, 0u, 0, &yuv, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+    const FrameGeom g = make_geom(w, h);
+    const NrRequest* q = std::get_if<NrRequest>(&req);
+    if (q && q->nr) return encode_nr_core(c, in, n, g, qbias, q->nr, q->state, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+    const TrellisArg* t = std::get_if<TrellisArg>(&req);
+    return encode_core(c, in, n, g, qbias, t ? Quantiser{*t} : Quantiser{PlainQuant{}}, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+}
+
+extern "C" int amvhip_encode_batch_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                                       uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+    return encode_dev(c, rgb_source(d_pix, pix_stride, is_bgr), n, w, h, qbias, PlainQuant{}, d_blob, blob_cap, d_offs, d_lens, stream);
+}
+
+extern "C" int amvhip_encode_nr_stream_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                                           uint32_t qbias, uint32_t nr, int32_t* d_state, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs,
+                                           uint32_t* d_lens, void* stream) {
+    return encode_dev(c, rgb_source(d_pix, pix_stride, is_bgr), n, w, h, qbias, NrRequest{nr, d_state}, d_blob, blob_cap, d_offs, d_lens, stream);
+}
+
+extern "C" int amvhip_encode_trellis_batch_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
+                                               uint32_t h, uint32_t qbias, uint32_t lambda, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs,
+                                               uint32_t* d_lens, void* stream) {
+    return encode_dev(c, rgb_source(d_pix, pix_stride, is_bgr), n, w, h, qbias, TrellisArg{lambda}, d_blob, blob_cap, d_offs, d_lens, stream);
 }
 
 extern "C" int amvhip_encode_yuv420_batch_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr, uint32_t y_stride,
                                               uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
                                               uint32_t h, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
                                               void* stream) {
-    return encode_yuv_dev(c, d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, d_blob, blob_cap, d_offs,
-                          d_lens, stream);
+    return encode_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, qbias, PlainQuant{}, d_blob,
+                      blob_cap, d_offs, d_lens, stream);
 }
 
 extern "C" int amvhip_encode_yuv422_batch_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr, uint32_t y_stride,
                                               uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
                                               uint32_t h, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
                                               void* stream) {
-    return encode_yuv_dev(c, d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 1u, n, w, h, qbias, d_blob, blob_cap, d_offs,
-                          d_lens, stream);
-}
-
-// ---- the reference's -nr for a stream (amv_encode_nr.hip, amv_nr_plan.h) ------------------------------------------------
-
-extern "C" uint32_t amvhip_encode_nr_max(uint32_t w, uint32_t h) {
-    if (!encode_size_ok(w, h, 0u)) return 0u;
-    return nr_max(make_geom(w, h).blocks);
-}
-
-// what the nr entries ask beyond the plain ones'; 0 = go on
-static int nr_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t nr, const int32_t* state) {
-    if (nr > amvhip_encode_nr_max(w, h))
-        return fail(c, AMVHIP_ERR_ARG, "encode_nr: nr %u is more than amvhip_encode_nr_max(%u, %u) = %u", nr, w, h, amvhip_encode_nr_max(w, h));
-    if (n && nr && (!state || ((uintptr_t)state & 3u))) return fail(c, AMVHIP_ERR_ARG, "encode_nr: the state is null or not 4-byte aligned");
-    return AMVHIP_OK;
-}
-
-// Passes A and B in front of encode_core (the context is locked; nr > 0): the frames' sums, the chain from d_state to
-// d_state, and the encoder with the offsets the chain wrote.
-static int encode_nr_core(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, const YuvSource* yuv, uint32_t n,
-                          const FrameGeom& g, uint32_t qbias, uint32_t nr, int32_t* d_state, uint8_t* d_blob, uint64_t blob_cap,
-                          uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
-    const NrPlan plan = nr_plan(n);
-    if (int r = ensure(c, c->nr_ws, plan.bytes)) return r;
-    uint32_t* sums = (uint32_t*)((uint8_t*)c->nr_ws.p + plan.sums);
-    uint16_t* offsets = (uint16_t*)((uint8_t*)c->nr_ws.p + plan.offsets);
-    launch_nr_sums(d_pix, pix_stride, is_bgr, yuv, n, g, sums, stream);
-    launch_nr_chain(sums, n, g.blocks, nr, d_state, offsets, stream);
-    if (int r = check_launch(c, "nr sums + chain")) return r;
-    return encode_core(c, d_pix, pix_stride, is_bgr, yuv, n, g, qbias, d_blob, blob_cap, d_offs, d_lens, stream, offsets);
-}
-
-extern "C" int amvhip_encode_nr_stream_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
-                                           uint32_t qbias, uint32_t nr, int32_t* d_state, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs,
-                                           uint32_t* d_lens, void* stream) {
-    if (!c) return AMVHIP_ERR_ARG;
-    if (!encode_size_ok(w, h, qbias) || pix_stride < w * 3 || (n && !d_pix))
-        return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
-    if (n && (!d_blob || !d_offs || !d_lens)) return fail(c, AMVHIP_ERR_ARG, "encode: null output");
-    if (int r = nr_args_ok(c, n, w, h, nr, d_state)) return r;
-    if (n == 0) return AMVHIP_OK;
-    if (int r = use_device(c)) return r;
-    std::lock_guard<std::mutex> lk(c->mu);
-    if (nr == 0u)
-        return encode_core(c, d_pix, pix_stride, is_bgr, nullptr, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens,
-                           (hipStream_t)stream);
-    return encode_nr_core(c, d_pix, pix_stride, is_bgr, nullptr, n, make_geom(w, h), qbias, nr, d_state, d_blob, blob_cap, d_offs, d_lens,
-                          (hipStream_t)stream);
+    return encode_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 1u}), n, w, h, qbias, PlainQuant{}, d_blob,
+                      blob_cap, d_offs, d_lens, stream);
 }
 
 extern "C" int amvhip_encode_yuv420_nr_stream_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr, uint32_t y_stride,
                                                   uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
                                                   uint32_t h, uint32_t qbias, uint32_t nr, int32_t* d_state, uint8_t* d_blob, uint64_t blob_cap,
                                                   uint64_t* d_offs, uint32_t* d_lens, void* stream) {
-    if (!c) return AMVHIP_ERR_ARG;
-    if (!encode_size_ok(w, h, qbias) || y_stride < w || c_stride < w / 2 ||
-        (n && (!d_y || !d_cb || !d_cr || !d_blob || !d_offs || !d_lens)))
-        return fail(c, AMVHIP_ERR_ARG, "encode_yuv: bad argument (width/height must be even)");
-    if (int r = nr_args_ok(c, n, w, h, nr, d_state)) return r;
-    if (n == 0) return AMVHIP_OK;
-    if (int r = use_device(c)) return r;
-    std::lock_guard<std::mutex> lk(c->mu);
-    const YuvSource yuv{d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u};
-    if (nr == 0u)
-        return encode_core(c, nullptr, 0u, 0, &yuv, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
-    return encode_nr_core(c, nullptr, 0u, 0, &yuv, n, make_geom(w, h), qbias, nr, d_state, d_blob, blob_cap, d_offs, d_lens,
-                          (hipStream_t)stream);
-}
-
-// ---- trellis quantisation (amv_trellis_plan.h; trellis_lane in amv_encode_common.h) ------------------------------------------
-
-extern "C" uint32_t amvhip_encode_trellis_lambda_max(void) { return trellis_lambda_max(); }
-extern "C" uint32_t amvhip_encode_trellis_lambda(uint32_t qscale) { return trellis_lambda_of_qscale(qscale); }
-
-static int trellis_args_ok(amvhip_ctx* c, uint32_t lambda) {
-    if (lambda > trellis_lambda_max())
-        return fail(c, AMVHIP_ERR_ARG, "encode_trellis: lambda %u is more than amvhip_encode_trellis_lambda_max() = %u", lambda, trellis_lambda_max());
-    return AMVHIP_OK;
-}
-
-extern "C" int amvhip_encode_trellis_coefs_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
-                                               uint32_t h, uint32_t qbias, uint32_t lambda, int16_t* d_coef, void* stream) {
-    if (!c) return AMVHIP_ERR_ARG;
-    if (!encode_size_ok(w, h, qbias) || pix_stride < w * 3 || (n && (!d_pix || !d_coef)))
-        return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
-    if ((uintptr_t)d_coef & 15u) return fail(c, AMVHIP_ERR_ARG, "encode: coef must be 16-byte aligned");
-    if (int r = trellis_args_ok(c, lambda)) return r;
-    if (int r = use_device(c)) return r;
-    const FrameGeom g = make_geom(w, h);
-    const TrellisArg trellis{lambda};
-    {
-        Timed t(c, AMVHIP_K_FDCT, (hipStream_t)stream);
-        launch_forward(d_pix, pix_stride, is_bgr, n, kAllFrames, n, g, qbias, d_coef, (hipStream_t)stream, nullptr, &trellis);
-    }
-    return check_launch(c, "forward (trellis)");
-}
-
-extern "C" int amvhip_encode_trellis_batch_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
-                                               uint32_t h, uint32_t qbias, uint32_t lambda, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs,
-                                               uint32_t* d_lens, void* stream) {
-    if (!c) return AMVHIP_ERR_ARG;
-    if (!encode_size_ok(w, h, qbias) || pix_stride < w * 3 || (n && !d_pix))
-        return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
-    if (n && (!d_blob || !d_offs || !d_lens)) return fail(c, AMVHIP_ERR_ARG, "encode: null output");
-    if (int r = trellis_args_ok(c, lambda)) return r;
-    if (n == 0) return AMVHIP_OK;
-    if (int r = use_device(c)) return r;
-    std::lock_guard<std::mutex> lk(c->mu);
-    const TrellisArg trellis{lambda};
-    return encode_core(c, d_pix, pix_stride, is_bgr, nullptr, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens,
-                       (hipStream_t)stream, nullptr, &trellis);
+    return encode_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, qbias, NrRequest{nr, d_state},
+                      d_blob, blob_cap, d_offs, d_lens, stream);
 }
 
 extern "C" int amvhip_encode_yuv420_trellis_batch_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr,
                                                       uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
                                                       uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, uint32_t lambda, uint8_t* d_blob,
                                                       uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
-    if (!c) return AMVHIP_ERR_ARG;
-    if (!encode_size_ok(w, h, qbias) || y_stride < w || c_stride < w / 2 ||
-        (n && (!d_y || !d_cb || !d_cr || !d_blob || !d_offs || !d_lens)))
-        return fail(c, AMVHIP_ERR_ARG, "encode_yuv: bad argument (width/height must be even)");
-    if (int r = trellis_args_ok(c, lambda)) return r;
-    if (n == 0) return AMVHIP_OK;
-    if (int r = use_device(c)) return r;
-    std::lock_guard<std::mutex> lk(c->mu);
-    const YuvSource yuv{d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u};
-    const TrellisArg trellis{lambda};
-    return encode_core(c, nullptr, 0u, 0, &yuv, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream, nullptr,
-                       &trellis);
-}
-
-// the host-buffer forms' state: up to the device before the call, back after it (the caller holds c->hmu)
-static int nr_state_up(amvhip_ctx* c, uint32_t nr, const int32_t* state, hipStream_t hs) {
-    if (nr == 0u) return AMVHIP_OK;
-    return stage(c, c->nr_state, kNrStateWords * 4u, state, kNrStateWords * 4u, hs);
-}
-static int nr_state_down(amvhip_ctx* c, uint32_t nr, int32_t* state, hipStream_t hs) {
-    if (nr == 0u) return AMVHIP_OK;
-    HIP_TRY(c, hipMemcpyAsync(state, c->nr_state.p, kNrStateWords * 4u, hipMemcpyDeviceToHost, hs));
-    HIP_TRY(c, hipStreamSynchronize(hs));
-    return AMVHIP_OK;
+    return encode_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, qbias, TrellisArg{lambda},
+                      d_blob, blob_cap, d_offs, d_lens, stream);
 }
 
 // the device-to-host half of the host-buffer encoders: offs/lens, then the chunks
@@ -264,120 +207,115 @@ static int encode_fetch(amvhip_ctx* c, hipStream_t hs, uint32_t n, uint8_t* blob
     return AMVHIP_OK;
 }
 
-// state: null for the plain entry; otherwise the nr entry's (with nr == 0 it goes through the plain route and stays as it was)
-static int encode_rgb_host(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
-                           uint32_t qbias, uint32_t nr, int32_t* state, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens,
-                           const uint32_t* lambda = nullptr) {
-    if (!c) return AMVHIP_ERR_ARG;
-    if (n && (!pix || !blob || !offs || !lens)) return fail(c, AMVHIP_ERR_ARG, "encode: null argument");
-    if (int r = nr_args_ok(c, n, w, h, nr, state)) return r;
-    if (lambda)
-        if (int r = trellis_args_ok(c, *lambda)) return r;
+// The host-buffer forms behind their own checks of the pointers and strides: the request's checks and n == 0 before anything
+// is staged; then, with c->hmu held round the staging buffers (one host-buffer call at a time), stage_in(hs, in) queues the
+// pixels' way to c->h_in and says where they are, the state of a request with nr > 0 goes up to the device before the call
+// and comes back after it, and the chunks follow.  req's state is the caller's, on the host.
+template <class StageIn>
+static int encode_host(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, QuantRequest req, uint8_t* blob, uint64_t blob_cap,
+                       uint64_t* offs, uint32_t* lens, StageIn&& stage_in) {
+    if (int r = quant_args_ok(c, n, w, h, req)) return r;
     if (n == 0) return AMVHIP_OK;
     hipStream_t hs;
     if (int r = host_stream(c, &hs)) return r;
-    const size_t in_bytes = (size_t)pix_stride * h * n;
-    std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
-    if (int r = stage(c, c->h_in, in_bytes, pix, in_bytes, hs)) return r;
-    if (int r = ensure(c, c->h_out, blob_cap + 16)) return r;
+    std::lock_guard<std::mutex> hlk(c->hmu);
+    if (int r = ensure(c, c->h_out, blob_cap + 16)) return r;   // (before a copy from the caller's memory is queued)
     if (int r = ensure(c, c->h_offs, (size_t)n * 8)) return r;
     if (int r = ensure(c, c->h_lens, (size_t)n * 4)) return r;
-    if (int r = nr_state_up(c, nr, state, hs)) return r;
-    if (int r = lambda ? amvhip_encode_trellis_batch_dev(c, (const uint8_t*)c->h_in.p, pix_stride, is_bgr, n, w, h, qbias, *lambda,
-                                                         (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs)
-                : nr   ? amvhip_encode_nr_stream_dev(c, (const uint8_t*)c->h_in.p, pix_stride, is_bgr, n, w, h, qbias, nr, (int32_t*)c->nr_state.p,
-                                                     (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs)
-                   : amvhip_encode_batch_dev(c, (const uint8_t*)c->h_in.p, pix_stride, is_bgr, n, w, h, qbias,
-                                             (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p,
-                                             (uint32_t*)c->h_lens.p, hs))
-        return r;
-    if (int r = nr_state_down(c, nr, state, hs)) return r;   // (the state has moved on even where the chunks do not fit the blob)
+    Source in;
+    if (int r = stage_in(hs, in)) return r;
+    NrRequest* q = std::get_if<NrRequest>(&req);
+    int32_t* const state = q && q->nr ? q->state : nullptr;
+    if (state) {                               // req is this call's copy: from here on its state is the device's, as encode_dev wants it
+        if (int r = stage(c, c->nr_state, kNrStateWords * 4u, state, kNrStateWords * 4u, hs)) return r;
+        q->state = (int32_t*)c->nr_state.p;
+    }
+    if (int r = encode_dev(c, in, n, w, h, qbias, req, (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs)) return r;
+    if (state) {                               // (the state has moved on even where the chunks do not fit the blob)
+        HIP_TRY(c, hipMemcpyAsync(state, c->nr_state.p, kNrStateWords * 4u, hipMemcpyDeviceToHost, hs));
+        HIP_TRY(c, hipStreamSynchronize(hs));
+    }
     return encode_fetch(c, hs, n, blob, blob_cap, offs, lens);
+}
+
+static int encode_rgb_host(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                           uint32_t qbias, const QuantRequest& req, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (n && (!pix || !blob || !offs || !lens)) return fail(c, AMVHIP_ERR_ARG, "encode: null argument");
+    return encode_host(c, n, w, h, qbias, req, blob, blob_cap, offs, lens, [&](hipStream_t hs, Source& in) -> int {
+        const size_t in_bytes = (size_t)pix_stride * h * n;
+        if (int r = stage(c, c->h_in, in_bytes, pix, in_bytes, hs)) return r;
+        in = rgb_source((const uint8_t*)c->h_in.p, pix_stride, is_bgr);
+        return AMVHIP_OK;
+    });
 }
 
 extern "C" int amvhip_encode_batch(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
                                    uint32_t qbias, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
-    return encode_rgb_host(c, pix, pix_stride, is_bgr, n, w, h, qbias, 0u, nullptr, blob, blob_cap, offs, lens);
+    return encode_rgb_host(c, pix, pix_stride, is_bgr, n, w, h, qbias, PlainQuant{}, blob, blob_cap, offs, lens);
 }
 
 extern "C" int amvhip_encode_nr_stream(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
                                        uint32_t qbias, uint32_t nr, int32_t* state, uint8_t* blob, uint64_t blob_cap, uint64_t* offs,
                                        uint32_t* lens) {
-    return encode_rgb_host(c, pix, pix_stride, is_bgr, n, w, h, qbias, nr, state, blob, blob_cap, offs, lens);
+    return encode_rgb_host(c, pix, pix_stride, is_bgr, n, w, h, qbias, NrRequest{nr, state}, blob, blob_cap, offs, lens);
 }
 
 extern "C" int amvhip_encode_trellis_batch(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
                                            uint32_t qbias, uint32_t lambda, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
-    return encode_rgb_host(c, pix, pix_stride, is_bgr, n, w, h, qbias, 0u, nullptr, blob, blob_cap, offs, lens, &lambda);
+    return encode_rgb_host(c, pix, pix_stride, is_bgr, n, w, h, qbias, TrellisArg{lambda}, blob, blob_cap, offs, lens);
 }
 
 static int encode_yuv_host(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride, uint32_t c_stride,
                            uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t rows422, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias,
-                           uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens, uint32_t nr = 0u, int32_t* state = nullptr,
-                           const uint32_t* lambda = nullptr) {
+                           const QuantRequest& req, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
     if (!c) return AMVHIP_ERR_ARG;
     if (!size_ok(w, h) || (w & 1) || (h & 1) || y_stride < w || c_stride < w / 2 || (n && (!y || !cb || !cr || !blob || !offs || !lens)))
         return fail(c, AMVHIP_ERR_ARG, "encode_yuv420: bad argument");
-    if (int r = nr_args_ok(c, n, w, h, nr, state)) return r;
-    if (lambda)
-        if (int r = trellis_args_ok(c, *lambda)) return r;
-    if (n == 0) return AMVHIP_OK;
-    hipStream_t hs;
-    if (int r = host_stream(c, &hs)) return r;
-    // staged tight: Y w*h, Cb, Cr (w/2 x h/2, or w/2 x h when the source is 4:2:2) per frame
-    const uint32_t cw = w / 2, chh = rows422 ? h : h / 2;
-    const uint64_t fb = (uint64_t)w * h + 2ull * cw * chh;
-    std::lock_guard<std::mutex> hlk(c->hmu);   // the staging buffers: one host-buffer call at a time
-    if (int r = ensure(c, c->h_in, fb * n)) return r;
-    if (int r = ensure(c, c->h_out, blob_cap + 16)) return r;
-    if (int r = ensure(c, c->h_offs, (size_t)n * 8)) return r;
-    if (int r = ensure(c, c->h_lens, (size_t)n * 4)) return r;
-    uint8_t* d = (uint8_t*)c->h_in.p;
-    for (uint32_t i = 0; i < n; ++i) {
-        HIP_TRY(c, hipMemcpy2DAsync(d + i * fb, w, y + i * y_frame_stride, y_stride, w, h, hipMemcpyHostToDevice, hs));
-        HIP_TRY(c, hipMemcpy2DAsync(d + i * fb + (uint64_t)w * h, cw, cb + i * c_frame_stride, c_stride, cw, chh, hipMemcpyHostToDevice, hs));
-        HIP_TRY(c, hipMemcpy2DAsync(d + i * fb + (uint64_t)w * h + (uint64_t)cw * chh, cw, cr + i * c_frame_stride, c_stride, cw, chh, hipMemcpyHostToDevice, hs));
-    }
-    if (int r = nr_state_up(c, nr, state, hs)) return r;
-    if (int r = lambda ? amvhip_encode_yuv420_trellis_batch_dev(c, d, d + (uint64_t)w * h, d + (uint64_t)w * h + (uint64_t)cw * chh, w, cw, fb, fb, n,
-                                                                w, h, qbias, *lambda, (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p,
-                                                                (uint32_t*)c->h_lens.p, hs)
-                : nr   ? amvhip_encode_yuv420_nr_stream_dev(c, d, d + (uint64_t)w * h, d + (uint64_t)w * h + (uint64_t)cw * chh, w, cw, fb, fb, n, w, h,
-                                                        qbias, nr, (int32_t*)c->nr_state.p, (uint8_t*)c->h_out.p, blob_cap,
-                                                        (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs)
-                   : encode_yuv_dev(c, d, d + (uint64_t)w * h, d + (uint64_t)w * h + (uint64_t)cw * chh, w, cw, fb, fb, rows422, n, w, h, qbias,
-                                    (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs))
-        return r;
-    if (int r = nr_state_down(c, nr, state, hs)) return r;   // (the state has moved on even where the chunks do not fit the blob)
-    return encode_fetch(c, hs, n, blob, blob_cap, offs, lens);
+    return encode_host(c, n, w, h, qbias, req, blob, blob_cap, offs, lens, [&](hipStream_t hs, Source& in) -> int {
+        // staged tight: Y w*h, Cb, Cr (w/2 x h/2, or w/2 x h when the source is 4:2:2) per frame
+        const uint32_t cw = w / 2, chh = rows422 ? h : h / 2;
+        const uint64_t fb = (uint64_t)w * h + 2ull * cw * chh;
+        if (int r = ensure(c, c->h_in, fb * n)) return r;
+        uint8_t* d = (uint8_t*)c->h_in.p;
+        for (uint32_t i = 0; i < n; ++i) {
+            HIP_TRY(c, hipMemcpy2DAsync(d + i * fb, w, y + i * y_frame_stride, y_stride, w, h, hipMemcpyHostToDevice, hs));
+            HIP_TRY(c, hipMemcpy2DAsync(d + i * fb + (uint64_t)w * h, cw, cb + i * c_frame_stride, c_stride, cw, chh, hipMemcpyHostToDevice, hs));
+            HIP_TRY(c, hipMemcpy2DAsync(d + i * fb + (uint64_t)w * h + (uint64_t)cw * chh, cw, cr + i * c_frame_stride, c_stride, cw, chh, hipMemcpyHostToDevice, hs));
+        }
+        in = yuv_source({d, d + (uint64_t)w * h, d + (uint64_t)w * h + (uint64_t)cw * chh, w, cw, fb, fb, rows422});
+        return AMVHIP_OK;
+    });
 }
 
 extern "C" int amvhip_encode_yuv420_nr_stream(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride,
                                               uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
                                               uint32_t h, uint32_t qbias, uint32_t nr, int32_t* state, uint8_t* blob, uint64_t blob_cap,
                                               uint64_t* offs, uint32_t* lens) {
-    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, blob, blob_cap, offs, lens, nr,
-                           state);
+    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, NrRequest{nr, state}, blob, blob_cap,
+                           offs, lens);
 }
 
 extern "C" int amvhip_encode_yuv420_trellis_batch(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride,
                                                   uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
                                                   uint32_t h, uint32_t qbias, uint32_t lambda, uint8_t* blob, uint64_t blob_cap, uint64_t* offs,
                                                   uint32_t* lens) {
-    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, blob, blob_cap, offs, lens, 0u,
-                           nullptr, &lambda);
+    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, TrellisArg{lambda}, blob, blob_cap,
+                           offs, lens);
 }
 
 extern "C" int amvhip_encode_yuv420_batch(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride,
                                           uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
                                           uint32_t h, uint32_t qbias, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
-    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, blob, blob_cap, offs, lens);
+    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, PlainQuant{}, blob, blob_cap, offs,
+                           lens);
 }
 
 extern "C" int amvhip_encode_yuv422_batch(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride,
                                           uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
                                           uint32_t h, uint32_t qbias, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
-    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 1u, n, w, h, qbias, blob, blob_cap, offs, lens);
+    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 1u, n, w, h, qbias, PlainQuant{}, blob, blob_cap, offs,
+                           lens);
 }
 
 // ---- picture rescale ------------------------------------------------------------------------------------------------
@@ -429,8 +367,8 @@ extern "C" int amvhip_resample_yuv420_dev(amvhip_ctx* c, const uint8_t* d_src_y,
 
 int amv::encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap,
                             uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
-    const YuvSource yuv = yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h));
-    return encode_core(c, nullptr, 0u, 0, &yuv, n, make_geom(w, h), qbias, d_blob, blob_cap, d_offs, d_lens, stream);
+    return encode_core(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, PlainQuant{}, d_blob,
+                       blob_cap, d_offs, d_lens, stream);
 }
 
 // rescale + encode in one call: what ffmpeg.c:757-814 does per picture (sws_scale, then avcodec_encode_video) for a

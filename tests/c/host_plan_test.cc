@@ -119,6 +119,35 @@ static int check_plans() {
     return 0;
 }
 
+// ---- seg_split, seg_place (amv_segment.h): the encoder's segments ------------------------------------------------------
+
+// every width up to the largest: a row's pieces are as many as the reconstruction's segments, no longer than one, in column
+// order without gap or overlap; an empty piece (false, cnt 0) only behind the row's last column; past the last row: none
+static int check_segments() {
+    for (uint32_t cols = 1; cols <= (AMVHIP_MAX_DIM + 15u) / 16u; ++cols)
+        for (uint32_t rows : {1u, 3u}) {
+            FrameGeom g{};
+            g.mcu_cols = cols;
+            g.mcu_rows = rows;
+            const SegSplit sp = seg_split(g);
+            if (sp.nseg != segs_per_row(g) || sp.per_seg > kSegMcus || (uint64_t)sp.nseg * sp.per_seg < cols) return printf("split %u\n", cols), 1;
+            for (uint32_t s = 0; s < (rows + 1u) * sp.nseg; ++s) {
+                uint32_t my = ~0u, m0 = ~0u, cnt = ~0u;
+                const bool has = seg_place(sp, g, s, my, m0, cnt);
+                const uint32_t piece = s % sp.nseg, from = piece * sp.per_seg;
+                const uint32_t want = s / sp.nseg < rows && from < cols ? std::min(sp.per_seg, cols - from) : 0u;
+                if (has != (want != 0u) || cnt != want || (has && (my != s / sp.nseg || m0 != from)))
+                    return printf("place cols=%u rows=%u s=%u: %d my %u m0 %u cnt %u\n", cols, rows, s, (int)has, my, m0, cnt), 1;
+            }
+            ++cases;
+        }
+    FrameGeom wide{};                                   // 11 columns: 6 + 5, not 10 + 1
+    wide.mcu_cols = 11;
+    wide.mcu_rows = 1;
+    if (seg_split(wide).per_seg != 6) return printf("11 columns are not 6 + 5\n"), 1;
+    return 0;
+}
+
 static void print_record_space(uint32_t len, uint32_t blocks) {
     FrameGeom g{};
     g.blocks = blocks;
@@ -210,7 +239,7 @@ static int check_routes() {
 
 int main(int argc, char** argv) {
     for (int i = 1; i + 1 < argc; i += 2) print_record_space((uint32_t)strtoul(argv[i], nullptr, 10), (uint32_t)strtoul(argv[i + 1], nullptr, 10));
-    if (check_images() || check_plans() || check_filters() || check_routes()) return 1;
+    if (check_images() || check_plans() || check_segments() || check_filters() || check_routes()) return 1;
     printf("ok %u\n", cases);
     return 0;
 }

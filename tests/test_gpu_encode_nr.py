@@ -198,6 +198,42 @@ def test_rgb_entry_and_host_forms(ctx, orc):
             assert got == want and (state == model_state).all(), form
 
 
+@pytest.mark.parametrize("bgr", [0, 1])
+def test_rgb_entry_on_the_two_stage_route(ctx, pkg, orc, bgr):
+    """amvhip_encode_nr_stream_dev in AMVHIP_ENTROPY_SERIAL mode: amv_forward_kernel's RGB instantiation with the offsets.
+    176x24: eleven MCUs a row (segments of 6 + 5), the last MCU row half outside the picture."""
+    import torch
+    w, h, n, nr = 176, 24, 3, 3000
+    L = orc.lib()
+    pix = np.stack([orc.synth_frame(0xA11CE, 30 + t, w, h) for t in range(n)])
+    frames = []
+    for t in range(n):
+        y, cb, cr = np.zeros((h, w), np.uint8), np.zeros((h // 2, w // 2), np.uint8), np.zeros((h // 2, w // 2), np.uint8)
+        L.amvo_rgb24_to_yuvj420p(pix[t].ctypes.data, w * 3, w, h, bgr, y.ctypes.data, cb.ctypes.data, cr.ctypes.data)
+        frames.append((y, cb, cr))
+    model_state = M.new_state()
+    want = M.encode_stream(frames, w, h, nr, state=model_state)
+    cap = ctx.encode_bound(w, h) * n
+    got = {}
+    try:
+        for mode in (pkg.ENTROPY_AUTO, pkg.ENTROPY_SERIAL):
+            ctx.set_entropy_mode(mode)
+            d_blob = torch.full((cap + 64,), FILL, dtype=torch.uint8, device="cuda:0")
+            d_offs = torch.full((n,), -1, dtype=torch.int64, device="cuda:0")
+            d_lens = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
+            d_state = _state_dev(M.new_state())
+            ctx.encode_nr_stream_dev(_t(pix), w * 3, bgr, n, w, h, 0, nr, d_state, d_blob, cap, d_offs, d_lens)
+            torch.cuda.synchronize()
+            got[mode] = (d_blob.cpu().numpy(), d_offs.cpu().numpy(), d_lens.cpu().numpy(), d_state.cpu().numpy())
+    finally:
+        ctx.set_entropy_mode(pkg.ENTROPY_AUTO)
+    auto, serial = got[pkg.ENTROPY_AUTO], got[pkg.ENTROPY_SERIAL]
+    for a, s, what in zip(auto, serial, ("bytes", "offsets", "lengths", "state")):
+        assert (a == s).all(), "%s differ between the two routes at %s" % (what, np.flatnonzero(a != s)[:8])
+    _check(*serial[:3], want, "pixels, bgr %d, serial" % bgr)
+    assert (serial[3] == model_state).all()
+
+
 def test_short_blob_and_refused_arguments(ctx, pkg):
     import torch
     w, h, nr = 48, 32, 300

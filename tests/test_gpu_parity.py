@@ -429,6 +429,73 @@ def test_encode_rejects_bad_arguments(ctx, pkg):
     assert pkg.load_library().encode_amv_frame(one.ctypes.data, 3, 1, 1, 0, one.ctypes.data, 16) == -1
 
 
+def test_plain_encode_entries_refuse_bad_arguments(ctx, pkg):
+    """amvhip_encode_batch_dev, _yuv420_batch_dev, _yuv422_batch_dev, _yuv420_scaled_batch_dev and the host-buffer forms of
+    the first three at 16x16 x 2, one fault at a time: the code, the message, and the outputs still at their fill value;
+    n == 0 is no fault"""
+    import torch
+    lib, w, h, n, cap, fill = ctx.lib, 16, 16, 2, 4096, 0xA5
+    pix = np.full((n, h, w * 3), 90, np.uint8)
+    Y, C = np.full((n, h, w), 90, np.uint8), np.full((n, h, w // 2), 90, np.uint8)       # (chroma rows enough for 4:2:2)
+    good = dict(w=w, h=h, n=n, qbias=0, stride=w * 3, ys=w, cs=w // 2, blob=True, offs=True, lens=True)
+    faults = [("odd width", dict(w=15)), ("odd height", dict(h=15)), ("qbias 256", dict(qbias=256)), ("stride one short", dict(stride=w * 3 - 1, ys=w - 1)),
+              ("chroma stride one short", dict(cs=w // 2 - 1)), ("null blob", dict(blob=False)), ("null offs", dict(offs=False)),
+              ("null lens", dict(lens=False)), ("n == 0", dict(n=0))]
+
+    def rgb(fn, src, a, out):
+        return fn(ctx.h, src, a["stride"], 0, a["n"], a["w"], a["h"], a["qbias"], *out)
+
+    def yuv(fn, src, a, out):
+        return fn(ctx.h, *src, a["ys"], a["cs"], h * w, h * (w // 2), a["n"], a["w"], a["h"], a["qbias"], *out)
+
+    def scaled(fn, src, a, out):
+        return fn(ctx.h, *src, a["ys"], a["cs"], h * w, h * (w // 2), w, h, a["n"], a["w"], a["h"], a["qbias"], *out)
+
+    d_pix, d_planes = _t(pix), (_t(Y), _t(C), _t(C.copy()))
+    dev_src = (d_pix.data_ptr(), tuple(p.data_ptr() for p in d_planes))
+    host_src = (pix.ctypes.data, (Y.ctypes.data, C.ctypes.data, C.ctypes.data))
+    # entry, its caller, device form?, source, then what it says to: a size or stride fault; a null output; qbias 256
+    table = [("amvhip_encode_batch_dev", rgb, True, 0, "encode: bad argument", "encode: null output", None),
+             ("amvhip_encode_yuv420_batch_dev", yuv, True, 1, "encode_yuv: bad argument", None, None),
+             ("amvhip_encode_yuv422_batch_dev", yuv, True, 1, "encode_yuv: bad argument", None, None),
+             ("amvhip_encode_yuv420_scaled_batch_dev", scaled, True, 1, "encode_scaled: bad argument", None, None),
+             ("amvhip_encode_batch", rgb, False, 0, "encode: bad argument", "encode: null argument", None),
+             ("amvhip_encode_yuv420_batch", yuv, False, 1, "encode_yuv420: bad argument", None, "encode_yuv: bad argument"),
+             ("amvhip_encode_yuv422_batch", yuv, False, 1, "encode_yuv420: bad argument", None, "encode_yuv: bad argument")]
+    for name, call, on_dev, kind, says, says_null, says_qbias in table:
+        for what, change in faults:
+            if kind == 0 and what == "chroma stride one short":
+                continue
+            a = dict(good, **change)
+            if on_dev:
+                keep = (torch.full((cap,), fill, dtype=torch.uint8, device="cuda:0"), torch.full((n,), -1, dtype=torch.int64, device="cuda:0"),
+                        torch.full((n,), -1, dtype=torch.int32, device="cuda:0"))
+                ptrs = [t.data_ptr() for t in keep]
+            else:
+                keep = (np.full(cap, fill, np.uint8), np.full(n, 2 ** 64 - 1, np.uint64), np.full(n, 2 ** 32 - 1, np.uint32))
+                ptrs = [t.ctypes.data for t in keep]
+            out = [ptrs[0] if a["blob"] else None, cap, ptrs[1] if a["offs"] else None, ptrs[2] if a["lens"] else None]
+            rc = call(getattr(lib, name), (dev_src if on_dev else host_src)[kind], a, out + [None] if on_dev else out)
+            said = lib.amvhip_last_error(ctx.h).decode()
+            if what == "n == 0":
+                assert rc == pkg.OK, (name, what, rc, said)
+            else:
+                want = says
+                if what.startswith("null") and says_null:
+                    want = says_null
+                if what == "qbias 256" and says_qbias:
+                    want = says_qbias
+                if name == "amvhip_encode_yuv420_scaled_batch_dev" and "stride" in what:
+                    want = "resample: bad argument"
+                assert rc == pkg.ERR_ARG and said.startswith(want), (name, what, rc, said)
+            if on_dev:
+                torch.cuda.synchronize()
+                got = [t.cpu().numpy() for t in keep]
+                assert (got[0] == fill).all() and (got[1] == -1).all() and (got[2] == -1).all(), (name, what)
+            else:
+                assert (keep[0] == fill).all() and (keep[1] == 2 ** 64 - 1).all() and (keep[2] == 2 ** 32 - 1).all(), (name, what)
+
+
 def test_round_trip_through_aliases(ctx, pkg, orc):
     lib = pkg.load_library()
     w, h = 320, 240
