@@ -16,7 +16,9 @@
 //   D. colour conversion of a 4x2-pixel patch per lane step, two pixels per instruction in packed
 //      16-bit arithmetic; the 12 bytes of each patch row go
 //      straight to the frame (the lanes of a step cover consecutive 12-byte pieces of a row, so a
-//      wave store is one contiguous run; the picture is stored bottom-up, AmvJpeg.c:800).
+//      wave store is one contiguous run; the picture is stored bottom-up, AmvJpeg.c:800).  A segment that is whole
+//      (ten decoded MCUs, 16 rows inside the picture) takes five unrolled steps without a test per lane; the picture's
+//      edges and damaged frames take the general loop.
 //
 // Pixels of MCUs at or after a frame's first decode error are zero (AMVDec.c:283 + the reference
 // stopping at the error).  Compiled with -fwrapv, as the reference's arithmetic wraps.
@@ -34,8 +36,8 @@ struct __attribute__((aligned(4))) Px12 { uint32_t w[3]; };   // four BGR pixels
 constexpr int kRowsPerGroup = 4;   // (five where fours leave too many slots idle: launch_reconstruct)
 
 // 8-point inverse DCT of AmvJpeg.c: idctrow (:1082-1128) when kColumn == false, idctcol
-// (:1130-1175, without its final clamp) when true.  The reference's all-AC-zero shortcuts
-// (:1087-1092, :1134-1140) are not branched on.  They are special cases of this arithmetic only while the general
+// (:1130-1175, without its final clamp and with 7 of its final 14 bits of shift: clamp_pack has the rest) when true.
+// The reference's all-AC-zero shortcuts (:1087-1092, :1134-1140) are not branched on.  They are special cases of this arithmetic only while the general
 // formula does not leave 32 bits where the shortcut stays inside them: the row shortcut's 8 * dc is
 // (dc * 2048 + 128) >> 8 for -2^20 <= dc < 2^20, the column shortcut's (x + 32) >> 6 is (x * 256 + 8192) >> 14 for
 // -2^23 <= x <= 2^23 - 33.  Every coefficient block a scan can carry stays inside both (DC any int16, |AC| <= 1023:
@@ -67,7 +69,7 @@ __device__ __forceinline__ void idct8(int& v0, int& v1, int& v2, int& v3, int& v
     constexpr int kBias = kKind == kRow0 ? 128 + 8192 : 128;
     constexpr int kRound = kColumn ? 4 : 0;
     constexpr int kDown = kColumn ? 3 : 0;
-    constexpr int kOut = kColumn ? 14 : 8;
+    constexpr int kOut = kColumn ? 7 : 8;
     int a0 = kColumn ? v0 : v0 * 2048 + kBias, a1 = kColumn ? v4 : v4 * 2048;   // (<<11; the column's <<8 is done)
     const int i2 = v6, i3 = v2, i4 = v1, i5 = v7, i6 = v5, i7 = v3;
     int t;
@@ -117,9 +119,18 @@ constexpr QuantWords pack_quant() {
 }
 __device__ const QuantWords kQuantWords = pack_quant();
 
-// iclp[] of AmvJpeg.c:1073-1080 (table spans -512..511; beyond it the reference reads out of
-// bounds, defined here as saturation)
-__device__ __forceinline__ int clamp_iclp(int x) { return min(max(x, -256), 255); }
+// iclp[] of AmvJpeg.c:1073-1080 (table spans -512..511; beyond it the reference reads out of bounds, defined here as
+// saturation) of two column sums x >> 14, as two int16 in a dword.  The column pass hands over x >> 7, and for every
+// 32-bit x  clamp(x >> 14, -256, 255) == sat_i16(x >> 7) >> 7: the shifts are arithmetic, so both sides are monotone
+// in x and (x >> 7) >> 7 is x >> 14; -32768 >> 7 is -256 and 32767 >> 7 is 255.  v_cvt_pk_i16_i32 saturates both
+// halves as it packs, and one packed shift finishes the pair: two instructions where two clamps and a permute stood.
+// (Written as the instructions: the compiler must not pick a pack of its own here)
+__device__ __forceinline__ uint32_t clamp_pack(int lo, int hi) {
+    uint32_t p, d;
+    asm("v_cvt_pk_i16_i32 %0, %1, %2" : "=v"(p) : "v"(lo), "v"(hi));
+    asm("v_pk_ashrrev_i16 %0, %1, %2" : "=v"(d) : "s"(0x00070007u), "v"(p));   // (the count in both halves of a scalar)
+    return d;
+}
 
 // a.lo * w.lo + a.hi * w.hi + 32768 (16-bit signed halves): the three-operand form, so that the bias stays in its
 // register (the builtin becomes the accumulating form plus a move to reload the accumulator)
@@ -136,6 +147,37 @@ __device__ __forceinline__ uint32_t sat_pair(uint32_t yy, uint32_t cc) {
     asm("v_pk_add_i16 %0, %1, %2" : "=v"(sum) : "v"(yy), "v"(cc));
     asm("v_sat_pk_u8_i16 %0, %1" : "=v"(d) : "v"(sum));
     return d;
+}
+
+// Stage D's arithmetic for one 4x2 patch (both of its loops use it).  The chroma terms of the patch's two chroma samples
+// (uu, vv: two int16 each): (u, v) of sample e as one pair of int16; each term (:808-810, +128) is one two-element dot
+// product, and bytes 1-2 of it -- the term >> 8 -- go into both halves of a dword with one byte permute.
+struct ChromaTerms { uint32_t r[2], g[2], b[2]; };
+__device__ __forceinline__ ChromaTerms chroma_terms(uint32_t uu, uint32_t vv) {
+    ChromaTerms c;
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const uint32_t uv = __builtin_amdgcn_perm(vv, uu, e ? 0x07060302u : 0x05040100u);
+        const uint32_t r = dot2_bias(uv, pair16(18, 367));
+        const uint32_t gg = dot2_bias(uv, pair16(-159, -220));
+        const uint32_t b = dot2_bias(uv, pair16(411, -29));
+        c.r[e] = __builtin_amdgcn_perm(r, r, 0x02010201u);
+        c.g[e] = __builtin_amdgcn_perm(gg, gg, 0x02010201u);
+        c.b[e] = __builtin_amdgcn_perm(b, b, 0x02010201u);
+    }
+    return c;
+}
+// ... and the twelve bytes of one of its rows (yy: four int16 of luma)
+__device__ __forceinline__ Px12 patch_row(uint2 yy, const ChromaTerms& c) {
+    const uint32_t b01 = sat_pair(yy.x, c.b[0]), g01 = sat_pair(yy.x, c.g[0]), r01 = sat_pair(yy.x, c.r[0]);
+    const uint32_t b23 = sat_pair(yy.y, c.b[1]), g23 = sat_pair(yy.y, c.g[1]), r23 = sat_pair(yy.y, c.r[1]);
+    const uint32_t gr = g01 | (r01 << 16);                         // G0 G1 R0 R1
+    const uint32_t bg = b23 | (g23 << 16);                         // B2 B3 G2 G3
+    Px12 v;                                                        // :829-831 B,G,R
+    v.w[0] = __builtin_amdgcn_perm(gr, b01, 0x01060400u);          // B0 G0 R0 B1
+    v.w[1] = __builtin_amdgcn_perm(bg, gr, 0x06040301u);           // G1 R1 B2 G2
+    v.w[2] = __builtin_amdgcn_perm(bg, r23, 0x01070500u);          // R2 B3 G3 R3
+    return v;
 }
 
 }  // namespace
@@ -210,11 +252,7 @@ __global__ __launch_bounds__(kWave * kRows) void amv_reconstruct_kernel(
         for (int r = 0; r < 8; ++r) {
             uint32_t w[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int lo = clamp_iclp(v[8 * r + 2 * q]);
-                const int hi = clamp_iclp(v[8 * r + 2 * q + 1]);
-                w[q] = __builtin_amdgcn_perm((uint32_t)hi, (uint32_t)lo, 0x05040100u);   // low halves: lo | hi << 16
-            }
+            for (int q = 0; q < 4; ++q) w[q] = clamp_pack(v[8 * r + 2 * q], v[8 * r + 2 * q + 1]);
             *reinterpret_cast<uint4*>(dst + r * pitch) = make_uint4(w[0], w[1], w[2], w[3]);
         }
     }
@@ -231,14 +269,52 @@ __global__ __launch_bounds__(kWave * kRows) void amv_reconstruct_kernel(
     const uint32_t px = min(cnt * 16u, g.width - m0 * 16u);            // pixels of this segment inside it (:803)
     const uint32_t groups = cnt * 4u;
     const bool all_decoded = mcu0 + cnt <= ok;                         // wave-uniform: the usual case skips the per-patch test
-    const uint32_t pairs = (vr + 1u) >> 1;
-    // patch t = lane, lane + 64, ...: row pair i2 = t / groups, group gi = t % groups, kept up by addition
-    const uint32_t step_i2 = kWave / groups, step_gi = kWave - step_i2 * groups;
-    uint32_t i2 = lane / groups, gi = lane - i2 * groups;
     // one base per wave (scalar) + 32-bit byte offsets inside the frame: picture row my*16+i is destination row
     // H-1-(my*16+i) (:800)
     uint8_t* const frame = out + (uint64_t)f * g.frame_bytes;
     const uint32_t row0 = (g.height - 1u - my * 16u) * g.stride + m0 * 48u;
+    // Patch t = lane, lane + 64, ...: row pair i2 = t / groups, group gi = t % groups.  In bytes: a row pair is
+    // 4 * kPitchY of luma and 2 * kPitchC of each chroma plane in LDS and 2 * stride back in the frame, a group 8, 4 and 12 on.
+    constexpr uint32_t kPairY = 4u * kPitchY, kPairC = 2u * kPitchC, kPlaneU = 32u * kPitchY, kPlaneV = kPlaneU + 16u * kPitchC;
+    if (all_decoded && cnt == kSegMcus && px == kSegMcus * 16u && vr == 16u) {
+        // A whole segment (wave-uniform; every wave of a 160x120 frame but its bottom row's): 40 groups in 8 row pairs,
+        // five trips, nothing to test per lane and every row a 12-byte store.  64 k patches on, trip k is q row pairs
+        // and r groups further; the lanes whose group then lies past the row's end (b + r >= 40) are one more row pair
+        // on and 40 groups back: a select between two fixed values of the lane, never a lane mask.  The 40 groups of a
+        // chroma row are its 160 bytes: patch t's chroma is at 4 t.  What depends on k alone is a constant of the LDS
+        // read or goes into the trip's scalar base (the lane's part of the frame offset stays positive: the MCU row has
+        // 15 picture rows below its first in the buffer, and the lane's part goes back at most four).
+        constexpr uint32_t kGroups = kSegMcus * 4u, kTrips = kGroups * 8u / kWave;
+        static_assert(kGroups * 8u % kWave == 0u && kGroups < kWave && kPairC == kGroups * 4u, "whole trips; chroma is linear in t");
+        const uint32_t a = lane >= kGroups ? 1u : 0u, b = lane - a * kGroups;
+        const uint8_t* const ly = s_img + a * kPairY + b * 8u;
+        const uint8_t* const ly_past = ly + (kPairY - kGroups * 8u);
+        const uint8_t* const lc = s_img + kPlaneU + lane * 4u;
+        const uint32_t off0 = row0 - a * 2u * g.stride + b * 12u;
+        const uint32_t off0_past = off0 - 2u * g.stride - kGroups * 12u;
+#pragma unroll
+        for (uint32_t k = 0; k < kTrips; ++k) {
+            const uint32_t q = k * kWave / kGroups, r = k * kWave % kGroups;
+            const bool past = r != 0u && b >= kGroups - r;
+            const uint8_t* const y = (past ? ly_past : ly) + (q * kPairY + r * 8u);
+            const uint2 ya = *reinterpret_cast<const uint2*>(y);
+            const uint2 yb = *reinterpret_cast<const uint2*>(y + 2u * kPitchY);
+            const uint32_t uu = *reinterpret_cast<const uint32_t*>(lc + k * kWave * 4u);
+            const uint32_t vv = *reinterpret_cast<const uint32_t*>(lc + k * kWave * 4u + (kPlaneV - kPlaneU));
+            const ChromaTerms c = chroma_terms(uu, vv);
+            uint8_t* const upper = frame + (int64_t)(int32_t)(r * 12u - q * 2u * g.stride);   // (scalar)
+            const uint32_t off = past ? off0_past : off0;
+            *reinterpret_cast<Px12*>(upper + off) = patch_row(ya, c);
+            *reinterpret_cast<Px12*>(upper - g.stride + off) = patch_row(yb, c);
+        }
+        continue;   // (to next_item)
+    }
+    // Everything else -- the picture's bottom and right edges, short segments, damaged frames: i2 and gi kept up by
+    // addition, the offsets formed from them on every trip (carried along and corrected where a group runs past the
+    // row's end they cost more instructions than the multiplies they replace: DESIGN.md, Appendix A.3)
+    const uint32_t pairs = (vr + 1u) >> 1;
+    const uint32_t step_i2 = kWave / groups, step_gi = kWave - step_i2 * groups;
+    uint32_t i2 = lane / groups, gi = lane - i2 * groups;
     for (; i2 < pairs; i2 += step_i2, gi += step_gi) {
         if (gi >= groups) { gi -= groups; ++i2; if (i2 >= pairs) break; }
         const uint32_t lc = gi * 4u;
@@ -251,32 +327,12 @@ __global__ __launch_bounds__(kWave * kRows) void amv_reconstruct_kernel(
             ya.x = ya.y = yb.x = yb.y = kDark;
             uu = vv = 0u;
         }
-        uint32_t cr[2], cg[2], cb[2];                                  // the chroma term of both pixels of a pair
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            // (u, v) of chroma sample e as one pair of int16; each term (:808-810, +128) is one two-element dot product,
-            // and bytes 1-2 of it -- the term >> 8 -- go into both halves of a dword with one byte permute
-            const uint32_t uv = __builtin_amdgcn_perm(vv, uu, e ? 0x07060302u : 0x05040100u);
-            const uint32_t r = dot2_bias(uv, pair16(18, 367));
-            const uint32_t gg = dot2_bias(uv, pair16(-159, -220));
-            const uint32_t b = dot2_bias(uv, pair16(411, -29));
-            cr[e] = __builtin_amdgcn_perm(r, r, 0x02010201u);
-            cg[e] = __builtin_amdgcn_perm(gg, gg, 0x02010201u);
-            cb[e] = __builtin_amdgcn_perm(b, b, 0x02010201u);
-        }
+        const ChromaTerms c = chroma_terms(uu, vv);                    // the chroma term of both pixels of a pair
         if (lc >= px) continue;                                        // right of the picture
         uint32_t off = row0 - 2u * i2 * g.stride + lc * 3u;
 #pragma unroll
         for (int row = 0; row < 2; ++row) {
-            const uint2 yy = row ? yb : ya;
-            const uint32_t b01 = sat_pair(yy.x, cb[0]), g01 = sat_pair(yy.x, cg[0]), r01 = sat_pair(yy.x, cr[0]);
-            const uint32_t b23 = sat_pair(yy.y, cb[1]), g23 = sat_pair(yy.y, cg[1]), r23 = sat_pair(yy.y, cr[1]);
-            const uint32_t gr = g01 | (r01 << 16);                         // G0 G1 R0 R1
-            const uint32_t bg = b23 | (g23 << 16);                         // B2 B3 G2 G3
-            Px12 v;                                                        // :829-831 B,G,R
-            v.w[0] = __builtin_amdgcn_perm(gr, b01, 0x01060400u);          // B0 G0 R0 B1
-            v.w[1] = __builtin_amdgcn_perm(bg, gr, 0x06040301u);           // G1 R1 B2 G2
-            v.w[2] = __builtin_amdgcn_perm(bg, r23, 0x01070500u);          // R2 B3 G3 R3
+            const Px12 v = patch_row(row ? yb : ya, c);
             if (2u * i2 + (uint32_t)row >= vr) break;                      // odd picture height
             if (lc + 4u <= px) {                                           // rows are 4-byte aligned (AmvJpeg.c:1524), lc*3 is 0 mod 4
                 *reinterpret_cast<Px12*>(frame + off) = v;
