@@ -126,6 +126,10 @@ SYMBOLS = {
     "amvhip_encode_trellis_batch": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp]),
     "amvhip_encode_yuv420_trellis_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "amvhip_encode_yuv420_trellis_batch": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp]),
+    "amvhip_encode_yuv420_nr_trellis_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_encode_yuv420_nr_trellis_stream": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp]),
+    "amvhip_encode_nr_trellis_stream_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_encode_nr_trellis_stream": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp]),
     "amvhip_resample_yuv420_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
     "amvhip_encode_yuv420_scaled_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "amvhip_img_convert_supported": (_int, [_int, _int, _u32, _u32]),
@@ -140,6 +144,7 @@ SYMBOLS = {
     "amvhip_deinterlace": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32]),
     "amvhip_video_frontend_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _vp]),
     "amvhip_encode_frontend_batch_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_encode_frontend_quant_stream_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp]),
     "amvhip_decode_fmt_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
     "amvhip_lowres_dim": (_u32, [_u32, _u32]),
     "amvhip_lowres_frame_bytes": (_u64, [_u32, _u32, _u32]),
@@ -225,6 +230,15 @@ class Frontend(ctypes.Structure):
     def __init__(self, deinterlace=0, crop=(0, 0, 0, 0), pad=(0, 0, 0, 0), pad_color=(16, 128, 128)):
         """crop and pad as (top, bottom, left, right)"""
         super().__init__(int(deinterlace), *crop, *pad, (ctypes.c_uint8 * 3)(*pad_color))
+
+
+class Quant(ctypes.Structure):
+    """amvhip_quant of include/amvhip.h: what amvhip_encode_frontend_quant_stream_dev asks of the quantiser"""
+    _fields_ = [("qbias", _u32), ("nr", _u32), ("trellis", _u32), ("lambda_", _u32), ("d_state", _vp)]
+
+    def __init__(self, qbias=0, nr=0, trellis=0, lam=0, state=None):
+        """state: int32[65] on the device (a tensor or an address), required when nr > 0; the caller keeps it alive"""
+        super().__init__(int(qbias), int(nr), int(trellis), int(lam), _ptr(state))
 
 
 def pad_color_from_rgb(rrggbb):
@@ -354,6 +368,31 @@ class Context:
                                                             _ptr(state), _ptr(blob), blob_cap, _ptr(offs), _ptr(lens)),
                            "encode_nr_stream")
 
+    def encode_yuv420_nr_trellis_stream_dev(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, qbias, nr, lam, state, blob,
+                                            blob_cap, offs, lens, stream=None):
+        """-nr and the trellis quantiser in one call: the search runs on the denoised outputs; state as in the -nr entries"""
+        return self._check(self.lib.amvhip_encode_yuv420_nr_trellis_stream_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride,
+                                                                               y_frame, c_frame, n, w, h, qbias, nr, lam, _ptr(state),
+                                                                               _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), stream),
+                           "encode_yuv420_nr_trellis_stream_dev")
+
+    def encode_yuv420_nr_trellis_stream(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, qbias, nr, lam, state, blob,
+                                        blob_cap, offs, lens):
+        return self._check(self.lib.amvhip_encode_yuv420_nr_trellis_stream(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride,
+                                                                           y_frame, c_frame, n, w, h, qbias, nr, lam, _ptr(state),
+                                                                           _ptr(blob), blob_cap, _ptr(offs), _ptr(lens)),
+                           "encode_yuv420_nr_trellis_stream")
+
+    def encode_nr_trellis_stream_dev(self, pix, pix_stride, is_bgr, n, w, h, qbias, nr, lam, state, blob, blob_cap, offs, lens, stream=None):
+        return self._check(self.lib.amvhip_encode_nr_trellis_stream_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, qbias, nr, lam,
+                                                                        _ptr(state), _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), stream),
+                           "encode_nr_trellis_stream_dev")
+
+    def encode_nr_trellis_stream(self, pix, pix_stride, is_bgr, n, w, h, qbias, nr, lam, state, blob, blob_cap, offs, lens):
+        return self._check(self.lib.amvhip_encode_nr_trellis_stream(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, qbias, nr, lam,
+                                                                    _ptr(state), _ptr(blob), blob_cap, _ptr(offs), _ptr(lens)),
+                           "encode_nr_trellis_stream")
+
     def encode_trellis_lambda_max(self):
         """the largest `lambda` the trellis entries take"""
         return self.lib.amvhip_encode_trellis_lambda_max()
@@ -476,6 +515,13 @@ class Context:
         return self._check(self.lib.amvhip_encode_frontend_batch_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n, self._fe(fe), w, h,
                                                                      qbias, _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), stream),
                            "encode_frontend_batch_dev")
+
+    def encode_frontend_quant_stream_dev(self, src_fmt, src, src_w, src_h, n, fe, w, h, quant, blob, blob_cap, offs, lens, stream=None):
+        """encode_frontend_batch_dev with a Quant (qbias, nr, trellis, lambda, state) in the place of qbias; None -> NULL"""
+        q = None if quant is None else ctypes.addressof(quant)
+        return self._check(self.lib.amvhip_encode_frontend_quant_stream_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n, self._fe(fe),
+                                                                            w, h, q, _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), stream),
+                           "encode_frontend_quant_stream_dev")
 
     def decode_fmt_batch_dev(self, blob, blob_bytes, offs, lens, n, w, h, flags, dst_fmt, out, out_stride, status, stream=None):
         return self._check(self.lib.amvhip_decode_fmt_batch_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, flags,

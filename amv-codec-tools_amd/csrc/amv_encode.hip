@@ -31,12 +31,13 @@ using namespace enc;
 // Nr: nothing (the plain kernel, its signature and code as they always were), or one `const uint16_t*` -- the noise-reduction
 // offsets of the call's frames (64 uint16 per frame, amv_nr_plan.h): a frame's 128 bytes go to LDS and transform_block
 // denoises with them between the column pass and the quantiser; or one TrellisArg -- the AC outputs leave transform_block
-// un-quantised, go to the lane's line in the planes' space, and trellis_lane makes the levels there.
+// un-quantised, go to the lane's line in the planes' space, and trellis_lane makes the levels there; or one NrTrellisArg --
+// both: the outputs are denoised with the offsets and trellis_lane searches on what is left.
 template <bool kYuv, class... Nr>
 __global__ __launch_bounds__(kWave) void amv_forward_kernel(Source in, uint32_t n, FrameSel sel, FrameGeom g, uint32_t nseg, uint32_t per_seg,
                                                             uint32_t qbias, int16_t* __restrict__ coef, Nr... nr) {
     constexpr bool kNr = OptKind<Nr...>::kNr, kTrellis = OptKind<Nr...>::kTrellis;
-    static_assert(sizeof...(Nr) == 0 || kNr || kTrellis, "the offsets, lambda, or nothing");
+    static_assert(sizeof...(Nr) == 0 || kNr || kTrellis, "the offsets, lambda, both, or nothing");
     __shared__ __attribute__((aligned(16))) int16_t s_planes[kPlaneSamples];
     __shared__ __attribute__((aligned(16))) uint32_t s_qmul[kQuantMulWords];
     uint32_t* s_nr_off = nullptr;
@@ -72,7 +73,8 @@ __global__ __launch_bounds__(kWave) void amv_forward_kernel(Source in, uint32_t 
         uint4* const dst = reinterpret_cast<uint4*>(coef + ((uint64_t)slot * g.mcus + (uint64_t)my * g.mcu_cols + m0) * 384u + lane * 64u);
         if constexpr (kTrellis) {
             uint32_t out[32], nz_lo, nz_hi;
-            if (lane < nb) transform_block<false, true>(s_y, s_cb, s_cr, s_qmul, lane, qbias, out, nz_lo, nz_hi);
+            if (lane < nb)
+                transform_block<kNr, true>(s_y, s_cb, s_cr, s_qmul, lane, qbias, out, nz_lo, nz_hi, reinterpret_cast<const uint16_t*>(s_nr_off));
             __syncthreads();               // every lane has its samples: the planes become the lines
             if (lane < nb) {
                 uint8_t* const region = reinterpret_cast<uint8_t*>(s_planes);

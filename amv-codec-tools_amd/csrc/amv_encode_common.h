@@ -377,6 +377,8 @@ __device__ __forceinline__ bool block_row_passes(const int16_t* s_y, const int16
 // 16-byte read).  The sums that denoise_dct_c also takes are amv_nr_sums_kernel's (amv_encode_nr.hip).
 // kTrellis: the AC outputs leave un-quantised (they fit 16 bits, see above), in the same pairs -- trellis_lane, below, turns
 // the line they make into levels; the DC is quantised here as ever, and the mask that comes back is not the levels'.
+// Both: the outputs are denoised first and leave as they then are -- the search runs on what denoise_dct left, as
+// dct_quantize_trellis_c's does (mpegvideo_enc.c:2987-2990); denoising only shrinks a magnitude, so the 16-bit fit holds.
 template <bool kNr = false, bool kTrellis = false>
 __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_t* s_cb, const int16_t* s_cr, const uint32_t* s_qmul,
                                                 uint32_t lane, uint32_t qbias, uint32_t (&out)[32], uint32_t& nz_lo, uint32_t& nz_hi,
@@ -437,16 +439,19 @@ __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_
 }
 
 // the one optional trailing argument of the encoder kernels (`class... Opt`), by Quantiser's alternative: nothing, the
-// frames' noise-reduction offsets (const uint16_t*), or the trellis quantiser's lambda (TrellisArg)
+// frames' noise-reduction offsets (const uint16_t*), the trellis quantiser's lambda (TrellisArg), or both (NrTrellisArg)
 template <class... Opt> struct OptKind { static constexpr bool kNr = false, kTrellis = false; };
 template <> struct OptKind<const uint16_t*> { static constexpr bool kNr = true, kTrellis = false; };
 template <> struct OptKind<TrellisArg> { static constexpr bool kNr = false, kTrellis = true; };
+template <> struct OptKind<NrTrellisArg> { static constexpr bool kNr = true, kTrellis = true; };
 __device__ __forceinline__ const uint16_t* nr_offsets_of() { return nullptr; }
 __device__ __forceinline__ const uint16_t* nr_offsets_of(const uint16_t* offs) { return offs; }
 __device__ __forceinline__ const uint16_t* nr_offsets_of(TrellisArg) { return nullptr; }
+__device__ __forceinline__ const uint16_t* nr_offsets_of(NrTrellisArg t) { return t.offsets; }
 __device__ __forceinline__ uint32_t trellis_lambda_of() { return 0u; }
 __device__ __forceinline__ uint32_t trellis_lambda_of(const uint16_t*) { return 0u; }
 __device__ __forceinline__ uint32_t trellis_lambda_of(TrellisArg t) { return t.lambda; }
+__device__ __forceinline__ uint32_t trellis_lambda_of(NrTrellisArg t) { return t.lambda; }
 
 // From what a launcher was handed to the kernels' template arguments: launch(std::bool_constant<kYuv>, opt...) is called
 // once, opt... being the instantiation's trailing argument -- `kernel<decltype(yuv)::value, decltype(opt)...>` with

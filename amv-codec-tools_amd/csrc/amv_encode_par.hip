@@ -212,14 +212,15 @@ __device__ __forceinline__ Cursor seek_symbol(uint32_t j, uint32_t nb, const uin
 // denoises with them between the column pass and the quantiser; or one TrellisArg -- transform_block leaves the AC outputs
 // un-quantised and trellis_lane makes the levels in the lane's line, once that is written (stage 1's end); the mask of the
 // non-zero ones is its result.  The walk's state is private (scratch), so the LDS grows by the tables alone (1 152 bytes)
-// and three workgroups still fit a CU.
+// and three workgroups still fit a CU.  Or one NrTrellisArg -- both: the offsets in LDS, the outputs denoised, and
+// trellis_lane searching on what is left (128 bytes of LDS more than the trellis instantiation).
 template <bool kYuv, class... Nr>
 __global__ __launch_bounds__(kLanes, 3) void amv_encode_frame_kernel(
     Source in, uint32_t n, FrameGeom g, uint32_t nseg, uint32_t per_seg, uint32_t qbias, const HuffEncodeImage* __restrict__ img,
     uint8_t* __restrict__ tmp, uint32_t bound, uint32_t* __restrict__ lens, uint32_t* __restrict__ retry_list,
     uint32_t* __restrict__ retry_count, Nr... nr) {
     constexpr bool kNr = OptKind<Nr...>::kNr, kTrellis = OptKind<Nr...>::kTrellis;
-    static_assert(sizeof...(Nr) == 0 || kNr || kTrellis, "the offsets, lambda, or nothing");
+    static_assert(sizeof...(Nr) == 0 || kNr || kTrellis, "the offsets, lambda, both, or nothing");
     __shared__ __attribute__((aligned(16))) uint8_t s_region[kWaves][kRegionBytes];
     __shared__ uint32_t s_own[kOwnWords * kLanes];
     __shared__ uint32_t s_bits[kWindowWords];

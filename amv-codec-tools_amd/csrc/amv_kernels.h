@@ -153,13 +153,15 @@ struct Source {
 using enc::Source;
 inline Source rgb_source(const uint8_t* pix, uint32_t pix_stride, int is_bgr) { return Source{pix, pix_stride, is_bgr, YuvSource{}, 0u}; }
 inline Source yuv_source(const YuvSource& yuv) { return Source{nullptr, 0u, 0, yuv, 1u}; }
-// How the AC coefficients of a call become levels, one of three: rounded (dct_quantize_c); rounded after denoising with the
-// noise-reduction offsets of the call's frames (uint16 [n][64], amv_nr_plan.h: launch_nr_chain writes them); or searched per
-// block by the trellis quantiser with this lambda (amv_trellis_plan.h).  Each is an instantiation of the encoder kernels
-// (their one optional trailing argument: none, the offsets, the TrellisArg).
+// How the AC coefficients of a call become levels, one of four: rounded (dct_quantize_c); rounded after denoising with the
+// noise-reduction offsets of the call's frames (uint16 [n][64], amv_nr_plan.h: launch_nr_chain writes them); searched per
+// block by the trellis quantiser with this lambda (amv_trellis_plan.h); or denoised with the offsets and then searched, as
+// dct_quantize_trellis_c does it (mpegvideo_enc.c:2987-2990).  Each is an instantiation of the encoder kernels (their one
+// optional trailing argument: none, the offsets, the TrellisArg, the NrTrellisArg).
 struct PlainQuant {};
 struct TrellisArg { uint32_t lambda; };
-using Quantiser = std::variant<PlainQuant, const uint16_t*, TrellisArg>;
+struct NrTrellisArg { const uint16_t* offsets; uint32_t lambda; };
+using Quantiser = std::variant<PlainQuant, const uint16_t*, TrellisArg, NrTrellisArg>;
 // The whole encoder, one workgroup per frame (amv_encode_par.hip): pixels -> FF D8 + escaped scan + FF D9 in
 // tmp[i*bound..], lens[i].  Frames whose bits do not fit the kernel's LDS window are appended to retry_list /
 // *retry_count for launch_forward + launch_pack (rounds).

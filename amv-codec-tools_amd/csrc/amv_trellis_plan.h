@@ -96,6 +96,9 @@ AMV_HD inline int32_t trellis_distortion(int32_t c, uint32_t a, uint32_t q) {
 // walk forms is a score plus one such step, the end rule's a score plus len[0x00] * lambda <= 59 lambda: with 63 positions
 // nothing the walk forms is above 63 * (kTrellisStepMost + 59 lambda).  lambda is taken while that is below
 // kTrellisNoScore (< 2^31): no sum wraps, and none reaches the value `best` starts from.
+// Behind -nr (the NrTrellisArg instantiations) the walk is handed denoised outputs: nr_denoise (amv_nr_plan.h) keeps the sign
+// and only shrinks the magnitude, |c'| <= |c| <= 8193.  Every step above uses |c| <= 8193 and nothing else of c, so the
+// 16-bit fit of the line and this bound stand as they are (tests/c/nr_trellis_plan_test.cc walks denoised blocks in 64 bits).
 constexpr uint32_t kTrellisQMost = 61;
 constexpr uint32_t kTrellisStepMost = (8u * kTrellisQMost + 2u) * (8u * kTrellisQMost + 2u);
 constexpr uint32_t kTrellisBitsMost = 59;

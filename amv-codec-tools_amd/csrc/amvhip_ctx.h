@@ -185,9 +185,26 @@ int pix_convert_launch(amvhip_ctx* c, int src_fmt, const PixPicture& src, int ds
 // ---- amvhip_encode.hip (the caller holds c->mu) ------------------------------------------------------------------------
 // what every encoder asks of the target size and of qbias
 inline bool encode_size_ok(uint32_t w, uint32_t h, uint32_t qbias) { return size_ok(w, h) && !(w & 1) && !(h & 1) && qbias <= 255; }
-// the tail of the scaled encoders: the w x h pictures they made as tight_420 in c->scaled, through encode_core
-int encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap,
-                       uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream);
+// What an entry asks of the AC quantiser, one of four: nothing; the reference's -nr for a stream (amv_encode_nr.hip,
+// amv_nr_plan.h) from the state the caller carries -- with nr == 0 the plain route, the state left alone; the trellis
+// search (amv_trellis_plan.h; trellis_lane in amv_encode_common.h); or both, the search on what -nr left -- with nr == 0
+// the trellis route, the state left alone.
+struct NrRequest {
+    uint32_t nr;
+    int32_t* state;
+};
+struct NrTrellisRequest {
+    uint32_t nr;
+    int32_t* state;
+    uint32_t lambda;
+};
+using QuantRequest = std::variant<PlainQuant, NrRequest, TrellisArg, NrTrellisRequest>;
+// what a request asks beyond the plain entries' checks; 0 = go on
+int quant_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const QuantRequest& req);
+// the tail of the scaled encoders: the w x h pictures they made as tight_420 in c->scaled, through the request's core
+// (req's state is on the device)
+int encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, uint8_t* d_blob,
+                       uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream);
 int resample_launch(amvhip_ctx* c, const PixPicture& src, uint32_t src_w, uint32_t src_h, const PixPicture& dst, uint32_t dst_w, uint32_t dst_h,
                     uint32_t n, bool to_jpeg, hipStream_t st);
 

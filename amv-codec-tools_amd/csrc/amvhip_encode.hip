@@ -3,14 +3,21 @@
 
 using namespace amv;
 
-// What an entry asks of the AC quantiser, one of three: nothing; the reference's -nr for a stream (amv_encode_nr.hip,
-// amv_nr_plan.h) from the state the caller carries -- with nr == 0 the plain route, the state left alone; or the trellis
-// search (amv_trellis_plan.h; trellis_lane in amv_encode_common.h).
-struct NrRequest {
+// The parts of a request (QuantRequest, amvhip_ctx.h): its -nr half -- nr and where the state's pointer is -- and its lambda
+struct NrPart {
     uint32_t nr;
-    int32_t* state;
+    int32_t** state;
 };
-using QuantRequest = std::variant<PlainQuant, NrRequest, TrellisArg>;
+static bool nr_part_of(QuantRequest& req, NrPart* p) {
+    if (NrRequest* q = std::get_if<NrRequest>(&req)) { *p = NrPart{q->nr, &q->state}; return true; }
+    if (NrTrellisRequest* q = std::get_if<NrTrellisRequest>(&req)) { *p = NrPart{q->nr, &q->state}; return true; }
+    return false;
+}
+static bool lambda_of(const QuantRequest& req, uint32_t* lambda) {
+    if (const TrellisArg* t = std::get_if<TrellisArg>(&req)) { *lambda = t->lambda; return true; }
+    if (const NrTrellisRequest* q = std::get_if<NrTrellisRequest>(&req)) { *lambda = q->lambda; return true; }
+    return false;
+}
 
 extern "C" uint32_t amvhip_encode_nr_max(uint32_t w, uint32_t h) {
     if (!encode_size_ok(w, h, 0u)) return 0u;
@@ -25,13 +32,16 @@ static int trellis_args_ok(amvhip_ctx* c, uint32_t lambda) {
         return fail(c, AMVHIP_ERR_ARG, "encode_trellis: lambda %u is more than amvhip_encode_trellis_lambda_max() = %u", lambda, trellis_lambda_max());
     return AMVHIP_OK;
 }
-static int quant_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const QuantRequest& req) {
-    if (const TrellisArg* t = std::get_if<TrellisArg>(&req)) return trellis_args_ok(c, t->lambda);
-    const NrRequest* q = std::get_if<NrRequest>(&req);
-    if (!q) return AMVHIP_OK;
-    if (q->nr > amvhip_encode_nr_max(w, h))
-        return fail(c, AMVHIP_ERR_ARG, "encode_nr: nr %u is more than amvhip_encode_nr_max(%u, %u) = %u", q->nr, w, h, amvhip_encode_nr_max(w, h));
-    if (n && q->nr && (!q->state || ((uintptr_t)q->state & 3u))) return fail(c, AMVHIP_ERR_ARG, "encode_nr: the state is null or not 4-byte aligned");
+int amv::quant_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const QuantRequest& req) {
+    uint32_t lambda;
+    if (lambda_of(req, &lambda))
+        if (int r = trellis_args_ok(c, lambda)) return r;
+    QuantRequest copy = req;
+    NrPart q;
+    if (!nr_part_of(copy, &q)) return AMVHIP_OK;
+    if (q.nr > amvhip_encode_nr_max(w, h))
+        return fail(c, AMVHIP_ERR_ARG, "encode_nr: nr %u is more than amvhip_encode_nr_max(%u, %u) = %u", q.nr, w, h, amvhip_encode_nr_max(w, h));
+    if (n && q.nr && (!*q.state || ((uintptr_t)*q.state & 3u))) return fail(c, AMVHIP_ERR_ARG, "encode_nr: the state is null or not 4-byte aligned");
     return AMVHIP_OK;
 }
 
@@ -105,9 +115,10 @@ static int encode_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameG
 }
 
 // Passes A and B in front of encode_core (the context is locked; nr > 0): the frames' sums, the chain from d_state to
-// d_state, and the encoder with the offsets the chain wrote.
+// d_state, and the encoder with the offsets the chain wrote -- rounding behind them, or, with a lambda, searching.  The sums
+// are taken before the offsets are applied, so the state does not depend on which.
 static int encode_nr_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, uint32_t nr, int32_t* d_state,
-                          uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
+                          const uint32_t* lambda, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
     const NrPlan plan = nr_plan(n);
     if (int r = ensure(c, c->nr_ws, plan.bytes)) return r;
     uint32_t* sums = (uint32_t*)((uint8_t*)c->nr_ws.p + plan.sums);
@@ -115,7 +126,19 @@ static int encode_nr_core(amvhip_ctx* c, const Source& in, uint32_t n, const Fra
     launch_nr_sums(in, n, g, sums, stream);
     launch_nr_chain(sums, n, g.blocks, nr, d_state, offsets, stream);
     if (int r = check_launch(c, "nr sums + chain")) return r;
-    return encode_core(c, in, n, g, qbias, offsets, d_blob, blob_cap, d_offs, d_lens, stream);
+    return encode_core(c, in, n, g, qbias, lambda ? Quantiser{NrTrellisArg{offsets, *lambda}} : Quantiser{offsets}, d_blob, blob_cap, d_offs, d_lens,
+                       stream);
+}
+
+// the request's core (the context is locked, the request checked, n > 0; req's state is on the device)
+static int encode_request(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, QuantRequest req, uint8_t* d_blob,
+                          uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
+    uint32_t lambda;
+    const bool trellis = lambda_of(req, &lambda);
+    NrPart q;
+    if (nr_part_of(req, &q) && q.nr)
+        return encode_nr_core(c, in, n, g, qbias, q.nr, *q.state, trellis ? &lambda : nullptr, d_blob, blob_cap, d_offs, d_lens, stream);
+    return encode_core(c, in, n, g, qbias, trellis ? Quantiser{TrellisArg{lambda}} : Quantiser{PlainQuant{}}, d_blob, blob_cap, d_offs, d_lens, stream);
 }
 
 // Every device-pointer encoder whole: the checks of the live half of `in`, of the outputs and of the request, n == 0, the
@@ -136,11 +159,7 @@ static int encode_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, u
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
-    const FrameGeom g = make_geom(w, h);
-    const NrRequest* q = std::get_if<NrRequest>(&req);
-    if (q && q->nr) return encode_nr_core(c, in, n, g, qbias, q->nr, q->state, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
-    const TrellisArg* t = std::get_if<TrellisArg>(&req);
-    return encode_core(c, in, n, g, qbias, t ? Quantiser{*t} : Quantiser{PlainQuant{}}, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+    return encode_request(c, in, n, make_geom(w, h), qbias, req, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
 }
 
 extern "C" int amvhip_encode_batch_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
@@ -192,6 +211,22 @@ extern "C" int amvhip_encode_yuv420_trellis_batch_dev(amvhip_ctx* c, const uint8
                       d_blob, blob_cap, d_offs, d_lens, stream);
 }
 
+extern "C" int amvhip_encode_nr_trellis_stream_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
+                                                   uint32_t h, uint32_t qbias, uint32_t nr, uint32_t lambda, int32_t* d_state, uint8_t* d_blob,
+                                                   uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+    return encode_dev(c, rgb_source(d_pix, pix_stride, is_bgr), n, w, h, qbias, NrTrellisRequest{nr, d_state, lambda}, d_blob, blob_cap, d_offs,
+                      d_lens, stream);
+}
+
+extern "C" int amvhip_encode_yuv420_nr_trellis_stream_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr,
+                                                          uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                                          uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, uint32_t nr, uint32_t lambda,
+                                                          int32_t* d_state, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
+                                                          void* stream) {
+    return encode_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, qbias,
+                      NrTrellisRequest{nr, d_state, lambda}, d_blob, blob_cap, d_offs, d_lens, stream);
+}
+
 // the device-to-host half of the host-buffer encoders: offs/lens, then the chunks
 static int encode_fetch(amvhip_ctx* c, hipStream_t hs, uint32_t n, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
     int32_t overflow = 0;
@@ -224,11 +259,11 @@ static int encode_host(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32
     if (int r = ensure(c, c->h_lens, (size_t)n * 4)) return r;
     Source in;
     if (int r = stage_in(hs, in)) return r;
-    NrRequest* q = std::get_if<NrRequest>(&req);
-    int32_t* const state = q && q->nr ? q->state : nullptr;
+    NrPart q;
+    int32_t* const state = nr_part_of(req, &q) && q.nr ? *q.state : nullptr;
     if (state) {                               // req is this call's copy: from here on its state is the device's, as encode_dev wants it
         if (int r = stage(c, c->nr_state, kNrStateWords * 4u, state, kNrStateWords * 4u, hs)) return r;
-        q->state = (int32_t*)c->nr_state.p;
+        *q.state = (int32_t*)c->nr_state.p;
     }
     if (int r = encode_dev(c, in, n, w, h, qbias, req, (uint8_t*)c->h_out.p, blob_cap, (uint64_t*)c->h_offs.p, (uint32_t*)c->h_lens.p, hs)) return r;
     if (state) {                               // (the state has moved on even where the chunks do not fit the blob)
@@ -264,6 +299,12 @@ extern "C" int amvhip_encode_nr_stream(amvhip_ctx* c, const uint8_t* pix, uint32
 extern "C" int amvhip_encode_trellis_batch(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
                                            uint32_t qbias, uint32_t lambda, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
     return encode_rgb_host(c, pix, pix_stride, is_bgr, n, w, h, qbias, TrellisArg{lambda}, blob, blob_cap, offs, lens);
+}
+
+extern "C" int amvhip_encode_nr_trellis_stream(amvhip_ctx* c, const uint8_t* pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
+                                               uint32_t h, uint32_t qbias, uint32_t nr, uint32_t lambda, int32_t* state, uint8_t* blob,
+                                               uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
+    return encode_rgb_host(c, pix, pix_stride, is_bgr, n, w, h, qbias, NrTrellisRequest{nr, state, lambda}, blob, blob_cap, offs, lens);
 }
 
 static int encode_yuv_host(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride, uint32_t c_stride,
@@ -302,6 +343,14 @@ extern "C" int amvhip_encode_yuv420_trellis_batch(amvhip_ctx* c, const uint8_t* 
                                                   uint32_t* lens) {
     return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias, TrellisArg{lambda}, blob, blob_cap,
                            offs, lens);
+}
+
+extern "C" int amvhip_encode_yuv420_nr_trellis_stream(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride,
+                                                      uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
+                                                      uint32_t h, uint32_t qbias, uint32_t nr, uint32_t lambda, int32_t* state, uint8_t* blob,
+                                                      uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
+    return encode_yuv_host(c, y, cb, cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u, n, w, h, qbias,
+                           NrTrellisRequest{nr, state, lambda}, blob, blob_cap, offs, lens);
 }
 
 extern "C" int amvhip_encode_yuv420_batch(amvhip_ctx* c, const uint8_t* y, const uint8_t* cb, const uint8_t* cr, uint32_t y_stride,
@@ -365,10 +414,10 @@ extern "C" int amvhip_resample_yuv420_dev(amvhip_ctx* c, const uint8_t* d_src_y,
                            false, (hipStream_t)stream);
 }
 
-int amv::encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, uint8_t* d_blob, uint64_t blob_cap,
-                            uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
-    return encode_core(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, PlainQuant{}, d_blob,
-                       blob_cap, d_offs, d_lens, stream);
+int amv::encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, uint8_t* d_blob,
+                            uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
+    return encode_request(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, req, d_blob, blob_cap,
+                          d_offs, d_lens, stream);
 }
 
 // rescale + encode in one call: what ffmpeg.c:757-814 does per picture (sws_scale, then avcodec_encode_video) for a
@@ -389,5 +438,5 @@ extern "C" int amvhip_encode_yuv420_scaled_batch_dev(amvhip_ctx* c, const uint8_
     if (int r = amvhip_resample_yuv420_dev(c, d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, src_w, src_h, dst.p[0],
                                            dst.p[1], dst.p[2], dst.stride[0], dst.stride[1], dst.frame[0], dst.frame[1], w, h, n, stream))
         return r;
-    return encode_scaled_tail(c, n, w, h, qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+    return encode_scaled_tail(c, n, w, h, qbias, PlainQuant{}, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
 }

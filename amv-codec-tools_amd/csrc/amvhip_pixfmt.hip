@@ -309,7 +309,7 @@ extern "C" int amvhip_encode_fmt_scaled_batch_dev(amvhip_ctx* c, int src_fmt, co
     if (int r = ensure(c, c->scaled, amvhip_yuv420_frame_bytes(w, h) * n)) return r;
     const PixPicture dst = tight_420((uint8_t*)c->scaled.p, w, h);
     if (int r = sws_core(c, src_fmt, src, src_w, src_h, AMVHIP_PIX_YUVJ420P, dst, w, h, n, (hipStream_t)stream)) return r;
-    return encode_scaled_tail(c, n, w, h, qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+    return encode_scaled_tail(c, n, w, h, qbias, PlainQuant{}, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
 }
 
 // the decoder of the patched FFmpeg, then img_convert towards what the next stage wants (ffmpeg -i x.amv -pix_fmt ...)
@@ -519,5 +519,34 @@ extern "C" int amvhip_encode_frontend_batch_dev(amvhip_ctx* c, int src_fmt, cons
     std::lock_guard<std::mutex> lk(c->mu);
     if (int r = ensure(c, c->scaled, p.padded_frame_bytes * n)) return r;
     if (int r = frontend_core(c, src_fmt, src, n, fe, p, tight_420((uint8_t*)c->scaled.p, w, h), (hipStream_t)stream)) return r;
-    return encode_scaled_tail(c, n, w, h, qbias, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+    return encode_scaled_tail(c, n, w, h, qbias, PlainQuant{}, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+}
+
+// amvhip_encode_frontend_batch_dev with a quantiser request in the place of qbias: the pictures always go through the
+// context's workspace (the identity front end too: the shim's conversion or copy), and the encoder behind them takes the
+// request -- what amvhip_video_frontend_dev into tight planes and the YUV420 entry of the request give in two calls.
+extern "C" int amvhip_encode_frontend_quant_stream_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1,
+                                                       const uint8_t* d_src2, uint32_t src_stride, uint32_t src_c_stride,
+                                                       uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_w, uint32_t src_h,
+                                                       uint32_t n, const amvhip_frontend* fe, uint32_t w, uint32_t h, const amvhip_quant* q,
+                                                       uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!q) return fail(c, AMVHIP_ERR_ARG, "encode_frontend_quant: the quantiser request is null");
+    if (q->trellis > 1u) return fail(c, AMVHIP_ERR_ARG, "encode_frontend_quant: trellis is 0 or 1");
+    if (!encode_size_ok(w, h, q->qbias) || (n && (!d_blob || !d_offs || !d_lens)))
+        return fail(c, AMVHIP_ERR_ARG, "encode_frontend: bad argument (width/height must be even)");
+    QuantRequest req = PlainQuant{};
+    if (q->trellis) req = NrTrellisRequest{q->nr, q->d_state, q->lambda};
+    else if (q->nr) req = NrRequest{q->nr, q->d_state};
+    if (int r = quant_args_ok(c, n, w, h, req)) return r;
+    const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    FrontPlan p;
+    if (int r = frontend_args_ok(c, src_fmt, src, src_w, src_h, fe, w, h, &p)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    // the padded picture is the context's: the lock is held from its allocation to the last launch that reads it
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int r = ensure(c, c->scaled, p.padded_frame_bytes * n)) return r;
+    if (int r = frontend_core(c, src_fmt, src, n, fe, p, tight_420((uint8_t*)c->scaled.p, w, h), (hipStream_t)stream)) return r;
+    return encode_scaled_tail(c, n, w, h, q->qbias, req, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
 }

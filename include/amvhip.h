@@ -440,6 +440,39 @@ int amvhip_encode_nr_stream(amvhip_ctx *ctx, const uint8_t *pix, uint32_t pix_st
                             uint32_t n, uint32_t width, uint32_t height, uint32_t qbias, uint32_t nr,
                             int32_t *state, uint8_t *blob, uint64_t blob_cap, uint64_t *offs, uint32_t *lens);
 /*
+ * Both levers in one call, `ffmpeg -nr N -trellis 1`: dct_quantize_trellis_c calls denoise_dct right behind the fdct
+ * (mpegvideo_enc.c:2987-2990) and searches on what comes out.  Here too: the sums are taken of the fdct's outputs, the dead
+ * zone is applied, the DC is quantised as ever, and the trellis search of the entries above runs on the denoised AC outputs.
+ * Arguments are those of the -nr stream entries with `lambda` directly behind `nr`, each with its own entry's meaning and
+ * bound:
+ *   nr      : more than amvhip_encode_nr_max(width, height) is refused.  0: the bytes of the trellis entry, the state left
+ *             as it was (and not looked at: it may be NULL).
+ *   lambda  : more than amvhip_encode_trellis_lambda_max() is refused (denoising only shrinks magnitudes, so the bound
+ *             stands).  0 is the trellis at lambda 0, not the plain quantiser.
+ *   d_state : as in the -nr entries, and the same state: the sums do not depend on the quantiser behind them, so a stream
+ *             may change between the -nr entries and these from call to call.  n frames in one call equal the same frames
+ *             in any number of calls with the state carried, byte for byte.
+ * The blob-capacity rule is the plain entries'.  Both entropy modes give the same bytes.
+ */
+int amvhip_encode_yuv420_nr_trellis_stream_dev(amvhip_ctx *ctx, const uint8_t *d_y, const uint8_t *d_cb, const uint8_t *d_cr,
+                                               uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride,
+                                               uint64_t c_frame_stride, uint32_t n, uint32_t width, uint32_t height,
+                                               uint32_t qbias, uint32_t nr, uint32_t lambda, int32_t *d_state, uint8_t *d_blob,
+                                               uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens, void *stream);
+int amvhip_encode_yuv420_nr_trellis_stream(amvhip_ctx *ctx, const uint8_t *y, const uint8_t *cb, const uint8_t *cr,
+                                           uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride,
+                                           uint64_t c_frame_stride, uint32_t n, uint32_t width, uint32_t height,
+                                           uint32_t qbias, uint32_t nr, uint32_t lambda, int32_t *state, uint8_t *blob,
+                                           uint64_t blob_cap, uint64_t *offs, uint32_t *lens);
+int amvhip_encode_nr_trellis_stream_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr,
+                                        uint32_t n, uint32_t width, uint32_t height, uint32_t qbias, uint32_t nr,
+                                        uint32_t lambda, int32_t *d_state, uint8_t *d_blob, uint64_t blob_cap,
+                                        uint64_t *d_offs, uint32_t *d_lens, void *stream);
+int amvhip_encode_nr_trellis_stream(amvhip_ctx *ctx, const uint8_t *pix, uint32_t pix_stride, int is_bgr,
+                                    uint32_t n, uint32_t width, uint32_t height, uint32_t qbias, uint32_t nr,
+                                    uint32_t lambda, int32_t *state, uint8_t *blob, uint64_t blob_cap, uint64_t *offs,
+                                    uint32_t *lens);
+/*
  * ... and from planar YUVJ422P, the other pixel format amv_encoder declares (mjpegenc.c:493; chroma planes (w/2) x h,
  * mpegvideo_enc.c:534-543 h/v sampling 2x2 : 1x2).  The reference would code such a picture as MCUs of eight blocks
  * (ff_mjpeg_encode_mb, mjpegenc.c:437-450, the CHROMA_420 test failing) -- a scan no AMV decoder can read: the container
@@ -637,6 +670,28 @@ int amvhip_encode_frontend_batch_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t
                                      uint64_t src_c_frame_stride, uint32_t src_width, uint32_t src_height, uint32_t n,
                                      const amvhip_frontend *fe, uint32_t width, uint32_t height, uint32_t qbias, uint8_t *d_blob,
                                      uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens, void *stream);
+/*
+ * The front end with a quantiser behind it, `ffmpeg -deinterlace -s 160x120 -nr N -trellis 1` in one call:
+ * amvhip_encode_frontend_batch_dev with the request *q in the place of qbias.  The pictures are made in the context's
+ * workspace (with every front end, the all-zero one included: then the shim's conversion or copy alone) and the encoder
+ * behind them takes the request, so chunks and state are those of amvhip_video_frontend_dev into tight planes followed
+ * by the YUV420 entry of the request -- amvhip_encode_yuv420_batch_dev, _nr_stream_dev, _trellis_batch_dev or
+ * _nr_trellis_stream_dev -- byte for byte.  nr == 0 and trellis == 0 give the bytes of amvhip_encode_frontend_batch_dev.
+ * q == NULL, a trellis other than 0 / 1, and what those entries refuse of nr, lambda and d_state are AMVHIP_ERR_ARG.
+ */
+typedef struct amvhip_quant {
+    uint32_t qbias;
+    uint32_t nr;        /* 0: no noise reduction */
+    uint32_t trellis;   /* 0 / 1 */
+    uint32_t lambda;    /* read when trellis is 1 */
+    int32_t *d_state;   /* int32[65] on the device; required when nr > 0, not touched otherwise */
+} amvhip_quant;
+int amvhip_encode_frontend_quant_stream_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1,
+                                            const uint8_t *d_src2, uint32_t src_stride, uint32_t src_c_stride,
+                                            uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_width,
+                                            uint32_t src_height, uint32_t n, const amvhip_frontend *fe, uint32_t width,
+                                            uint32_t height, const amvhip_quant *q, uint8_t *d_blob, uint64_t blob_cap,
+                                            uint64_t *d_offs, uint32_t *d_lens, void *stream);
 /*
  * Decoder + back end in one call: the patched FFmpeg's amv decoder (AMVHIP_FLAG_FFMPEG, required: AMVHIP_ERR_ARG without)
  * into workspace planes, then img_convert YUVJ420P -> dst_fmt (yuvj420p_to_*, imgconvert.c:1977-1993; the planar route for
