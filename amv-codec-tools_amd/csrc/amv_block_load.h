@@ -71,8 +71,12 @@ __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, const S
                                                     uint32_t lane, uint8_t* s_img, uint32_t (&c)[32], bool& skip) {
     const uint32_t f = sg.f, slot = sg.slot, segidx = sg.segidx, nsegs = sg.nsegs, mcu0 = sg.mcu0, cnt = sg.cnt, ok = sg.ok;
     const uint32_t nb = cnt * 6u;
-    // everything the wave must know before it can ask for its records is requested at once (one round trip to
-    // memory, not three in a row): form of the frame, the segment's record range
+    // What the wave must know before it can ask for its records: the form of the frame and the segment's record range
+    // (asked for together here), how far the frame was decoded (segment_of's load) and where its records begin
+    // (rec_line, below).  In the code object these are three waits for memory in a row, not one: the compiler sinks
+    // each load behind the branch that first uses its value.  Asked for together and waited for once -- held in place
+    // by empty asm statements over scalar registers -- they cost eleven scalar instructions more and bought nothing
+    // that could be measured, so they are left as the compiler places them.
     uint32_t rc = 0xffffffffu, r0 = 0u, r1 = 0u;
     if (in.rec != nullptr && !dense_only) {
         // a segment's records lie in [from of its own entry, to of the next one) -- bounds, not exact positions: the range
@@ -108,7 +112,14 @@ __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, const S
             if (i < nrec) q[j] = *reinterpret_cast<const Rec4*>(rec + i);   // (may read up to 3 words past r1: see ensure())
         }
         uint4* img16 = reinterpret_cast<uint4*>(s_img);
-        for (uint32_t i = lane; i < nb * 8u; i += kWave) img16[i] = make_uint4(0, 0, 0, 0);
+        if (nb == 60u) {   // (wave-uniform) the whole image is seven and a half stores a lane: no test per trip
+            constexpr uint32_t kWhole = 60u * 8u / kWave;
+#pragma unroll
+            for (uint32_t j = 0; j < kWhole; ++j) img16[j * kWave + lane] = make_uint4(0, 0, 0, 0);
+            if (lane < 60u * 8u - kWhole * kWave) img16[kWhole * kWave + lane] = make_uint4(0, 0, 0, 0);
+        } else {
+            for (uint32_t i = lane; i < nb * 8u; i += kWave) img16[i] = make_uint4(0, 0, 0, 0);
+        }
         seg_sync();
         // Scatter, without a branch per record.  A word is index | block field << 6 | filler << 15 | value << 16, the
         // field counting from the frame's end modulo 64.  The index's granule bits (3-5) are XOR-ed with the field's low

@@ -13,8 +13,8 @@
 //      arithmetic -- no transposition, no LDS between the passes;
 //   C. results go to 16-row Y and 8-row U/V planes in LDS (one 16-byte store per block row; the
 //      planes reuse the space of the records' image, which every lane has read by then);
-//   D. colour conversion of a 4x2-pixel patch per lane step, two pixels per instruction in packed
-//      16-bit arithmetic; the 12 bytes of each patch row go
+//   D. colour conversion of a 4x2-pixel patch per lane step, two bytes per instruction in packed
+//      16-bit arithmetic, paired in the order they leave; the 12 bytes of each patch row go
 //      straight to the frame (the lanes of a step cover consecutive 12-byte pieces of a row, so a
 //      wave store is one contiguous run; the picture is stored bottom-up, AmvJpeg.c:800).  A segment that is whole
 //      (ten decoded MCUs, 16 rows inside the picture) takes five unrolled steps without a test per lane; the picture's
@@ -63,6 +63,20 @@ __device__ __forceinline__ int mad24(int x, int w, int c) {
 // row's, kRow4 without), and the column pass neither shifts them up again nor adds: the same numbers modulo 2^32.
 enum RowKind { kRowPlain, kRow0, kRow4 };
 
+// The row pass's two 181-products carry their + 128 in from the odd products.  181 is odd, so there is an s with
+// 181 * 2 s == 128 modulo 2^32: s = 64 / 181 modulo 2^31.  With + s in the chain of W1 x4 + W7 x5 and - s in that of
+// W5 x6 + W3 x7 (the addends of their inner multiply-adds, zero otherwise) the sum of the two is what it was, their
+// difference carries + 2 s, and both 181 * (that difference +- the other one) come out with the 128 in them: exact in
+// the ring of the reference's wrapping int arithmetic.  Not in the column pass: its products are shifted right by 3
+// before they meet, and a seed in front of an arithmetic shift is not exact once the sum wraps.
+constexpr uint32_t inverse_of_odd(uint32_t a) {   // modulo 2^32 (Newton: each step doubles the bits that are right)
+    uint32_t x = a;
+    for (int i = 0; i < 5; ++i) x *= 2u - a * x;
+    return x;
+}
+constexpr int kRowSeed = (int)((64u * inverse_of_odd(181u)) & 0x7fffffffu);
+static_assert(181u * 2u * (uint32_t)kRowSeed == 128u, "the seed puts 128 into both 181-products");
+
 template <bool kColumn, RowKind kKind = kRowPlain>
 __device__ __forceinline__ void idct8(int& v0, int& v1, int& v2, int& v3, int& v4, int& v5, int& v6, int& v7) {
     constexpr int W1 = 2841, W2 = 2676, W3 = 2408, W5 = 1609, W6 = 1108, W7 = 565;
@@ -70,12 +84,13 @@ __device__ __forceinline__ void idct8(int& v0, int& v1, int& v2, int& v3, int& v
     constexpr int kRound = kColumn ? 4 : 0;
     constexpr int kDown = kColumn ? 3 : 0;
     constexpr int kOut = kColumn ? 7 : 8;
+    constexpr int kSeed = kColumn ? 0 : kRowSeed, kHalf = kColumn ? 128 : 0;
     int a0 = kColumn ? v0 : v0 * 2048 + kBias, a1 = kColumn ? v4 : v4 * 2048;   // (<<11; the column's <<8 is done)
     const int i2 = v6, i3 = v2, i4 = v1, i5 = v7, i6 = v5, i7 = v3;
     int t;
-    int a4 = mad24(i4, W1, mad24(i5, W7, kRound)) >> kDown;     // W7*(x4+x5) + (W1-W7)*x4
+    int a4 = mad24(i4, W1, mad24(i5, W7, kRound + kSeed)) >> kDown;     // W7*(x4+x5) + (W1-W7)*x4
     int a5 = mad24(i4, W7, mad24(i5, -W1, kRound)) >> kDown;    // W7*(x4+x5) - (W1+W7)*x5
-    int a6 = mad24(i6, W5, mad24(i7, W3, kRound)) >> kDown;     // W3*(x6+x7) - (W3-W5)*x6
+    int a6 = mad24(i6, W5, mad24(i7, W3, kRound - kSeed)) >> kDown;     // W3*(x6+x7) - (W3-W5)*x6
     int a7 = mad24(i6, W3, mad24(i7, -W5, kRound)) >> kDown;    // W3*(x6+x7) - (W3+W5)*x7
     t = a0 + a1;
     a0 -= a1;
@@ -89,8 +104,8 @@ __device__ __forceinline__ void idct8(int& v0, int& v1, int& v2, int& v3, int& v
     t -= a3;
     a3 = a0 + a2;
     a0 -= a2;
-    a2 = (181 * (a4 + a5) + 128) >> 8;
-    a4 = (181 * (a4 - a5) + 128) >> 8;
+    a2 = (181 * (a4 + a5) + kHalf) >> 8;      // (the row pass: the 128 came in with the seeds)
+    a4 = (181 * (a4 - a5) + kHalf) >> 8;
     v0 = a7 + a1;
     v1 = a3 + a2;
     v2 = a0 + a4;
@@ -141,18 +156,13 @@ __device__ __forceinline__ uint32_t dot2_bias(uint32_t a, uint32_t w) {
     return d;
 }
 
-// two pixels of one channel: (y0 + c, y1 + c) clamped to 0..255, in bytes 0 and 1
-__device__ __forceinline__ uint32_t sat_pair(uint32_t yy, uint32_t cc) {
-    uint32_t sum, d;
-    asm("v_pk_add_i16 %0, %1, %2" : "=v"(sum) : "v"(yy), "v"(cc));
-    asm("v_sat_pk_u8_i16 %0, %1" : "=v"(d) : "v"(sum));
-    return d;
-}
-
-// Stage D's arithmetic for one 4x2 patch (both of its loops use it).  The chroma terms of the patch's two chroma samples
-// (uu, vv: two int16 each): (u, v) of sample e as one pair of int16; each term (:808-810, +128) is one two-element dot
-// product, and bytes 1-2 of it -- the term >> 8 -- go into both halves of a dword with one byte permute.
-struct ChromaTerms { uint32_t r[2], g[2], b[2]; };
+// Stage D's arithmetic for one 4x2 patch (both of its loops use it), on byte pairs in the order they leave.  The twelve
+// bytes of a patch row are (B0 G0)(R0 B1)(G1 R1)(B2 G2)(R2 B3)(G3 R3): each bracket is one packed add of a luma pair
+// and a chroma pair, and one saturating pack.
+// The chroma pairs of the patch's two chroma samples (uu, vv: two int16 each): (u, v) of sample e as one pair of int16;
+// each term (:808-810, +128) is one two-element dot product, and bytes 1-2 of two of them -- the terms >> 8 -- make
+// the pairs (b, g), (r, b) and (g, r) with one byte permute each.
+struct ChromaTerms { uint32_t bg[2], rb[2], gr[2]; };
 __device__ __forceinline__ ChromaTerms chroma_terms(uint32_t uu, uint32_t vv) {
     ChromaTerms c;
 #pragma unroll
@@ -161,22 +171,39 @@ __device__ __forceinline__ ChromaTerms chroma_terms(uint32_t uu, uint32_t vv) {
         const uint32_t r = dot2_bias(uv, pair16(18, 367));
         const uint32_t gg = dot2_bias(uv, pair16(-159, -220));
         const uint32_t b = dot2_bias(uv, pair16(411, -29));
-        c.r[e] = __builtin_amdgcn_perm(r, r, 0x02010201u);
-        c.g[e] = __builtin_amdgcn_perm(gg, gg, 0x02010201u);
-        c.b[e] = __builtin_amdgcn_perm(b, b, 0x02010201u);
+        c.bg[e] = __builtin_amdgcn_perm(gg, b, 0x06050201u);
+        c.rb[e] = __builtin_amdgcn_perm(b, r, 0x06050201u);
+        c.gr[e] = __builtin_amdgcn_perm(r, gg, 0x06050201u);
     }
     return c;
 }
-// ... and the twelve bytes of one of its rows (yy: four int16 of luma)
+// One dword of the row: (ya + c0.lo, yb + c0.hi, yc + c1.lo, yd + c1.hi) clamped to 0..255 (:812-827), a byte each.
+// The luma of a bracket is (y.lo, y.lo), (y.lo, y.hi) or (y.hi, y.hi) of one luma pair: kLo / kHi say which half of y
+// goes to the add's low / high result (op_sel and op_sel_hi of the first operand: no instruction of their own).  The
+// first pack writes bytes 0-1 of the dword and zeroes the rest, the second (SDWA, UNUSED_PRESERVE) its high half in place.
+// (Nothing but the frame store reads such a dword: the compiler does not see into these statements and pads no hazard
+// for them, and the one this chip has behind a write of half a register concerns a vector instruction that reads it.)
+template <int kLo, int kHi>
+__device__ __forceinline__ uint32_t pair_sum(uint32_t yy, uint32_t cc) {
+    uint32_t sum;
+    if (kLo == 0 && kHi == 0) asm("v_pk_add_i16 %0, %1, %2 op_sel_hi:[0,1]" : "=v"(sum) : "v"(yy), "v"(cc));
+    else if (kLo == 0 && kHi == 1) asm("v_pk_add_i16 %0, %1, %2" : "=v"(sum) : "v"(yy), "v"(cc));
+    else asm("v_pk_add_i16 %0, %1, %2 op_sel:[1,0]" : "=v"(sum) : "v"(yy), "v"(cc));
+    static_assert(kLo <= kHi, "(hi, lo) is not a bracket of the row");
+    return sum;
+}
+__device__ __forceinline__ uint32_t sat_quad(uint32_t lo, uint32_t hi) {
+    uint32_t d;
+    asm("v_sat_pk_u8_i16 %0, %1" : "=v"(d) : "v"(lo));
+    asm("v_sat_pk_u8_i16_sdwa %0, %1 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD" : "+v"(d) : "v"(hi));
+    return d;
+}
+// ... and the twelve bytes of one of its rows (yy: four int16 of luma), :829-831 B,G,R
 __device__ __forceinline__ Px12 patch_row(uint2 yy, const ChromaTerms& c) {
-    const uint32_t b01 = sat_pair(yy.x, c.b[0]), g01 = sat_pair(yy.x, c.g[0]), r01 = sat_pair(yy.x, c.r[0]);
-    const uint32_t b23 = sat_pair(yy.y, c.b[1]), g23 = sat_pair(yy.y, c.g[1]), r23 = sat_pair(yy.y, c.r[1]);
-    const uint32_t gr = g01 | (r01 << 16);                         // G0 G1 R0 R1
-    const uint32_t bg = b23 | (g23 << 16);                         // B2 B3 G2 G3
-    Px12 v;                                                        // :829-831 B,G,R
-    v.w[0] = __builtin_amdgcn_perm(gr, b01, 0x01060400u);          // B0 G0 R0 B1
-    v.w[1] = __builtin_amdgcn_perm(bg, gr, 0x06040301u);           // G1 R1 B2 G2
-    v.w[2] = __builtin_amdgcn_perm(bg, r23, 0x01070500u);          // R2 B3 G3 R3
+    Px12 v;
+    v.w[0] = sat_quad(pair_sum<0, 0>(yy.x, c.bg[0]), pair_sum<0, 1>(yy.x, c.rb[0]));   // B0 G0 R0 B1
+    v.w[1] = sat_quad(pair_sum<1, 1>(yy.x, c.gr[0]), pair_sum<0, 0>(yy.y, c.bg[1]));   // G1 R1 B2 G2
+    v.w[2] = sat_quad(pair_sum<0, 1>(yy.y, c.rb[1]), pair_sum<1, 1>(yy.y, c.gr[1]));   // R2 B3 G3 R3
     return v;
 }
 
@@ -262,9 +289,10 @@ __global__ __launch_bounds__(kWave * kRows) void amv_reconstruct_kernel(
     // ---- D: StoreBuffer (AmvJpeg.c:789-840), straight to the frame.  A lane takes a 4x2-pixel patch: the two rows
     // share their chroma samples, whose three products (:808-810) are formed once, with luma's +128 folded in:
     // (256 (y + 128) + c) >> 8 == y + ((c + 32768) >> 8) exactly.  Everything that follows fits 16 bits (|y| <= 256,
-    // |c >> 8| <= 440), so two pixels go through each instruction: v_pk_add_i16 adds the pair's luma to the (doubled)
-    // chroma term, v_sat_pk_u8_i16 clamps both to 0..255 (:812-827) and packs them into two bytes, and three byte
-    // permutes interleave B, G, R.  MCUs that were not decoded get y = -1024, c = 0: every channel clamps to 0.
+    // |c >> 8| <= 440), so two bytes go through each instruction, paired as they lie in the row (patch_row): v_pk_add_i16
+    // adds a pair of luma values to a pair of chroma terms, v_sat_pk_u8_i16 clamps both sums to 0..255 (:812-827) and packs
+    // them into two bytes of their dword -- twelve instructions a row, nothing to interleave afterwards.  MCUs that
+    // were not decoded get y = -1024, c = 0: every channel clamps to 0.
     const uint32_t vr = min(16u, g.height - my * 16u);                 // rows of this MCU row inside the picture (:798); even
     const uint32_t px = min(cnt * 16u, g.width - m0 * 16u);            // pixels of this segment inside it (:803)
     const uint32_t groups = cnt * 4u;
