@@ -145,6 +145,14 @@ SYMBOLS = {
     "amvhip_video_frontend_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _vp]),
     "amvhip_encode_frontend_batch_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp]),
     "amvhip_encode_frontend_quant_stream_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp]),
+    "amvhip_psnr_db": (ctypes.c_double, [_u64, _u64]),
+    "amvhip_psnr_report": (None, [_vp, _u32, _u32, _u32, _vp]),
+    "amvhip_picture_sse_supported": (_int, [_int, _u32, _u32]),
+    "amvhip_picture_sse_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp]),
+    "amvhip_picture_sse": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
+    "amvhip_encode_quant_psnr_stream_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_yuv420_quant_psnr_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_frontend_quant_psnr_stream_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "amvhip_decode_fmt_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
     "amvhip_lowres_dim": (_u32, [_u32, _u32]),
     "amvhip_lowres_frame_bytes": (_u64, [_u32, _u32, _u32]),
@@ -523,6 +531,42 @@ class Context:
                                                                             w, h, q, _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), stream),
                            "encode_frontend_quant_stream_dev")
 
+    # `-psnr`: the encoder's own error beside the chunks (sse: uint64 [n][3] on the device), and picture against picture
+    def encode_quant_psnr_stream_dev(self, pix, pix_stride, is_bgr, n, w, h, quant, blob, blob_cap, offs, lens, sse, stream=None):
+        """encode_batch_dev / _nr_stream_dev / _trellis_batch_dev / _nr_trellis_stream_dev by the Quant, and per frame and plane
+        the squared error between the handed picture and the reconstruction of the coded levels"""
+        q = None if quant is None else ctypes.addressof(quant)
+        return self._check(self.lib.amvhip_encode_quant_psnr_stream_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, q, _ptr(blob),
+                                                                        blob_cap, _ptr(offs), _ptr(lens), _ptr(sse), stream),
+                           "encode_quant_psnr_stream_dev")
+
+    def encode_yuv420_quant_psnr_stream_dev(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, quant, blob, blob_cap, offs,
+                                            lens, sse, stream=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        return self._check(self.lib.amvhip_encode_yuv420_quant_psnr_stream_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride,
+                                                                               y_frame, c_frame, n, w, h, q, _ptr(blob), blob_cap,
+                                                                               _ptr(offs), _ptr(lens), _ptr(sse), stream),
+                           "encode_yuv420_quant_psnr_stream_dev")
+
+    def encode_frontend_quant_psnr_stream_dev(self, src_fmt, src, src_w, src_h, n, fe, w, h, quant, blob, blob_cap, offs, lens, sse,
+                                              stream=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        return self._check(self.lib.amvhip_encode_frontend_quant_psnr_stream_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n,
+                                                                                 self._fe(fe), w, h, q, _ptr(blob), blob_cap, _ptr(offs),
+                                                                                 _ptr(lens), _ptr(sse), stream),
+                           "encode_frontend_quant_psnr_stream_dev")
+
+    def picture_sse_supported(self, fmt, w, h):
+        return picture_sse_supported(fmt, w, h)
+
+    def picture_sse_dev(self, fmt, a, b, w, h, n, sse, stream=None):
+        """two batches of n pictures of one format (each as in img_convert_dev) -> sse uint64 [n][3] on the device"""
+        return self._check(self.lib.amvhip_picture_sse_dev(self.h, fmt, *self._pic(a), *self._pic(b), w, h, n, _ptr(sse), stream),
+                           "picture_sse_dev")
+
+    def picture_sse(self, fmt, a, b, w, h, n, sse):
+        return self._check(self.lib.amvhip_picture_sse(self.h, fmt, *self._pic(a), *self._pic(b), w, h, n, _ptr(sse)), "picture_sse")
+
     def decode_fmt_batch_dev(self, blob, blob_bytes, offs, lens, n, w, h, flags, dst_fmt, out, out_stride, status, stream=None):
         return self._check(self.lib.amvhip_decode_fmt_batch_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, flags,
                                                                 dst_fmt, _ptr(out), out_stride, _ptr(status), stream),
@@ -657,6 +701,24 @@ class Context:
 
     def kernel_name(self, kernel):
         return self.lib.amvhip_kernel_name(kernel).decode()
+
+
+def psnr_db(sse, samples):
+    """ffmpeg's psnr() on sse / (samples * 255^2), dB: inf at sse == 0, nan at samples == 0 (host arithmetic, no device)"""
+    return load_library().amvhip_psnr_db(int(sse), int(samples))
+
+
+def psnr_report(sse, w, h):
+    """the last-report PSNR line over the frames of sse (uint64 [n][3], numpy) -> (Y, U, V, *) in dB"""
+    import numpy as np
+    sse = np.ascontiguousarray(sse, np.uint64).reshape(-1, 3)
+    out = (ctypes.c_double * 4)()
+    load_library().amvhip_psnr_report(sse.ctypes.data, sse.shape[0], w, h, ctypes.cast(out, ctypes.c_void_p))
+    return tuple(out)
+
+
+def picture_sse_supported(fmt, w, h):
+    return load_library().amvhip_picture_sse_supported(fmt, w, h)
 
 
 def audio_resample_out_samples(in_rate, out_rate, in_samples):

@@ -259,6 +259,39 @@ inline uint64_t pix_frame_bytes(int fmt, uint32_t stride, uint32_t height) {
     return (uint64_t)stride * height + 2 * cs * cr;
 }
 
+// ---- `-psnr`: from summed squared errors to the figures ffmpeg prints ---------------------------------------------------
+
+// psnr() of ffmpeg.c:849-852 on d = sse / (samples * 255^2): INFINITY at d == 0; NaN where there are no samples
+inline double psnr_db(uint64_t sse, uint64_t samples) {
+    if (samples == 0) return NAN;
+    const double d = (double)sse / ((double)samples * 255.0 * 255.0);
+    if (d == 0) return INFINITY;
+    return -10.0 * log(d) / log(10.0);
+}
+
+// the last-report line of ffmpeg.c:953-972 over n frames of width x height whose plane errors are sse[n][3]: Y, U, V and *
+// (the summed errors over the summed scales).  The luma scale is width * height * 255^2 * n, a chroma scale a quarter of it.
+inline void psnr_report(const uint64_t* sse, uint32_t n, uint32_t width, uint32_t height, double out[4]) {
+    double error_sum = 0, scale_sum = 0;
+    for (int j = 0; j < 3; ++j) {
+        uint64_t e = 0;
+        for (uint32_t i = 0; i < n; ++i) e += sse[(size_t)i * 3 + j];
+        const double error = (double)e;
+        double scale = (double)((uint64_t)width * height) * 255.0 * 255.0 * n;
+        if (j) scale /= 4;
+        error_sum += error;
+        scale_sum += scale;
+        out[j] = scale == 0 ? NAN : (error == 0 ? INFINITY : -10.0 * log(error / scale) / log(10.0));
+    }
+    out[3] = scale_sum == 0 ? NAN : (error_sum == 0 ? INFINITY : -10.0 * log(error_sum / scale_sum) / log(10.0));
+}
+
+// what amvhip_picture_sse_dev takes: the six planar YUV formats, GRAY8, RGB24 and BGR24, at every size the decoder takes
+inline int picture_sse_ok(int fmt, uint32_t w, uint32_t h) {
+    const bool listed = pix_planar_yuv(fmt) || fmt == AMVHIP_PIX_GRAY8 || fmt == AMVHIP_PIX_RGB24 || fmt == AMVHIP_PIX_BGR24;
+    return listed && size_ok(w, h);
+}
+
 // ---- video front end: deinterlace, crop, rescale / convert, pad (pre_process_video_frame + do_video_out) --------------
 
 // avpicture_deinterlace's own list (imgconvert.c:2824-2831) among our formats; the YUVJ formats are not in it

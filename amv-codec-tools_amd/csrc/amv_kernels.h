@@ -182,6 +182,11 @@ void launch_forward(const Source& in, uint32_t n, const FrameSel& sel, uint32_t 
                     const Quantiser& quant, int16_t* coef, hipStream_t s);
 void launch_pack(const int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g,
                  const HuffEncodeImage* d_img, uint8_t* tmp, uint32_t bound, uint32_t* lens, hipStream_t s);
+// The encoder's own error (amv_encode_error.hip): for the frames of `sel` whose dense lines launch_forward wrote to coef, the
+// squared error between the source's planes and simple_idct_put of level * Q, summed over the samples inside the picture
+// and ADDED to sse [n][3] uint64 (Y, Cb, Cr of frame f at sse[3 f ..]; the caller zeroes it).  sel and items as launch_forward's.
+void launch_encode_error(const Source& in, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const int16_t* coef,
+                         uint64_t* sse, hipStream_t s);
 // exclusive scan of lens -> offs (single workgroup), then gather tmp -> blob.  A chunk that would end past
 // blob_cap is not copied and its lens entry becomes 0; *overflow = 1 when the total exceeds blob_cap.
 void launch_compact(const uint8_t* tmp, uint32_t bound, uint32_t* lens, uint32_t n,
@@ -242,6 +247,21 @@ void launch_pix_rgb_in(const PixPicture& src, const PixPicture& dst, uint32_t w,
                        hipStream_t s);
 void launch_pix_rgb_out(const PixPicture& src, const PixPicture& dst, uint32_t w, uint32_t h, uint32_t bpp, const PixRgbOut& k, uint32_t n,
                         hipStream_t s);
+
+// ---- picture against picture (amv_picture_sse.hip) --------------------------------------------------------------------
+struct SsePlane {           // one plane of both pictures: rows of row_bytes bytes; frame i at a + i*aframe, b + i*bframe
+    const uint8_t* a;
+    const uint8_t* b;
+    uint32_t astride, bstride;
+    uint64_t aframe, bframe;
+    uint32_t row_bytes, rows;
+    uint32_t entry;         // interleave 1: the plane's sum goes to entry `entry` of the frame's three
+    uint32_t interleave;    // 3: a packed plane, byte x belongs to entry x % 3
+    uint32_t tiles_x, tiles;   // (the launcher's)
+};
+struct SseJobs { SsePlane j[3]; uint32_t count; };
+// the squared differences of n frames ADDED to sse [n][3] uint64 (the caller zeroes it)
+void launch_picture_sse(SseJobs jobs, uint32_t n, uint64_t* sse, hipStream_t s);
 
 // ---- video front end (amv_frontend.hip): avpicture_deinterlace and av_picture_pad's bands ------------------------------
 struct DeintPlane {         // one plane: the window x0, y0, w, h of a source plane of full_h rows -> a destination of w x h

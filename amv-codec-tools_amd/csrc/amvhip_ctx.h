@@ -201,10 +201,19 @@ struct NrTrellisRequest {
 using QuantRequest = std::variant<PlainQuant, NrRequest, TrellisArg, NrTrellisRequest>;
 // what a request asks beyond the plain entries' checks; 0 = go on
 int quant_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const QuantRequest& req);
+// the request an amvhip_quant stands for (its state is on the device); q == NULL and a trellis other than 0 / 1 are refused
+int quant_request_of(amvhip_ctx* c, const amvhip_quant* q, QuantRequest* req);
+// where a _psnr entry wants the frames' error: uint64 [n][3] on the device, 8-byte aligned (wanted == false: the entry has none)
+struct ErrorSink {
+    uint64_t* sse;
+    bool wanted;
+};
+constexpr ErrorSink kNoError{nullptr, false};
+int error_sink_ok(amvhip_ctx* c, uint32_t n, const ErrorSink& err);
 // the tail of the scaled encoders: the w x h pictures they made as tight_420 in c->scaled, through the request's core
-// (req's state is on the device)
+// (req's state is on the device; d_sse: the frames' error, for the _psnr entry)
 int encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, uint8_t* d_blob,
-                       uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream);
+                       uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream, uint64_t* d_sse = nullptr);
 int resample_launch(amvhip_ctx* c, const PixPicture& src, uint32_t src_w, uint32_t src_h, const PixPicture& dst, uint32_t dst_w, uint32_t dst_h,
                     uint32_t n, bool to_jpeg, hipStream_t st);
 

@@ -45,6 +45,19 @@ int amv::quant_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const 
     return AMVHIP_OK;
 }
 
+int amv::quant_request_of(amvhip_ctx* c, const amvhip_quant* q, QuantRequest* req) {
+    if (!q) return fail(c, AMVHIP_ERR_ARG, "encode_quant: the quantiser request is null");
+    if (q->trellis > 1u) return fail(c, AMVHIP_ERR_ARG, "encode_quant: trellis is 0 or 1");
+    *req = PlainQuant{};
+    if (q->trellis) *req = NrTrellisRequest{q->nr, q->d_state, q->lambda};
+    else if (q->nr) *req = NrRequest{q->nr, q->d_state};
+    return AMVHIP_OK;
+}
+int amv::error_sink_ok(amvhip_ctx* c, uint32_t n, const ErrorSink& err) {
+    if (err.wanted && n && (!err.sse || ((uintptr_t)err.sse & 7u))) return fail(c, AMVHIP_ERR_ARG, "encode_psnr: d_sse is null or not 8-byte aligned");
+    return AMVHIP_OK;
+}
+
 // amvhip_encode_coefs_dev and its trellis form: amv_forward_kernel's lines for the caller (no workspace, so no lock)
 static int encode_coefs(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias,
                         const Quantiser& quant, int16_t* d_coef, void* stream, const char* what) {
@@ -76,8 +89,28 @@ extern "C" int amvhip_encode_trellis_coefs_dev(amvhip_ctx* c, const uint8_t* d_p
 // the whole batch in AMVHIP_ENTROPY_SERIAL mode -- goes through amv_forward_kernel + amv_pack_kernel a round of dense lines
 // at a time (with a list the count is on the device: the rounds past it find nothing to do and leave at once -- usually all
 // of them).  Both routes run the instantiation of `quant`.
+// d_sse (the _psnr entries; else nullptr): the frames' error, amv_encode_error.hip, off the dense lines of `quant`'s
+// instantiation of amv_forward_kernel -- in AMVHIP_ENTROPY_SERIAL mode the lines the call packs, between the two launches;
+// otherwise the one-kernel encoder keeps its levels on the chip, so the front half runs a second time for all frames, a
+// round of the workspace at a time, as default launches over the round's part of the source.
+static Source frames_from(const Source& in, uint32_t base, const FrameGeom& g) {
+    Source s = in;
+    if (s.planar) {
+        s.yuv.y += (uint64_t)base * s.yuv.y_frame;
+        s.yuv.cb += (uint64_t)base * s.yuv.c_frame;
+        s.yuv.cr += (uint64_t)base * s.yuv.c_frame;
+    } else {
+        s.pix += (uint64_t)base * s.pix_stride * g.height;
+    }
+    return s;
+}
+static Quantiser frames_from(const Quantiser& quant, uint32_t base) {   // (the offsets are 64 per frame)
+    if (const uint16_t* const* o = std::get_if<const uint16_t*>(&quant)) return Quantiser{*o + (uint64_t)base * 64u};
+    if (const NrTrellisArg* t = std::get_if<NrTrellisArg>(&quant)) return Quantiser{NrTrellisArg{t->offsets + (uint64_t)base * 64u, t->lambda}};
+    return quant;
+}
 static int encode_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, const Quantiser& quant, uint8_t* d_blob,
-                       uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
+                       uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse, hipStream_t stream) {
     const uint32_t bound = amvhip_encode_bound(g.width, g.height);
     const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
     const uint32_t round = fallback_round(n, g, 1024u, 2u);
@@ -88,6 +121,7 @@ static int encode_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameG
     uint32_t* retry_count = (uint32_t*)c->enc_retry.p;
     uint32_t* retry_list = retry_count + 8;
     HIP_TRY(c, hipMemsetAsync(retry_count, 0, 32, stream));
+    if (d_sse) HIP_TRY(c, hipMemsetAsync(d_sse, 0, (size_t)n * 24u, stream));
     const bool fused = c->entropy_mode != AMVHIP_ENTROPY_SERIAL;
     if (fused) {
         Timed t(c, AMVHIP_K_PACK, stream);
@@ -100,12 +134,23 @@ static int encode_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameG
         {
             Timed t(c, AMVHIP_K_FDCT, stream);
             launch_forward(in, n, sel, items, g, qbias, quant, (int16_t*)c->coef.p, stream);
+            if (d_sse && !fused) launch_encode_error(in, n, sel, items, g, (const int16_t*)c->coef.p, d_sse, stream);
         }
         {
             Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
             launch_pack((const int16_t*)c->coef.p, n, sel, items, g, book, (uint8_t*)c->tmp.p, bound, d_lens, stream);
         }
         if (int r = check_launch(c, "forward + pack")) return r;
+    }
+    for (uint32_t base = 0; d_sse && fused && base < n; base += round) {
+        const uint32_t items = n - base < round ? n - base : round;
+        {
+            Timed t(c, AMVHIP_K_FDCT, stream);
+            const Source part = frames_from(in, base, g);
+            launch_forward(part, items, kAllFrames, items, g, qbias, frames_from(quant, base), (int16_t*)c->coef.p, stream);
+            launch_encode_error(part, items, kAllFrames, items, g, (const int16_t*)c->coef.p, d_sse + (uint64_t)base * 3u, stream);
+        }
+        if (int r = check_launch(c, "forward + error")) return r;
     }
     {
         Timed t(c, AMVHIP_K_COMPACT, stream);
@@ -118,7 +163,8 @@ static int encode_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameG
 // d_state, and the encoder with the offsets the chain wrote -- rounding behind them, or, with a lambda, searching.  The sums
 // are taken before the offsets are applied, so the state does not depend on which.
 static int encode_nr_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, uint32_t nr, int32_t* d_state,
-                          const uint32_t* lambda, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
+                          const uint32_t* lambda, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse,
+                          hipStream_t stream) {
     const NrPlan plan = nr_plan(n);
     if (int r = ensure(c, c->nr_ws, plan.bytes)) return r;
     uint32_t* sums = (uint32_t*)((uint8_t*)c->nr_ws.p + plan.sums);
@@ -127,24 +173,26 @@ static int encode_nr_core(amvhip_ctx* c, const Source& in, uint32_t n, const Fra
     launch_nr_chain(sums, n, g.blocks, nr, d_state, offsets, stream);
     if (int r = check_launch(c, "nr sums + chain")) return r;
     return encode_core(c, in, n, g, qbias, lambda ? Quantiser{NrTrellisArg{offsets, *lambda}} : Quantiser{offsets}, d_blob, blob_cap, d_offs, d_lens,
-                       stream);
+                       d_sse, stream);
 }
 
 // the request's core (the context is locked, the request checked, n > 0; req's state is on the device)
 static int encode_request(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, QuantRequest req, uint8_t* d_blob,
-                          uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
+                          uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse, hipStream_t stream) {
     uint32_t lambda;
     const bool trellis = lambda_of(req, &lambda);
     NrPart q;
     if (nr_part_of(req, &q) && q.nr)
-        return encode_nr_core(c, in, n, g, qbias, q.nr, *q.state, trellis ? &lambda : nullptr, d_blob, blob_cap, d_offs, d_lens, stream);
-    return encode_core(c, in, n, g, qbias, trellis ? Quantiser{TrellisArg{lambda}} : Quantiser{PlainQuant{}}, d_blob, blob_cap, d_offs, d_lens, stream);
+        return encode_nr_core(c, in, n, g, qbias, q.nr, *q.state, trellis ? &lambda : nullptr, d_blob, blob_cap, d_offs, d_lens, d_sse, stream);
+    return encode_core(c, in, n, g, qbias, trellis ? Quantiser{TrellisArg{lambda}} : Quantiser{PlainQuant{}}, d_blob, blob_cap, d_offs, d_lens, d_sse,
+                       stream);
 }
 
 // Every device-pointer encoder whole: the checks of the live half of `in`, of the outputs and of the request, n == 0, the
 // device, the lock (held from the workspace's allocation to the last launch), the request's core.  req's state is on the device.
+// err: where a _psnr entry wants the frames' error (kNoError: not asked for).
 static int encode_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req,
-                      uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+                      uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream, const ErrorSink& err = kNoError) {
     if (!c) return AMVHIP_ERR_ARG;
     const bool no_out = n && (!d_blob || !d_offs || !d_lens);
     if (in.planar) {
@@ -156,10 +204,12 @@ static int encode_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, u
         if (no_out) return fail(c, AMVHIP_ERR_ARG, "encode: null output");
     }
     if (int r = quant_args_ok(c, n, w, h, req)) return r;
+    if (int r = error_sink_ok(c, n, err)) return r;
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
-    return encode_request(c, in, n, make_geom(w, h), qbias, req, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+    return encode_request(c, in, n, make_geom(w, h), qbias, req, d_blob, blob_cap, d_offs, d_lens, err.wanted ? err.sse : nullptr,
+                          (hipStream_t)stream);
 }
 
 extern "C" int amvhip_encode_batch_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
@@ -225,6 +275,28 @@ extern "C" int amvhip_encode_yuv420_nr_trellis_stream_dev(amvhip_ctx* c, const u
                                                           void* stream) {
     return encode_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, qbias,
                       NrTrellisRequest{nr, d_state, lambda}, d_blob, blob_cap, d_offs, d_lens, stream);
+}
+
+// ---- the _psnr entries: a request (amvhip_quant) in the place of qbias, and the frames' error beside the chunks ---------
+extern "C" int amvhip_encode_quant_psnr_stream_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
+                                                   uint32_t h, const amvhip_quant* q, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs,
+                                                   uint32_t* d_lens, uint64_t* d_sse, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    QuantRequest req;
+    if (int r = quant_request_of(c, q, &req)) return r;
+    return encode_dev(c, rgb_source(d_pix, pix_stride, is_bgr), n, w, h, q->qbias, req, d_blob, blob_cap, d_offs, d_lens, stream,
+                      ErrorSink{d_sse, true});
+}
+
+extern "C" int amvhip_encode_yuv420_quant_psnr_stream_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr,
+                                                          uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                                          uint32_t n, uint32_t w, uint32_t h, const amvhip_quant* q, uint8_t* d_blob,
+                                                          uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    QuantRequest req;
+    if (int r = quant_request_of(c, q, &req)) return r;
+    return encode_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, q->qbias, req, d_blob,
+                      blob_cap, d_offs, d_lens, stream, ErrorSink{d_sse, true});
 }
 
 // the device-to-host half of the host-buffer encoders: offs/lens, then the chunks
@@ -415,9 +487,9 @@ extern "C" int amvhip_resample_yuv420_dev(amvhip_ctx* c, const uint8_t* d_src_y,
 }
 
 int amv::encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, uint8_t* d_blob,
-                            uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream) {
+                            uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream, uint64_t* d_sse) {
     return encode_request(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, req, d_blob, blob_cap,
-                          d_offs, d_lens, stream);
+                          d_offs, d_lens, d_sse, stream);
 }
 
 // rescale + encode in one call: what ffmpeg.c:757-814 does per picture (sws_scale, then avcodec_encode_video) for a

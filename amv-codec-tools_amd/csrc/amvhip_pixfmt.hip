@@ -525,20 +525,18 @@ extern "C" int amvhip_encode_frontend_batch_dev(amvhip_ctx* c, int src_fmt, cons
 // amvhip_encode_frontend_batch_dev with a quantiser request in the place of qbias: the pictures always go through the
 // context's workspace (the identity front end too: the shim's conversion or copy), and the encoder behind them takes the
 // request -- what amvhip_video_frontend_dev into tight planes and the YUV420 entry of the request give in two calls.
-extern "C" int amvhip_encode_frontend_quant_stream_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1,
-                                                       const uint8_t* d_src2, uint32_t src_stride, uint32_t src_c_stride,
-                                                       uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_w, uint32_t src_h,
-                                                       uint32_t n, const amvhip_frontend* fe, uint32_t w, uint32_t h, const amvhip_quant* q,
-                                                       uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+// err: where the _psnr form wants the frames' error (the error of the workspace pictures against what was coded of them)
+static int frontend_quant(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2, uint32_t src_stride,
+                          uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_w, uint32_t src_h, uint32_t n,
+                          const amvhip_frontend* fe, uint32_t w, uint32_t h, const amvhip_quant* q, uint8_t* d_blob, uint64_t blob_cap,
+                          uint64_t* d_offs, uint32_t* d_lens, const ErrorSink& err, void* stream) {
     if (!c) return AMVHIP_ERR_ARG;
-    if (!q) return fail(c, AMVHIP_ERR_ARG, "encode_frontend_quant: the quantiser request is null");
-    if (q->trellis > 1u) return fail(c, AMVHIP_ERR_ARG, "encode_frontend_quant: trellis is 0 or 1");
+    QuantRequest req;
+    if (int r = quant_request_of(c, q, &req)) return r;
     if (!encode_size_ok(w, h, q->qbias) || (n && (!d_blob || !d_offs || !d_lens)))
         return fail(c, AMVHIP_ERR_ARG, "encode_frontend: bad argument (width/height must be even)");
-    QuantRequest req = PlainQuant{};
-    if (q->trellis) req = NrTrellisRequest{q->nr, q->d_state, q->lambda};
-    else if (q->nr) req = NrRequest{q->nr, q->d_state};
     if (int r = quant_args_ok(c, n, w, h, req)) return r;
+    if (int r = error_sink_ok(c, n, err)) return r;
     const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
     FrontPlan p;
     if (int r = frontend_args_ok(c, src_fmt, src, src_w, src_h, fe, w, h, &p)) return r;
@@ -548,5 +546,123 @@ extern "C" int amvhip_encode_frontend_quant_stream_dev(amvhip_ctx* c, int src_fm
     std::lock_guard<std::mutex> lk(c->mu);
     if (int r = ensure(c, c->scaled, p.padded_frame_bytes * n)) return r;
     if (int r = frontend_core(c, src_fmt, src, n, fe, p, tight_420((uint8_t*)c->scaled.p, w, h), (hipStream_t)stream)) return r;
-    return encode_scaled_tail(c, n, w, h, q->qbias, req, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream);
+    return encode_scaled_tail(c, n, w, h, q->qbias, req, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream, err.wanted ? err.sse : nullptr);
+}
+
+extern "C" int amvhip_encode_frontend_quant_stream_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1,
+                                                       const uint8_t* d_src2, uint32_t src_stride, uint32_t src_c_stride,
+                                                       uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_w, uint32_t src_h,
+                                                       uint32_t n, const amvhip_frontend* fe, uint32_t w, uint32_t h, const amvhip_quant* q,
+                                                       uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream) {
+    return frontend_quant(c, src_fmt, d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride, src_w, src_h, n, fe,
+                          w, h, q, d_blob, blob_cap, d_offs, d_lens, kNoError, stream);
+}
+
+extern "C" int amvhip_encode_frontend_quant_psnr_stream_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1,
+                                                            const uint8_t* d_src2, uint32_t src_stride, uint32_t src_c_stride,
+                                                            uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_w,
+                                                            uint32_t src_h, uint32_t n, const amvhip_frontend* fe, uint32_t w, uint32_t h,
+                                                            const amvhip_quant* q, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs,
+                                                            uint32_t* d_lens, uint64_t* d_sse, void* stream) {
+    return frontend_quant(c, src_fmt, d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride, src_w, src_h, n, fe,
+                          w, h, q, d_blob, blob_cap, d_offs, d_lens, ErrorSink{d_sse, true}, stream);
+}
+
+// ---- `-psnr`: the host arithmetic, and picture against picture ------------------------------------------------------------
+extern "C" double amvhip_psnr_db(uint64_t sse, uint64_t samples) { return psnr_db(sse, samples); }
+
+extern "C" void amvhip_psnr_report(const uint64_t* sse, uint32_t n, uint32_t w, uint32_t h, double out[4]) {
+    if (out && (sse || !n)) psnr_report(sse, n, w, h, out);
+}
+
+extern "C" int amvhip_picture_sse_supported(int fmt, uint32_t w, uint32_t h) { return picture_sse_ok(fmt, w, h); }
+
+namespace {
+
+// both pictures' planes as the kernel's jobs; 0: a plane is missing or a pitch is below the row
+int sse_jobs(int fmt, const PixPicture& a, const PixPicture& b, uint32_t w, uint32_t h, SseJobs* jobs) {
+    *jobs = SseJobs{};
+    for (uint32_t p = 0; p < 3; ++p) {
+        uint32_t rb, rows;
+        pix_plane_size(fmt, p, w, h, &rb, &rows);
+        if (!rows) continue;
+        if (!a.p[p] || !b.p[p] || a.stride[p] < rb || b.stride[p] < rb) return 0;
+        jobs->j[jobs->count++] = SsePlane{a.p[p], b.p[p], a.stride[p], b.stride[p], a.frame[p], b.frame[p], rb, rows, p, pix_bpp(fmt) == 3u ? 3u : 1u, 0u, 0u};
+    }
+    return 1;
+}
+
+int sse_launch(amvhip_ctx* c, const SseJobs& jobs, uint32_t n, uint64_t* d_sse, hipStream_t st) {
+    HIP_TRY(c, hipMemsetAsync(d_sse, 0, (size_t)n * 24u, st));
+    {
+        Timed t(c, AMVHIP_K_PIXFMT, st);
+        launch_picture_sse(jobs, n, d_sse, st);
+    }
+    return check_launch(c, "picture_sse");
+}
+
+}  // namespace
+
+extern "C" int amvhip_picture_sse_dev(amvhip_ctx* c, int fmt, const uint8_t* d_a0, const uint8_t* d_a1, const uint8_t* d_a2, uint32_t a_stride,
+                                      uint32_t a_c_stride, uint64_t a_frame_stride, uint64_t a_c_frame_stride, const uint8_t* d_b0,
+                                      const uint8_t* d_b1, const uint8_t* d_b2, uint32_t b_stride, uint32_t b_c_stride, uint64_t b_frame_stride,
+                                      uint64_t b_c_frame_stride, uint32_t w, uint32_t h, uint32_t n, uint64_t* d_sse, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!picture_sse_ok(fmt, w, h)) return fail(c, AMVHIP_ERR_ARG, "picture_sse: format %d at %ux%u is not taken (planar YUV, GRAY8, RGB24, BGR24)", fmt, w, h);
+    SseJobs jobs;
+    if (!sse_jobs(fmt, make_picture(d_a0, d_a1, d_a2, a_stride, a_c_stride, a_frame_stride, a_c_frame_stride),
+                  make_picture(d_b0, d_b1, d_b2, b_stride, b_c_stride, b_frame_stride, b_c_frame_stride), w, h, &jobs))
+        return fail(c, AMVHIP_ERR_ARG, "picture_sse: null plane, or a row pitch below the row");
+    if (n && (!d_sse || ((uintptr_t)d_sse & 7u))) return fail(c, AMVHIP_ERR_ARG, "picture_sse: d_sse is null or not 8-byte aligned");
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);   // (the timing records are the context's)
+    return sse_launch(c, jobs, n, d_sse, (hipStream_t)stream);
+}
+
+// host buffers: both pictures staged tight in c->h_in (a's planes, then b's, every plane 16-byte aligned), the sums in c->h_out
+extern "C" int amvhip_picture_sse(amvhip_ctx* c, int fmt, const uint8_t* a0, const uint8_t* a1, const uint8_t* a2, uint32_t a_stride,
+                                  uint32_t a_c_stride, uint64_t a_frame_stride, uint64_t a_c_frame_stride, const uint8_t* b0, const uint8_t* b1,
+                                  const uint8_t* b2, uint32_t b_stride, uint32_t b_c_stride, uint64_t b_frame_stride, uint64_t b_c_frame_stride,
+                                  uint32_t w, uint32_t h, uint32_t n, uint64_t* sse) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!picture_sse_ok(fmt, w, h)) return fail(c, AMVHIP_ERR_ARG, "picture_sse: format %d at %ux%u is not taken (planar YUV, GRAY8, RGB24, BGR24)", fmt, w, h);
+    const PixPicture host[2] = {make_picture(a0, a1, a2, a_stride, a_c_stride, a_frame_stride, a_c_frame_stride),
+                                make_picture(b0, b1, b2, b_stride, b_c_stride, b_frame_stride, b_c_frame_stride)};
+    SseJobs jobs;
+    if (!sse_jobs(fmt, host[0], host[1], w, h, &jobs)) return fail(c, AMVHIP_ERR_ARG, "picture_sse: null plane, or a row pitch below the row");
+    if (n && !sse) return fail(c, AMVHIP_ERR_ARG, "picture_sse: sse is null");
+    if (n == 0) return AMVHIP_OK;
+    uint64_t off[4] = {0, 0, 0, 0};          // of one picture's planes in a staged frame
+    for (uint32_t p = 0; p < 3; ++p) {
+        uint32_t rb, rows;
+        pix_plane_size(fmt, p, w, h, &rb, &rows);
+        off[p + 1] = off[p] + (((uint64_t)rb * rows + 15u) & ~15ull);
+    }
+    const uint64_t side = off[3] * n;
+    hipStream_t st;
+    if (int r = host_stream(c, &st)) return r;
+    std::lock_guard<std::mutex> hlk(c->hmu);
+    if (int r = ensure(c, c->h_in, 2u * side)) return r;
+    if (int r = ensure(c, c->h_out, (size_t)n * 24u)) return r;
+    for (uint32_t k = 0; k < jobs.count; ++k) {
+        SsePlane& j = jobs.j[k];
+        const uint32_t p = j.entry;
+        for (uint32_t s = 0; s < 2; ++s) {
+            uint8_t* d = (uint8_t*)c->h_in.p + s * side + off[p];
+            for (uint32_t i = 0; i < n; ++i)
+                HIP_TRY(c, hipMemcpy2DAsync(d + i * off[3], j.row_bytes, host[s].p[p] + i * host[s].frame[p], host[s].stride[p], j.row_bytes,
+                                            j.rows, hipMemcpyHostToDevice, st));
+            (s ? j.b : j.a) = d;
+            (s ? j.bstride : j.astride) = j.row_bytes;
+            (s ? j.bframe : j.aframe) = off[3];
+        }
+    }
+    {
+        std::lock_guard<std::mutex> lk(c->mu);
+        if (int r = sse_launch(c, jobs, n, (uint64_t*)c->h_out.p, st)) return r;
+    }
+    HIP_TRY(c, hipMemcpyAsync(sse, c->h_out.p, (size_t)n * 24u, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return AMVHIP_OK;
 }

@@ -693,6 +693,83 @@ int amvhip_encode_frontend_quant_stream_dev(amvhip_ctx *ctx, int src_fmt, const 
                                             uint32_t height, const amvhip_quant *q, uint8_t *d_blob, uint64_t blob_cap,
                                             uint64_t *d_offs, uint32_t *d_lens, void *stream);
 /*
+ * `ffmpeg -psnr`: what a lever did to the picture, beside what it did to the size.
+ *
+ * Host arithmetic (no context, no device):
+ *   amvhip_psnr_db      psnr() of ffmpeg.c:849-852 on sse / (samples * 255^2), in dB; INFINITY for sse == 0, NaN for
+ *                       samples == 0.  The -vstats figure of a frame (:873-877) is amvhip_psnr_db(sse[i][0], width * height).
+ *   amvhip_psnr_report  the last-report line (:953-972) over n frames whose errors are sse[n][3]: out = Y, U, V and `*`.
+ *                       The luma scale is width * height * 255^2 * n, a chroma scale a quarter of it, `*` is the summed
+ *                       errors over the summed scales.
+ *   amvhip_picture_sse_supported   1: amvhip_picture_sse_dev takes the format at that size.
+ *
+ * Picture against picture, amvhip_picture_sse_dev (asynchronous on `stream`, no workspace) and amvhip_picture_sse (host
+ * buffers, synchronous): two batches of n pictures of one format and size, each handed over flat as in
+ * amvhip_img_convert_dev (plane pointers need no alignment here).  d_sse is uint64_t [n][3], 8-byte aligned; entries a
+ * format has no use for are written as 0.  The six planar YUV formats: entry k is plane k (4:2:0 chroma (w + 1) / 2 x
+ * (h + 1) / 2, every size the decoder takes; 4:2:2 chroma (w + 1) / 2 x h); GRAY8: entry 0; RGB24 and BGR24: entry k is
+ * byte k of the pixel.  Every other format returns AMVHIP_ERR_ARG.  Only a row's own bytes count, never those between a
+ * row's end and the pitch.  This is the general tool: a source against what amvhip_decode_batch_dev or
+ * amvhip_decode_fmt_batch_dev shows for it, in either decoder's domain.
+ *
+ * The encoder's own error, in the coding call (device-pointer forms only):
+ *   amvhip_encode_quant_psnr_stream_dev           RGB24 / BGR24 source, arguments as amvhip_encode_batch_dev with the
+ *                                                 request *q (amvhip_quant, d_state on the device) in the place of qbias
+ *   amvhip_encode_yuv420_quant_psnr_stream_dev    planes as amvhip_encode_yuv420_batch_dev, then q
+ *   amvhip_encode_frontend_quant_psnr_stream_dev  amvhip_encode_frontend_quant_stream_dev with d_sse in front of stream
+ * Chunks, d_offs, d_lens and the -nr state are byte for byte those of the entry of the request without _psnr -- the plain
+ * one, _nr_stream, _trellis_batch or _nr_trellis_stream -- in both entropy modes; the state advances once per call; what
+ * those entries refuse of q is refused here (and q == NULL, a trellis other than 0 / 1, a null or misaligned d_sse).
+ * d_sse[i][p], uint64_t [n][3], 8-byte aligned, is written for every frame, a frame whose chunk did not fit the blob
+ * included: the squared error, summed over the visible samples of plane p (w x h luma, w/2 x h/2 chroma), between the
+ * picture the encoder was handed and the reconstruction of the levels it coded.  The handed picture: for RGB / BGR sources
+ * the planes of the fused rgb24_to_yuvj420p, for the front-end entry the workspace pictures, with -nr the picture before
+ * the dead zone (the reference compares new_picture, mpegvideo_enc.c:2590-2606).  The reconstruction is the FFmpeg-compat
+ * decoder's block arithmetic with the encoder's own tables in the place of Q60: v[natural] = (int16)(level[scan] *
+ * Q[scan]) with amvlib's luma / chroma tables and the standard scan the encoder writes, + 1024 on the DC, simple_idct_put
+ * (the reference encoder's idct_put) and its 0..255 clip, placed as the encoder places its blocks (bottom-up); rows and
+ * columns an edge MCU replicates beyond the picture do not count.  This is the pixel-domain form of the trellis search's
+ * own distortion model ("level * Q").
+ *   It is NOT the reference's number: the reference's MPV_decode_mb unquantises with the MPEG-1 intra rule and the MPEG
+ *   matrix, a rule that fits neither AMV decoder.
+ *   It is not amvlib's picture either: amvlib differs by its IDCT's rounding, its one scan quirk and the colour step.
+ *   amvhip_picture_sse_dev measures against amvlib's picture (or the FFmpeg-compat decoder's planes).
+ * No entropy decode, no host synchronisation, no launch per frame: the levels are made a second time by the two-stage
+ * route's front half (in AMVHIP_ENTROPY_SERIAL mode they are the ones the call packs) a round of the context's
+ * coefficient workspace at a time, and one kernel per round reconstructs and compares.
+ * For users of amvhip_prof_read: no kernel id was added.  amv_picture_sse_kernel is counted under AMVHIP_K_PIXFMT; the
+ * error kernel shares a timed span with the forward launch in front of it, so under AMVHIP_K_FDCT (which
+ * amvhip_kernel_name calls amv_forward_kernel) a _psnr call's figure is the second front half and the error kernel together.
+ */
+double amvhip_psnr_db(uint64_t sse, uint64_t samples);
+void amvhip_psnr_report(const uint64_t *sse /* [n][3] */, uint32_t n, uint32_t width, uint32_t height, double out[4]);
+int amvhip_picture_sse_supported(int fmt, uint32_t width, uint32_t height);
+int amvhip_picture_sse_dev(amvhip_ctx *ctx, int fmt, const uint8_t *d_a0, const uint8_t *d_a1, const uint8_t *d_a2,
+                           uint32_t a_stride, uint32_t a_c_stride, uint64_t a_frame_stride, uint64_t a_c_frame_stride,
+                           const uint8_t *d_b0, const uint8_t *d_b1, const uint8_t *d_b2,
+                           uint32_t b_stride, uint32_t b_c_stride, uint64_t b_frame_stride, uint64_t b_c_frame_stride,
+                           uint32_t width, uint32_t height, uint32_t n, uint64_t *d_sse, void *stream);
+int amvhip_picture_sse(amvhip_ctx *ctx, int fmt, const uint8_t *a0, const uint8_t *a1, const uint8_t *a2,
+                       uint32_t a_stride, uint32_t a_c_stride, uint64_t a_frame_stride, uint64_t a_c_frame_stride,
+                       const uint8_t *b0, const uint8_t *b1, const uint8_t *b2,
+                       uint32_t b_stride, uint32_t b_c_stride, uint64_t b_frame_stride, uint64_t b_c_frame_stride,
+                       uint32_t width, uint32_t height, uint32_t n, uint64_t *sse);
+int amvhip_encode_quant_psnr_stream_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr,
+                                        uint32_t n, uint32_t width, uint32_t height, const amvhip_quant *q,
+                                        uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens,
+                                        uint64_t *d_sse, void *stream);
+int amvhip_encode_yuv420_quant_psnr_stream_dev(amvhip_ctx *ctx, const uint8_t *d_y, const uint8_t *d_cb, const uint8_t *d_cr,
+                                               uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride,
+                                               uint64_t c_frame_stride, uint32_t n, uint32_t width, uint32_t height,
+                                               const amvhip_quant *q, uint8_t *d_blob, uint64_t blob_cap,
+                                               uint64_t *d_offs, uint32_t *d_lens, uint64_t *d_sse, void *stream);
+int amvhip_encode_frontend_quant_psnr_stream_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1,
+                                                 const uint8_t *d_src2, uint32_t src_stride, uint32_t src_c_stride,
+                                                 uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_width,
+                                                 uint32_t src_height, uint32_t n, const amvhip_frontend *fe, uint32_t width,
+                                                 uint32_t height, const amvhip_quant *q, uint8_t *d_blob, uint64_t blob_cap,
+                                                 uint64_t *d_offs, uint32_t *d_lens, uint64_t *d_sse, void *stream);
+/*
  * Decoder + back end in one call: the patched FFmpeg's amv decoder (AMVHIP_FLAG_FFMPEG, required: AMVHIP_ERR_ARG without)
  * into workspace planes, then img_convert YUVJ420P -> dst_fmt (yuvj420p_to_*, imgconvert.c:1977-1993; the planar route for
  * YUV420P; the gray route for GRAY8): what `ffmpeg -i x.amv [-pix_fmt rgb24|bgr24|rgb32|rgb565] out` hands its next stage
