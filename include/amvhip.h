@@ -496,6 +496,9 @@ int amvhip_encode_yuv422_batch(amvhip_ctx *ctx, const uint8_t *y, const uint8_t 
  * into bytes, vertical pass over four such lines, edges repeated; the luma increments and filters also serve the
  * chroma planes, which are (w >> 1) x (h >> 1).  YUV420P frames in, YUV420P frames out, plane layout as in
  * amvhip_encode_yuv420_batch_dev; at most 65535 frames per call.  Byte-identical to the reference's routine.
+ * A source from 2 x 2 on is taken.  For a source plane narrower than the four taps (source width below 4, chroma below 8)
+ * the reference's h_resample is undefined at imgresample.c:339-341 (its count of fast columns goes negative and steps
+ * the destination back), and the library repeats the edge sample, there as at every other edge.
  */
 int amvhip_resample_yuv420_dev(amvhip_ctx *ctx, const uint8_t *d_src_y, const uint8_t *d_src_cb, const uint8_t *d_src_cr,
                                uint32_t src_y_stride, uint32_t src_c_stride, uint64_t src_y_frame_stride,
@@ -589,7 +592,9 @@ int amvhip_img_convert(amvhip_ctx *ctx, int src_fmt, const uint8_t *src0, const 
  * (w >> 1) x (h >> 1) chroma samples.  Into YUV420P / YUVJ420P the last chroma column and row of the caller's planes are
  * then left as they were (undefined in the reference too); towards the RGB formats the routine reads
  * those samples, which the reference leaves undefined and which are 128 here: the picture's last column and row come out
- * without colour (GRAY8 reads no chroma; YUYV422 / UYVY422 want even sizes).
+ * without colour (GRAY8 reads no chroma; YUYV422 / UYVY422 want even sizes).  A narrow source: for a source plane narrower
+ * than the four taps (source width below 4, chroma below 8) the reference's h_resample is undefined at
+ * imgresample.c:339-341, and the library repeats the edge sample (see amvhip_resample_yuv420_dev).
  */
 int amvhip_sws_scale_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1, const uint8_t *d_src2,
                          uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,

@@ -96,7 +96,10 @@ void amvo_build_resample_filter(int16_t filter[64], int out_size, int in_size);
 /* component_resample (imgresample.c:341-405) of one plane */
 void amvo_resample_plane(const uint8_t *in, int iwrap, int iw, int ih, uint8_t *out, int owrap, int ow, int oh,
                          int h_incr, int v_incr, const int16_t *hf, const int16_t *vf);
-/* img_resample (:474-495): tight YUV420P frame iw x ih -> ow x oh (chroma planes (w >> 1) x (h >> 1)) */
+/* img_resample (:474-495): tight YUV420P frame iw x ih -> ow x oh (chroma planes (w >> 1) x (h >> 1)).
+ * For a source plane narrower than the four taps (source width below 4, chroma below 8) the reference's h_resample is
+ * undefined at imgresample.c:339-341 (n goes negative and `dst += n` steps the destination back); this routine, like the
+ * library, repeats the edge sample.  From a source width of 4 on it is the reference byte for byte. */
 void amvo_img_resample_yuv420(const uint8_t *in, int iw, int ih, uint8_t *out, int ow, int oh);
 
 /* ---- IMA ADPCM (AMV layout) ------------------------------------------------------ */
