@@ -153,6 +153,12 @@ SYMBOLS = {
     "amvhip_encode_quant_psnr_stream_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "amvhip_encode_yuv420_quant_psnr_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "amvhip_encode_frontend_quant_psnr_stream_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_qns_lambda2_max": (_u32, []),
+    "amvhip_encode_qns_lambda2": (_u32, [_u32]),
+    "amvhip_encode_qns_stream_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_yuv420_qns_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_frontend_qns_stream_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_qns_coefs_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp]),
     "amvhip_decode_fmt_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
     "amvhip_lowres_dim": (_u32, [_u32, _u32]),
     "amvhip_lowres_frame_bytes": (_u64, [_u32, _u32, _u32]),
@@ -555,6 +561,41 @@ class Context:
                                                                                  self._fe(fe), w, h, q, _ptr(blob), blob_cap, _ptr(offs),
                                                                                  _ptr(lens), _ptr(sse), stream),
                            "encode_frontend_quant_psnr_stream_dev")
+
+    # `-qns`: quantizer noise shaping behind the Quant's quantiser (qns 0 .. 3, lambda2); sse None: errors not wanted
+    def encode_qns_lambda2_max(self):
+        return self.lib.amvhip_encode_qns_lambda2_max()
+
+    def encode_qns_lambda2(self, qscale):
+        """the reference's lambda2 for a -qscale (6962 at 8); 0 where it is above encode_qns_lambda2_max()"""
+        return self.lib.amvhip_encode_qns_lambda2(qscale)
+
+    def encode_qns_stream_dev(self, pix, pix_stride, is_bgr, n, w, h, quant, qns, lambda2, blob, blob_cap, offs, lens, sse=None, stream=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        return self._check(self.lib.amvhip_encode_qns_stream_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, q, qns, lambda2, _ptr(blob),
+                                                                 blob_cap, _ptr(offs), _ptr(lens), None if sse is None else _ptr(sse), stream),
+                           "encode_qns_stream_dev")
+
+    def encode_yuv420_qns_stream_dev(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, quant, qns, lambda2, blob, blob_cap, offs,
+                                     lens, sse=None, stream=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        return self._check(self.lib.amvhip_encode_yuv420_qns_stream_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride, y_frame,
+                                                                        c_frame, n, w, h, q, qns, lambda2, _ptr(blob), blob_cap, _ptr(offs),
+                                                                        _ptr(lens), None if sse is None else _ptr(sse), stream),
+                           "encode_yuv420_qns_stream_dev")
+
+    def encode_frontend_qns_stream_dev(self, src_fmt, src, src_w, src_h, n, fe, w, h, quant, qns, lambda2, blob, blob_cap, offs, lens, sse=None,
+                                       stream=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        return self._check(self.lib.amvhip_encode_frontend_qns_stream_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n, self._fe(fe), w,
+                                                                          h, q, qns, lambda2, _ptr(blob), blob_cap, _ptr(offs), _ptr(lens),
+                                                                          None if sse is None else _ptr(sse), stream),
+                           "encode_frontend_qns_stream_dev")
+
+    def encode_qns_coefs_dev(self, pix, pix_stride, is_bgr, n, w, h, quant, qns, lambda2, coef, stream=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        return self._check(self.lib.amvhip_encode_qns_coefs_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, q, qns, lambda2, _ptr(coef),
+                                                                stream), "encode_qns_coefs_dev")
 
     def picture_sse_supported(self, fmt, w, h):
         return picture_sse_supported(fmt, w, h)

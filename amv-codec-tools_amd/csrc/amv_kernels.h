@@ -187,6 +187,11 @@ void launch_pack(const int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t 
 // and ADDED to sse [n][3] uint64 (Y, Cb, Cr of frame f at sse[3 f ..]; the caller zeroes it).  sel and items as launch_forward's.
 void launch_encode_error(const Source& in, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const int16_t* coef,
                          uint64_t* sse, hipStream_t s);
+// Quantizer noise shaping (amv_encode_qns.hip, arithmetic in amv_qns_plan.h): for the frames of `sel` whose dense lines
+// launch_forward wrote to coef, every block's levels refined in place against the source's planes.  basis_t: the basis on the
+// device, int16 [sample][scan position]; qns 1 .. 3, lambda2 <= kQnsLambda2Max.  sel and items as launch_forward's.
+void launch_qns_refine(const Source& in, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, int16_t* coef, const int16_t* basis_t,
+                       uint32_t qns, uint32_t lambda2, hipStream_t s);
 // exclusive scan of lens -> offs (single workgroup), then gather tmp -> blob.  A chunk that would end past
 // blob_cap is not copied and its lens entry becomes 0; *overflow = 1 when the total exceeds blob_cap.
 void launch_compact(const uint8_t* tmp, uint32_t bound, uint32_t* lens, uint32_t n,

@@ -16,6 +16,7 @@
 #include "amv_host_plan.h"
 #include "amv_kernels.h"
 #include "amv_nr_plan.h"
+#include "amv_qns_plan.h"
 #include "amv_trellis_plan.h"
 
 namespace amv {
@@ -54,6 +55,8 @@ struct amvhip_ctx {
     DevBuf coef, tmp, flag, enc_retry, stats, ws, ws_line, layout, ws_bytes, scaled, trellis_ws, trellis_chain, chain, split;
     // the -nr entries: the frames' sums and offsets (nr_plan of amv_nr_plan.h); the host-buffer forms' copy of the state
     DevBuf nr_ws, nr_state;
+    // the -qns entries: the basis of amv_qns_plan.h as the kernel reads it, int16 [sample][scan position], uploaded once
+    DevBuf qns_basis;
     // the shim around the rescaler: the source as YUV420P, the rescaled YUV420P ahead of a last conversion, the decoder's planes
     DevBuf pix_in, pix_out, pix_dec;
     // the video front end: the deinterlaced (and cropped) source ahead of the shim
@@ -210,10 +213,17 @@ struct ErrorSink {
 };
 constexpr ErrorSink kNoError{nullptr, false};
 int error_sink_ok(amvhip_ctx* c, uint32_t n, const ErrorSink& err);
+// what a -qns entry asks behind the request's quantiser (amv_qns_plan.h): qns 0 = nothing, today's path
+struct QnsArg {
+    uint32_t qns, lambda2;
+};
+constexpr QnsArg kNoQns{0u, 0u};
+int qns_args_ok(amvhip_ctx* c, const QnsArg& qns);
 // the tail of the scaled encoders: the w x h pictures they made as tight_420 in c->scaled, through the request's core
 // (req's state is on the device; d_sse: the frames' error, for the _psnr entry)
 int encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, uint8_t* d_blob,
-                       uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream, uint64_t* d_sse = nullptr);
+                       uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream, uint64_t* d_sse = nullptr,
+                       const QnsArg& qns = kNoQns);
 int resample_launch(amvhip_ctx* c, const PixPicture& src, uint32_t src_w, uint32_t src_h, const PixPicture& dst, uint32_t dst_w, uint32_t dst_h,
                     uint32_t n, bool to_jpeg, hipStream_t st);
 

@@ -53,6 +53,33 @@ int amv::quant_request_of(amvhip_ctx* c, const amvhip_quant* q, QuantRequest* re
     else if (q->nr) *req = NrRequest{q->nr, q->d_state};
     return AMVHIP_OK;
 }
+extern "C" uint32_t amvhip_encode_qns_lambda2_max(void) { return qns_lambda2_max(); }
+extern "C" uint32_t amvhip_encode_qns_lambda2(uint32_t qscale) { return qns_lambda2_of_qscale(qscale); }
+int amv::qns_args_ok(amvhip_ctx* c, const QnsArg& qns) {
+    if (qns.qns > kQnsMost) return fail(c, AMVHIP_ERR_ARG, "encode_qns: qns is 0 .. %u", kQnsMost);
+    if (qns.lambda2 > qns_lambda2_max())
+        return fail(c, AMVHIP_ERR_ARG, "encode_qns: lambda2 %u is more than amvhip_encode_qns_lambda2_max() = %u", qns.lambda2, qns_lambda2_max());
+    return AMVHIP_OK;
+}
+// the basis as amv_qns_refine_kernel reads it, on the device (the context is locked): made and uploaded on the first call
+static int qns_basis_on_device(amvhip_ctx* c) {
+    if (c->qns_basis.p) return AMVHIP_OK;
+    static const std::vector<int16_t> table = [] {
+        QnsBasis basis;
+        qns_build_basis(basis);
+        constexpr QnsScan scan = make_qns_scan();
+        std::vector<int16_t> t(64 * 64);
+        for (int k = 0; k < 64; ++k)
+            for (int i = 0; i < 64; ++i) t[k * 64 + i] = basis.b[scan.natural[i]][k];
+        return t;
+    }();
+    DevBuf fresh;
+    if (int r = ensure(c, fresh, table.size() * 2)) return r;
+    HIP_TRY(c, hipMemcpy(fresh.p, table.data(), table.size() * 2, hipMemcpyHostToDevice));   // (done before any stream reads it)
+    std::swap(c->qns_basis.p, fresh.p);
+    std::swap(c->qns_basis.cap, fresh.cap);
+    return AMVHIP_OK;
+}
 int amv::error_sink_ok(amvhip_ctx* c, uint32_t n, const ErrorSink& err) {
     if (err.wanted && n && (!err.sse || ((uintptr_t)err.sse & 7u))) return fail(c, AMVHIP_ERR_ARG, "encode_psnr: d_sse is null or not 8-byte aligned");
     return AMVHIP_OK;
@@ -109,20 +136,24 @@ static Quantiser frames_from(const Quantiser& quant, uint32_t base) {   // (the 
     if (const NrTrellisArg* t = std::get_if<NrTrellisArg>(&quant)) return Quantiser{NrTrellisArg{t->offsets + (uint64_t)base * 64u, t->lambda}};
     return quant;
 }
-static int encode_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, const Quantiser& quant, uint8_t* d_blob,
-                       uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse, hipStream_t stream) {
+// qns (qns.qns > 0): every frame takes the two-stage route in both entropy modes, with the refinement (amv_encode_qns.hip)
+// between amv_forward_kernel and what reads its lines -- the error kernel, where errors are wanted, and amv_pack_kernel.
+static int encode_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, const Quantiser& quant, const QnsArg& qns,
+                       uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse, hipStream_t stream) {
     const uint32_t bound = amvhip_encode_bound(g.width, g.height);
     const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
     const uint32_t round = fallback_round(n, g, 1024u, 2u);
     if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
     if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
     if (int r = ensure(c, c->flag, 16)) return r;
+    if (qns.qns)
+        if (int r = qns_basis_on_device(c)) return r;
     if (int r = ensure(c, c->enc_retry, ((size_t)n + 4) * 8)) return r;   // (the encoder's own: the decode path's counter is read by amvhip_entropy_stats)
     uint32_t* retry_count = (uint32_t*)c->enc_retry.p;
     uint32_t* retry_list = retry_count + 8;
     HIP_TRY(c, hipMemsetAsync(retry_count, 0, 32, stream));
     if (d_sse) HIP_TRY(c, hipMemsetAsync(d_sse, 0, (size_t)n * 24u, stream));
-    const bool fused = c->entropy_mode != AMVHIP_ENTROPY_SERIAL;
+    const bool fused = c->entropy_mode != AMVHIP_ENTROPY_SERIAL && !qns.qns;
     if (fused) {
         Timed t(c, AMVHIP_K_PACK, stream);
         launch_encode_frames(in, n, g, qbias, quant, book, (uint8_t*)c->tmp.p, bound, d_lens, retry_list, retry_count, stream);
@@ -134,6 +165,8 @@ static int encode_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameG
         {
             Timed t(c, AMVHIP_K_FDCT, stream);
             launch_forward(in, n, sel, items, g, qbias, quant, (int16_t*)c->coef.p, stream);
+            if (qns.qns)
+                launch_qns_refine(in, n, sel, items, g, (int16_t*)c->coef.p, (const int16_t*)c->qns_basis.p, qns.qns, qns.lambda2, stream);
             if (d_sse && !fused) launch_encode_error(in, n, sel, items, g, (const int16_t*)c->coef.p, d_sse, stream);
         }
         {
@@ -162,9 +195,8 @@ static int encode_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameG
 // Passes A and B in front of encode_core (the context is locked; nr > 0): the frames' sums, the chain from d_state to
 // d_state, and the encoder with the offsets the chain wrote -- rounding behind them, or, with a lambda, searching.  The sums
 // are taken before the offsets are applied, so the state does not depend on which.
-static int encode_nr_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, uint32_t nr, int32_t* d_state,
-                          const uint32_t* lambda, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse,
-                          hipStream_t stream) {
+static int nr_quantiser(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t nr, int32_t* d_state, const uint32_t* lambda,
+                        Quantiser* quant, hipStream_t stream) {
     const NrPlan plan = nr_plan(n);
     if (int r = ensure(c, c->nr_ws, plan.bytes)) return r;
     uint32_t* sums = (uint32_t*)((uint8_t*)c->nr_ws.p + plan.sums);
@@ -172,27 +204,34 @@ static int encode_nr_core(amvhip_ctx* c, const Source& in, uint32_t n, const Fra
     launch_nr_sums(in, n, g, sums, stream);
     launch_nr_chain(sums, n, g.blocks, nr, d_state, offsets, stream);
     if (int r = check_launch(c, "nr sums + chain")) return r;
-    return encode_core(c, in, n, g, qbias, lambda ? Quantiser{NrTrellisArg{offsets, *lambda}} : Quantiser{offsets}, d_blob, blob_cap, d_offs, d_lens,
-                       d_sse, stream);
+    *quant = lambda ? Quantiser{NrTrellisArg{offsets, *lambda}} : Quantiser{offsets};
+    return AMVHIP_OK;
 }
-
-// the request's core (the context is locked, the request checked, n > 0; req's state is on the device)
-static int encode_request(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, QuantRequest req, uint8_t* d_blob,
-                          uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse, hipStream_t stream) {
+// the request's quantiser as the kernels take it (the context is locked; for nr > 0 passes A and B run, and the state moves on)
+static int request_quantiser(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, QuantRequest req, Quantiser* quant,
+                             hipStream_t stream) {
     uint32_t lambda;
     const bool trellis = lambda_of(req, &lambda);
     NrPart q;
-    if (nr_part_of(req, &q) && q.nr)
-        return encode_nr_core(c, in, n, g, qbias, q.nr, *q.state, trellis ? &lambda : nullptr, d_blob, blob_cap, d_offs, d_lens, d_sse, stream);
-    return encode_core(c, in, n, g, qbias, trellis ? Quantiser{TrellisArg{lambda}} : Quantiser{PlainQuant{}}, d_blob, blob_cap, d_offs, d_lens, d_sse,
-                       stream);
+    if (nr_part_of(req, &q) && q.nr) return nr_quantiser(c, in, n, g, q.nr, *q.state, trellis ? &lambda : nullptr, quant, stream);
+    *quant = trellis ? Quantiser{TrellisArg{lambda}} : Quantiser{PlainQuant{}};
+    return AMVHIP_OK;
+}
+
+// the request's core (the context is locked, the request checked, n > 0; req's state is on the device)
+static int encode_request(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, QuantRequest req, const QnsArg& qns,
+                          uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse, hipStream_t stream) {
+    Quantiser quant;
+    if (int r = request_quantiser(c, in, n, g, req, &quant, stream)) return r;
+    return encode_core(c, in, n, g, qbias, quant, qns, d_blob, blob_cap, d_offs, d_lens, d_sse, stream);
 }
 
 // Every device-pointer encoder whole: the checks of the live half of `in`, of the outputs and of the request, n == 0, the
 // device, the lock (held from the workspace's allocation to the last launch), the request's core.  req's state is on the device.
 // err: where a _psnr entry wants the frames' error (kNoError: not asked for).
 static int encode_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req,
-                      uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream, const ErrorSink& err = kNoError) {
+                      uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream, const ErrorSink& err = kNoError,
+                      const QnsArg& qns = kNoQns) {
     if (!c) return AMVHIP_ERR_ARG;
     const bool no_out = n && (!d_blob || !d_offs || !d_lens);
     if (in.planar) {
@@ -205,10 +244,11 @@ static int encode_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, u
     }
     if (int r = quant_args_ok(c, n, w, h, req)) return r;
     if (int r = error_sink_ok(c, n, err)) return r;
+    if (int r = qns_args_ok(c, qns)) return r;
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
-    return encode_request(c, in, n, make_geom(w, h), qbias, req, d_blob, blob_cap, d_offs, d_lens, err.wanted ? err.sse : nullptr,
+    return encode_request(c, in, n, make_geom(w, h), qbias, req, qns, d_blob, blob_cap, d_offs, d_lens, err.wanted ? err.sse : nullptr,
                           (hipStream_t)stream);
 }
 
@@ -297,6 +337,56 @@ extern "C" int amvhip_encode_yuv420_quant_psnr_stream_dev(amvhip_ctx* c, const u
     if (int r = quant_request_of(c, q, &req)) return r;
     return encode_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, q->qbias, req, d_blob,
                       blob_cap, d_offs, d_lens, stream, ErrorSink{d_sse, true});
+}
+
+// ---- the _qns entries: the request, then qns and lambda2 (amv_qns_plan.h); d_sse NULL = errors not wanted -----------------
+extern "C" int amvhip_encode_qns_stream_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                                            const amvhip_quant* q, uint32_t qns, uint32_t lambda2, uint8_t* d_blob, uint64_t blob_cap,
+                                            uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    QuantRequest req;
+    if (int r = quant_request_of(c, q, &req)) return r;
+    return encode_dev(c, rgb_source(d_pix, pix_stride, is_bgr), n, w, h, q->qbias, req, d_blob, blob_cap, d_offs, d_lens, stream,
+                      ErrorSink{d_sse, d_sse != nullptr}, QnsArg{qns, lambda2});
+}
+
+extern "C" int amvhip_encode_yuv420_qns_stream_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr, uint32_t y_stride,
+                                                   uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
+                                                   uint32_t h, const amvhip_quant* q, uint32_t qns, uint32_t lambda2, uint8_t* d_blob,
+                                                   uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint64_t* d_sse, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    QuantRequest req;
+    if (int r = quant_request_of(c, q, &req)) return r;
+    return encode_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, q->qbias, req, d_blob,
+                      blob_cap, d_offs, d_lens, stream, ErrorSink{d_sse, d_sse != nullptr}, QnsArg{qns, lambda2});
+}
+
+// the levels themselves, beside amvhip_encode_trellis_coefs_dev: the request's quantiser, then the refinement, into d_coef
+extern "C" int amvhip_encode_qns_coefs_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                                           const amvhip_quant* q, uint32_t qns, uint32_t lambda2, int16_t* d_coef, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    QuantRequest req;
+    if (int r = quant_request_of(c, q, &req)) return r;
+    if (!encode_size_ok(w, h, q->qbias) || pix_stride < w * 3 || (n && (!d_pix || !d_coef)))
+        return fail(c, AMVHIP_ERR_ARG, "encode_qns: bad argument (width/height must be even)");
+    if ((uintptr_t)d_coef & 15u) return fail(c, AMVHIP_ERR_ARG, "encode_qns: coef must be 16-byte aligned");
+    if (int r = quant_args_ok(c, n, w, h, req)) return r;
+    if (int r = qns_args_ok(c, QnsArg{qns, lambda2})) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);       // (the -nr workspace and the basis are the context's)
+    const Source in = rgb_source(d_pix, pix_stride, is_bgr);
+    const FrameGeom g = make_geom(w, h);
+    Quantiser quant;
+    if (int r = request_quantiser(c, in, n, g, req, &quant, (hipStream_t)stream)) return r;
+    if (qns)
+        if (int r = qns_basis_on_device(c)) return r;
+    {
+        Timed t(c, AMVHIP_K_FDCT, (hipStream_t)stream);
+        launch_forward(in, n, kAllFrames, n, g, q->qbias, quant, d_coef, (hipStream_t)stream);
+        if (qns) launch_qns_refine(in, n, kAllFrames, n, g, d_coef, (const int16_t*)c->qns_basis.p, qns, lambda2, (hipStream_t)stream);
+    }
+    return check_launch(c, "forward + qns");
 }
 
 // the device-to-host half of the host-buffer encoders: offs/lens, then the chunks
@@ -487,9 +577,9 @@ extern "C" int amvhip_resample_yuv420_dev(amvhip_ctx* c, const uint8_t* d_src_y,
 }
 
 int amv::encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, uint8_t* d_blob,
-                            uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream, uint64_t* d_sse) {
-    return encode_request(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, req, d_blob, blob_cap,
-                          d_offs, d_lens, d_sse, stream);
+                            uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream, uint64_t* d_sse, const QnsArg& qns) {
+    return encode_request(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, req, qns, d_blob,
+                          blob_cap, d_offs, d_lens, d_sse, stream);
 }
 
 // rescale + encode in one call: what ffmpeg.c:757-814 does per picture (sws_scale, then avcodec_encode_video) for a

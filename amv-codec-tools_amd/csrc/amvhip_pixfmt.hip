@@ -529,7 +529,7 @@ extern "C" int amvhip_encode_frontend_batch_dev(amvhip_ctx* c, int src_fmt, cons
 static int frontend_quant(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2, uint32_t src_stride,
                           uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_w, uint32_t src_h, uint32_t n,
                           const amvhip_frontend* fe, uint32_t w, uint32_t h, const amvhip_quant* q, uint8_t* d_blob, uint64_t blob_cap,
-                          uint64_t* d_offs, uint32_t* d_lens, const ErrorSink& err, void* stream) {
+                          uint64_t* d_offs, uint32_t* d_lens, const ErrorSink& err, void* stream, const QnsArg& qns = kNoQns) {
     if (!c) return AMVHIP_ERR_ARG;
     QuantRequest req;
     if (int r = quant_request_of(c, q, &req)) return r;
@@ -537,6 +537,7 @@ static int frontend_quant(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, con
         return fail(c, AMVHIP_ERR_ARG, "encode_frontend: bad argument (width/height must be even)");
     if (int r = quant_args_ok(c, n, w, h, req)) return r;
     if (int r = error_sink_ok(c, n, err)) return r;
+    if (int r = qns_args_ok(c, qns)) return r;
     const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
     FrontPlan p;
     if (int r = frontend_args_ok(c, src_fmt, src, src_w, src_h, fe, w, h, &p)) return r;
@@ -546,7 +547,8 @@ static int frontend_quant(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, con
     std::lock_guard<std::mutex> lk(c->mu);
     if (int r = ensure(c, c->scaled, p.padded_frame_bytes * n)) return r;
     if (int r = frontend_core(c, src_fmt, src, n, fe, p, tight_420((uint8_t*)c->scaled.p, w, h), (hipStream_t)stream)) return r;
-    return encode_scaled_tail(c, n, w, h, q->qbias, req, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream, err.wanted ? err.sse : nullptr);
+    return encode_scaled_tail(c, n, w, h, q->qbias, req, d_blob, blob_cap, d_offs, d_lens, (hipStream_t)stream, err.wanted ? err.sse : nullptr,
+                              qns);
 }
 
 extern "C" int amvhip_encode_frontend_quant_stream_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1,
@@ -566,6 +568,17 @@ extern "C" int amvhip_encode_frontend_quant_psnr_stream_dev(amvhip_ctx* c, int s
                                                             uint32_t* d_lens, uint64_t* d_sse, void* stream) {
     return frontend_quant(c, src_fmt, d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride, src_w, src_h, n, fe,
                           w, h, q, d_blob, blob_cap, d_offs, d_lens, ErrorSink{d_sse, true}, stream);
+}
+
+// ... with qns, lambda2 behind the request (amv_qns_plan.h); d_sse NULL = errors not wanted
+extern "C" int amvhip_encode_frontend_qns_stream_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2,
+                                                     uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride,
+                                                     uint64_t src_c_frame_stride, uint32_t src_w, uint32_t src_h, uint32_t n,
+                                                     const amvhip_frontend* fe, uint32_t w, uint32_t h, const amvhip_quant* q, uint32_t qns,
+                                                     uint32_t lambda2, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
+                                                     uint64_t* d_sse, void* stream) {
+    return frontend_quant(c, src_fmt, d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride, src_w, src_h, n, fe,
+                          w, h, q, d_blob, blob_cap, d_offs, d_lens, ErrorSink{d_sse, d_sse != nullptr}, stream, QnsArg{qns, lambda2});
 }
 
 // ---- `-psnr`: the host arithmetic, and picture against picture ------------------------------------------------------------

@@ -775,6 +775,60 @@ int amvhip_encode_frontend_quant_psnr_stream_dev(amvhip_ctx *ctx, int src_fmt, c
                                                  uint32_t height, const amvhip_quant *q, uint8_t *d_blob, uint64_t blob_cap,
                                                  uint64_t *d_offs, uint32_t *d_lens, uint64_t *d_sse, void *stream);
 /*
+ * `ffmpeg -qns N`: quantizer noise shaping (avctx->quantizer_noise_shaping), the reference encoder's one perceptual lever,
+ * behind any of the request's quantisers (device-pointer forms only).
+ *
+ * The reference (encode_mb_internal, mpegvideo_enc.c:1637-1671) takes a visual weight per sample from the local variance of
+ * the source block (get_vissual_weight), quantises with the installed quantiser, and then refines each block's levels one
+ * +-1 change at a time (dct_quantize_refine, :3271-3645), each change the one that lowers the weighted error of the
+ * reconstruction in the pixel domain plus lambda * bits the most: error in busy texture is cheap, error in flat areas dear.
+ * The walk, its roundings and the weights are the reference's.  The reference's own ffmpeg cannot run the function for its
+ * amv encoder (it unquantises by the H.263 rule and reads a length table MJPEG does not set), so -- as for the trellis --
+ * the reconstruction is the one every AMV decoder applies, level * Q, and the rate is the length of AMV's fixed AC code
+ * itself, ZRLs and the EOB included.  Its numbers are therefore neither the reference's own nor those of amvlib's picture
+ * (amvlib differs by its IDCT's rounding, its one scan quirk and the colour step); tests/golden/ref_qns.json pins the walk
+ * to the reference's real function.
+ *   qns      0: nothing -- the bytes, state and errors of the corresponding _psnr (d_sse != NULL) or plain entry.
+ *            1: only changes that lower a level's magnitude, up to one position behind the last non-zero one.
+ *            2: changes that raise a magnitude too.  3: every position, and the gradient rule for every block.
+ *   lambda2  the reference's lambda2; amvhip_encode_qns_lambda2(qscale) = ((118 * qscale)^2 + 64) >> 7 is its value for a
+ *            -qscale (6962 at 8), 0 where that is above amvhip_encode_qns_lambda2_max(); 0 shapes the noise with no regard
+ *            for size.
+ * With qns > 0 every frame takes the two-stage route in both entropy modes (equal bytes): per round of the coefficient
+ * workspace amv_forward_kernel with the request's quantiser, amv_qns_refine_kernel, the error kernel where d_sse is given,
+ * amv_pack_kernel.  The -nr sums and state are as ever: the refinement works towards the undenoised samples, as the
+ * reference's does.  d_sse NULL: errors not wanted; otherwise as in the _psnr entries, measured on the refined levels.
+ * AMVHIP_ERR_ARG: qns > 3, lambda2 above the bound, a misaligned d_sse, whatever the entries of q refuse.  No kernel id was
+ * added: the refinement is counted under AMVHIP_K_FDCT.  There are no host-buffer forms.
+ *   amvhip_encode_qns_stream_dev            RGB24 / BGR24 source, as amvhip_encode_quant_psnr_stream_dev with qns, lambda2
+ *                                           behind q
+ *   amvhip_encode_yuv420_qns_stream_dev     planes as amvhip_encode_yuv420_quant_psnr_stream_dev
+ *   amvhip_encode_frontend_qns_stream_dev   as amvhip_encode_frontend_quant_psnr_stream_dev
+ *   amvhip_encode_qns_coefs_dev             the levels themselves, beside amvhip_encode_trellis_coefs_dev: d_coef
+ *                                           [n][blocks][64] int16, scan order, 16-byte aligned, the DC not predicted
+ */
+uint32_t amvhip_encode_qns_lambda2(uint32_t qscale);
+uint32_t amvhip_encode_qns_lambda2_max(void);
+int amvhip_encode_qns_stream_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr, uint32_t n,
+                                 uint32_t width, uint32_t height, const amvhip_quant *q, uint32_t qns, uint32_t lambda2,
+                                 uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens, uint64_t *d_sse,
+                                 void *stream);
+int amvhip_encode_yuv420_qns_stream_dev(amvhip_ctx *ctx, const uint8_t *d_y, const uint8_t *d_cb, const uint8_t *d_cr,
+                                        uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                        uint32_t n, uint32_t width, uint32_t height, const amvhip_quant *q, uint32_t qns,
+                                        uint32_t lambda2, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offs,
+                                        uint32_t *d_lens, uint64_t *d_sse, void *stream);
+int amvhip_encode_frontend_qns_stream_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1,
+                                          const uint8_t *d_src2, uint32_t src_stride, uint32_t src_c_stride,
+                                          uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_width,
+                                          uint32_t src_height, uint32_t n, const amvhip_frontend *fe, uint32_t width,
+                                          uint32_t height, const amvhip_quant *q, uint32_t qns, uint32_t lambda2,
+                                          uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens,
+                                          uint64_t *d_sse, void *stream);
+int amvhip_encode_qns_coefs_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr, uint32_t n,
+                                uint32_t width, uint32_t height, const amvhip_quant *q, uint32_t qns, uint32_t lambda2,
+                                int16_t *d_coef, void *stream);
+/*
  * Decoder + back end in one call: the patched FFmpeg's amv decoder (AMVHIP_FLAG_FFMPEG, required: AMVHIP_ERR_ARG without)
  * into workspace planes, then img_convert YUVJ420P -> dst_fmt (yuvj420p_to_*, imgconvert.c:1977-1993; the planar route for
  * YUV420P; the gray route for GRAY8): what `ffmpeg -i x.amv [-pix_fmt rgb24|bgr24|rgb32|rgb565] out` hands its next stage

@@ -15,6 +15,9 @@ line per mismatch and a summary, and exits non-zero if anything differed.
   trellis LO HI  the trellis entry on random small geometries (up to ~2 000 blocks a seed: the model is Python), channel
                  orders, quantiser biases, lambdas from 0 to the bound and content, in both entropy modes: chunks against
                  the product mode of tests/trellis_ref.py.
+  qns LO HI      the -qns entry on random small geometries (up to ~1 000 blocks a seed: the model is Python), channel orders,
+                 quantiser biases, qns 1 .. 3, lambda2 from 0 to the bound, behind the plain quantiser or the trellis, in
+                 both entropy modes: chunks against the product mode of tests/qns_ref.py.
 """
 import os
 import sys
@@ -244,14 +247,64 @@ def soak_trellis(pkg, orc, lo, hi):
     return bad
 
 
+def soak_qns(pkg, orc, lo, hi):
+    import torch
+    import pixel_builder as pb
+    import qns_ref as Q
+    import test_gpu_parity as T
+    import trellis_ref as R
+    ctx = pkg.Context(0)
+    bad = 0
+    for seed in range(lo, hi):
+        rng = np.random.default_rng(seed)
+        w, h = 2 * int(rng.integers(4, 100)), 2 * int(rng.integers(4, 70))
+        n = max(1, min(int(rng.integers(1, 6)), 1000 // (6 * ((w + 15) // 16) * ((h + 15) // 16))))
+        bgr, qbias = int(rng.integers(0, 2)), int(rng.choice([0, 128, int(rng.integers(0, 256))]))
+        qns = int(rng.integers(1, 4))
+        lambda2 = int(rng.choice([0, 6962, Q.LAMBDA2_MAX, int(rng.integers(0, Q.LAMBDA2_MAX + 1)), int(rng.integers(0, 40000))]))
+        lam = int(rng.choice([0, 3481]))             # the trellis in front of it, every second seed
+        trellis = seed & 1
+        kind = int(rng.integers(0, 3))
+        if kind == 0:
+            pix = rng.integers(0, 256, (n, h, w, 3)).astype(np.uint8)
+        elif kind == 1:
+            pix = np.stack([orc.synth_frame(SEED, 31 * seed + t, w, h) for t in range(n)])
+        else:
+            pix = np.stack([orc.synth_frame(SEED, 7 * seed + t, w, h) for t in range(n)]).astype(np.int32)
+            pix = (pix + rng.integers(-40, 41, pix.shape)).clip(0, 255).astype(np.uint8)
+        frames = [pb.to_planes(orc, pix[t], w, h, bgr) for t in range(n)]
+        base = R.encode_frames(frames, w, h, qbias, lam, want_coef=True) if trellis else R.encode_frames_plain(frames, w, h, qbias, want_coef=True)
+        want = [R.N._chunk(zz) for zz in Q.refine_lines(frames, w, h, base, qns, lambda2)]
+        cap = ctx.encode_bound(w, h) * n
+        for mode in (pkg.ENTROPY_AUTO, pkg.ENTROPY_SERIAL):
+            ctx.set_entropy_mode(mode)
+            d_blob = torch.zeros(cap, dtype=torch.uint8, device="cuda:0")
+            d_offs = torch.zeros(n, dtype=torch.int64, device="cuda:0")
+            d_lens = torch.zeros(n, dtype=torch.int32, device="cuda:0")
+            ctx.encode_qns_stream_dev(T._t(pix), w * 3, bgr, n, w, h, pkg.Quant(qbias, 0, trellis, lam, None), qns, lambda2, d_blob, cap, d_offs,
+                                      d_lens)
+            torch.cuda.synchronize()
+            blob, offs, lens = d_blob.cpu().numpy(), d_offs.cpu().numpy(), d_lens.cpu().numpy()
+            for i in range(n):
+                if int(lens[i]) != len(want[i]) or blob[int(offs[i]):int(offs[i]) + len(want[i])].tobytes() != want[i]:
+                    bad += 1
+                    print("MISMATCH qns seed", seed, w, h, n, "frame", i, "kind", kind, "qbias", qbias, "qns", qns, "lambda2", lambda2, "trellis",
+                          trellis, lam, "mode", mode, flush=True)
+                    break
+        ctx.set_entropy_mode(pkg.ENTROPY_AUTO)
+    print("the most changes a block took:", Q.most_changes())
+    return bad
+
+
 def main():
-    if len(sys.argv) != 4 or sys.argv[1] not in ("adpcm", "decode", "ffmpeg", "encode", "trellis"):
+    if len(sys.argv) != 4 or sys.argv[1] not in ("adpcm", "decode", "ffmpeg", "encode", "trellis", "qns"):
         raise SystemExit(__doc__)
     what, lo, hi = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
     pkg = entry.build()
     orc = entry.load_oracle()
     orc.lib()
-    bad = {"adpcm": soak_adpcm, "decode": soak_decode, "ffmpeg": soak_ffmpeg, "encode": soak_encode, "trellis": soak_trellis}[what](pkg, orc, lo, hi)
+    bad = {"adpcm": soak_adpcm, "decode": soak_decode, "ffmpeg": soak_ffmpeg, "encode": soak_encode, "trellis": soak_trellis,
+           "qns": soak_qns}[what](pkg, orc, lo, hi)
     print("soak", what, "seeds", lo, "..", hi - 1, "mismatches:", bad)
     sys.exit(1 if bad else 0)
 
