@@ -26,6 +26,7 @@ K_PIXFMT = 12
 PIX_COUNT = 14
 AUDIO_RATE_MIN, AUDIO_RATE_MAX = 1000, 192000
 ENTROPY_AUTO, ENTROPY_SERIAL = 0, 1
+RATE_RUNGS_MAX, RATE_OVER = 16, 0x80000000
 
 _vp, _u8p = ctypes.c_void_p, ctypes.c_void_p
 _u32, _u64, _i32, _int = ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int
@@ -159,6 +160,11 @@ SYMBOLS = {
     "amvhip_encode_yuv420_qns_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
     "amvhip_encode_frontend_qns_stream_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
     "amvhip_encode_qns_coefs_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp]),
+    "amvhip_encode_rate_probe_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "amvhip_encode_yuv420_rate_probe_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "amvhip_encode_rate_stream_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_yuv420_rate_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_frontend_rate_stream_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "amvhip_decode_fmt_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
     "amvhip_lowres_dim": (_u32, [_u32, _u32]),
     "amvhip_lowres_frame_bytes": (_u64, [_u32, _u32, _u32]),
@@ -253,6 +259,19 @@ class Quant(ctypes.Structure):
     def __init__(self, qbias=0, nr=0, trellis=0, lam=0, state=None):
         """state: int32[65] on the device (a tensor or an address), required when nr > 0; the caller keeps it alive"""
         super().__init__(int(qbias), int(nr), int(trellis), int(lam), _ptr(state))
+
+
+class Rate(ctypes.Structure):
+    """amvhip_rate of include/amvhip.h: a ladder of lambdas (host) and a byte budget per frame, uniform or uint32 [n] on the device"""
+    _fields_ = [("ladder", _vp), ("rungs", _u32), ("budget", _u32), ("d_budget", _vp)]
+
+    def __init__(self, ladder, budget=0, d_budget=None, rungs=None):
+        """ladder: a sequence of lambdas (kept alive here as a C array), or None for NULL; rungs: the count handed over where
+        it is not the ladder's own; d_budget: a tensor or an address the caller keeps alive"""
+        self._ladder = None if ladder is None else (_u32 * max(len(ladder), 1))(*[int(x) for x in ladder])
+        at = None if self._ladder is None else ctypes.addressof(self._ladder)
+        own = 0 if ladder is None else len(ladder)
+        super().__init__(at, int(own if rungs is None else rungs), int(budget), _ptr(d_budget))
 
 
 def pad_color_from_rgb(rrggbb):
@@ -596,6 +615,46 @@ class Context:
         q = None if quant is None else ctypes.addressof(quant)
         return self._check(self.lib.amvhip_encode_qns_coefs_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, q, qns, lambda2, _ptr(coef),
                                                                 stream), "encode_qns_coefs_dev")
+
+    # a byte budget per frame: the Quant (trellis 1; its lambda is not read), then a ladder of lambdas / a Rate
+    def encode_rate_probe_dev(self, pix, pix_stride, is_bgr, n, w, h, quant, ladder, bits, stream=None, rungs=None):
+        """bits uint32 [n][rungs] on the device: the bits of every frame's scan at every lambda of `ladder` (a sequence; None -> NULL)"""
+        q = None if quant is None else ctypes.addressof(quant)
+        rate = Rate(ladder, rungs=rungs)
+        return self._check(self.lib.amvhip_encode_rate_probe_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, q, rate.ladder, rate.rungs,
+                                                                 _ptr(bits), stream), "encode_rate_probe_dev")
+
+    def encode_yuv420_rate_probe_dev(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, quant, ladder, bits, stream=None,
+                                     rungs=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        rate = Rate(ladder, rungs=rungs)
+        return self._check(self.lib.amvhip_encode_yuv420_rate_probe_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride, y_frame,
+                                                                        c_frame, n, w, h, q, rate.ladder, rate.rungs, _ptr(bits), stream),
+                           "encode_yuv420_rate_probe_dev")
+
+    def encode_rate_stream_dev(self, pix, pix_stride, is_bgr, n, w, h, quant, rate, blob, blob_cap, offs, lens, rung, stream=None):
+        """every frame at the first rung of the Rate's ladder whose chunk fits its budget; rung uint32 [n] on the device says
+        which (RATE_OVER or-ed in where none did)"""
+        q = None if quant is None else ctypes.addressof(quant)
+        r = None if rate is None else ctypes.addressof(rate)
+        return self._check(self.lib.amvhip_encode_rate_stream_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, q, r, _ptr(blob), blob_cap,
+                                                                  _ptr(offs), _ptr(lens), _ptr(rung), stream), "encode_rate_stream_dev")
+
+    def encode_yuv420_rate_stream_dev(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, quant, rate, blob, blob_cap, offs, lens,
+                                      rung, stream=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        r = None if rate is None else ctypes.addressof(rate)
+        return self._check(self.lib.amvhip_encode_yuv420_rate_stream_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride, y_frame,
+                                                                         c_frame, n, w, h, q, r, _ptr(blob), blob_cap, _ptr(offs), _ptr(lens),
+                                                                         _ptr(rung), stream), "encode_yuv420_rate_stream_dev")
+
+    def encode_frontend_rate_stream_dev(self, src_fmt, src, src_w, src_h, n, fe, w, h, quant, rate, blob, blob_cap, offs, lens, rung,
+                                        stream=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        r = None if rate is None else ctypes.addressof(rate)
+        return self._check(self.lib.amvhip_encode_frontend_rate_stream_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n, self._fe(fe), w,
+                                                                           h, q, r, _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), _ptr(rung),
+                                                                           stream), "encode_frontend_rate_stream_dev")
 
     def picture_sse_supported(self, fmt, w, h):
         return picture_sse_supported(fmt, w, h)

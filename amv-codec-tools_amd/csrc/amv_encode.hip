@@ -32,7 +32,8 @@ using namespace enc;
 // offsets of the call's frames (64 uint16 per frame, amv_nr_plan.h): a frame's 128 bytes go to LDS and transform_block
 // denoises with them between the column pass and the quantiser; or one TrellisArg -- the AC outputs leave transform_block
 // un-quantised, go to the lane's line in the planes' space, and trellis_lane makes the levels there; or one NrTrellisArg --
-// both: the outputs are denoised with the offsets and trellis_lane searches on what is left.
+// both: the outputs are denoised with the offsets and trellis_lane searches on what is left; or a TrellisFrames / an
+// NrTrellisFrames -- those two with the lambda read at the frame's own index (the rate entries).
 template <bool kYuv, class... Nr>
 __global__ __launch_bounds__(kWave) void amv_forward_kernel(Source in, uint32_t n, FrameSel sel, FrameGeom g, uint32_t nseg, uint32_t per_seg,
                                                             uint32_t qbias, int16_t* __restrict__ coef, Nr... nr) {
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(kWave) void amv_forward_kernel(Source in, uint32_t 
             if (lane < nb) {
                 uint8_t* const region = reinterpret_cast<uint8_t*>(s_planes);
                 store_line(region, lane, out);
-                trellis_lane(region, lane, *s_trellis, qbias, trellis_lambda_of(nr...), nz_lo, nz_hi);
+                trellis_lane(region, lane, *s_trellis, qbias, frame_lambda_of(f, nr...), nz_lo, nz_hi);
 #pragma unroll
                 for (uint32_t i = 0; i < 8; ++i) dst[i] = load_line_granule(region, lane, i);
             }

@@ -439,11 +439,14 @@ __device__ __forceinline__ void transform_block(const int16_t* s_y, const int16_
 }
 
 // the one optional trailing argument of the encoder kernels (`class... Opt`), by Quantiser's alternative: nothing, the
-// frames' noise-reduction offsets (const uint16_t*), the trellis quantiser's lambda (TrellisArg), or both (NrTrellisArg)
+// frames' noise-reduction offsets (const uint16_t*), the trellis quantiser's lambda (TrellisArg), or both (NrTrellisArg);
+// the last two once more with a lambda per frame (TrellisFrames, NrTrellisFrames)
 template <class... Opt> struct OptKind { static constexpr bool kNr = false, kTrellis = false; };
 template <> struct OptKind<const uint16_t*> { static constexpr bool kNr = true, kTrellis = false; };
 template <> struct OptKind<TrellisArg> { static constexpr bool kNr = false, kTrellis = true; };
 template <> struct OptKind<NrTrellisArg> { static constexpr bool kNr = true, kTrellis = true; };
+template <> struct OptKind<TrellisFrames> { static constexpr bool kNr = false, kTrellis = true; };
+template <> struct OptKind<NrTrellisFrames> { static constexpr bool kNr = true, kTrellis = true; };
 __device__ __forceinline__ const uint16_t* nr_offsets_of() { return nullptr; }
 __device__ __forceinline__ const uint16_t* nr_offsets_of(const uint16_t* offs) { return offs; }
 __device__ __forceinline__ const uint16_t* nr_offsets_of(TrellisArg) { return nullptr; }
@@ -452,6 +455,13 @@ __device__ __forceinline__ uint32_t trellis_lambda_of() { return 0u; }
 __device__ __forceinline__ uint32_t trellis_lambda_of(const uint16_t*) { return 0u; }
 __device__ __forceinline__ uint32_t trellis_lambda_of(TrellisArg t) { return t.lambda; }
 __device__ __forceinline__ uint32_t trellis_lambda_of(NrTrellisArg t) { return t.lambda; }
+// ... and of frame f, for the instantiations that carry a lambda per frame (amv_forward_kernel alone); the others' is the call's
+__device__ __forceinline__ const uint16_t* nr_offsets_of(TrellisFrames) { return nullptr; }
+__device__ __forceinline__ const uint16_t* nr_offsets_of(NrTrellisFrames t) { return t.offsets; }
+template <class... Opt>
+__device__ __forceinline__ uint32_t frame_lambda_of(uint32_t, Opt... opt) { return trellis_lambda_of(opt...); }
+__device__ __forceinline__ uint32_t frame_lambda_of(uint32_t f, TrellisFrames t) { return t.lambda[f]; }
+__device__ __forceinline__ uint32_t frame_lambda_of(uint32_t f, NrTrellisFrames t) { return t.lambda[f]; }
 
 // From what a launcher was handed to the kernels' template arguments: launch(std::bool_constant<kYuv>, opt...) is called
 // once, opt... being the instantiation's trailing argument -- `kernel<decltype(yuv)::value, decltype(opt)...>` with

@@ -27,6 +27,9 @@
 // A frame whose round does not fit the bit-string window (noise: more than ~200 bits a block on average) is handed
 // back through a list; amv_forward_kernel + amv_pack_kernel (one lane per frame) take it, a round of dense
 // coefficient lines at a time.  Output is byte-identical to that route's and to the CPU oracle's (tests).
+#include <stdio.h>
+#include <stdlib.h>
+
 #include "amv_encode_common.h"
 
 namespace amv {
@@ -417,8 +420,14 @@ void launch_encode_frames(const Source& in, uint32_t n, const FrameGeom& g, uint
     if (n == 0) return;
     const SegSplit sp = seg_split(g);
     with_instantiation(in, quant, [&](auto yuv, auto... opt) {
-        hipLaunchKernelGGL((amv_encode_frame_kernel<decltype(yuv)::value, decltype(opt)...>), dim3(n), dim3(kLanes), 0, s, in, n, g, sp.nseg,
-                           sp.per_seg, qbias, d_img, tmp, bound, lens, retry_list, retry_count, opt...);
+        // a lambda per frame is the two-stage route's alone: this kernel has no such instantiation
+        if constexpr ((std::is_same_v<decltype(opt), TrellisFrames> || ...) || (std::is_same_v<decltype(opt), NrTrellisFrames> || ...)) {
+            fprintf(stderr, "launch_encode_frames: a quantiser with a lambda per frame takes launch_forward + launch_pack\n");
+            abort();
+        } else {
+            hipLaunchKernelGGL((amv_encode_frame_kernel<decltype(yuv)::value, decltype(opt)...>), dim3(n), dim3(kLanes), 0, s, in, n, g, sp.nseg,
+                               sp.per_seg, qbias, d_img, tmp, bound, lens, retry_list, retry_count, opt...);
+        }
     });
 }
 

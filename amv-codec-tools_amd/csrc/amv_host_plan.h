@@ -580,4 +580,29 @@ inline ChainPlan adpcm_chain_plan(uint32_t n, bool blocked) {
 inline ChainPlan adpcm_plain_chain_plan(uint32_t n) { return adpcm_chain_plan(n, true); }
 inline ChainPlan adpcm_trellis_chain_plan(uint32_t n) { return adpcm_chain_plan(n, false); }
 
+// ---- video encode: the rate entries' workspace (amv_rate_plan.h; amvhip_encode.hip: rate_core, probe_core) ---------------
+// For n frames of `blocks` blocks and a ladder of `rungs`: the zeroed span -- a row of 32 counters (word p, p = 1 .. rungs - 1:
+// the frames redo pass p codes again; word `rungs` takes what the last check appends, which is nothing) and the bits table
+// uint32 [n][rungs] -- then the frames' lambdas uint32 [n], the two lists that take turns uint32 [n] each, a probe's copy of the -nr
+// state, and the quantised DCs int16 [n][blocks] on their way between the probe's two launches.
+struct RatePlan {
+    uint64_t counters, bits, lambda, list[2], state, dc;   // byte offsets
+    uint64_t zero, zero_bytes;                             // the span a call zeroes
+    uint64_t bytes;                                        // the whole
+};
+inline RatePlan rate_plan(uint32_t n, uint32_t rungs, uint32_t blocks) {
+    RatePlan p;
+    p.counters = 0;
+    p.bits = 32u * 4u;
+    p.lambda = p.bits + (uint64_t)n * rungs * 4u;
+    p.list[0] = p.lambda + (uint64_t)n * 4u;
+    p.list[1] = p.list[0] + (uint64_t)n * 4u;
+    p.state = p.list[1] + (uint64_t)n * 4u;
+    p.dc = (p.state + 65u * 4u + 15u) & ~15ull;
+    p.bytes = p.dc + (uint64_t)n * blocks * 2u;
+    p.zero = p.counters;
+    p.zero_bytes = p.lambda - p.counters;
+    return p;
+}
+
 }  // namespace amv

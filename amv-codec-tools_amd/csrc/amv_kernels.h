@@ -161,7 +161,12 @@ inline Source yuv_source(const YuvSource& yuv) { return Source{nullptr, 0u, 0, y
 struct PlainQuant {};
 struct TrellisArg { uint32_t lambda; };
 struct NrTrellisArg { const uint16_t* offsets; uint32_t lambda; };
-using Quantiser = std::variant<PlainQuant, const uint16_t*, TrellisArg, NrTrellisArg>;
+// ... and the two searching ones with a lambda per frame, uint32 [n] on the device, read at the frame's own index (the rate
+// entries, amvhip_encode.hip: rate_core).  amv_forward_kernel alone has these instantiations: a call that carries one takes
+// the two-stage route for every frame, and launch_encode_frames refuses them.
+struct TrellisFrames { const uint32_t* lambda; };
+struct NrTrellisFrames { const uint16_t* offsets; const uint32_t* lambda; };
+using Quantiser = std::variant<PlainQuant, const uint16_t*, TrellisArg, NrTrellisArg, TrellisFrames, NrTrellisFrames>;
 // The whole encoder, one workgroup per frame (amv_encode_par.hip): pixels -> FF D8 + escaped scan + FF D9 in
 // tmp[i*bound..], lens[i].  Frames whose bits do not fit the kernel's LDS window are appended to retry_list /
 // *retry_count for launch_forward + launch_pack (rounds).
@@ -192,6 +197,29 @@ void launch_encode_error(const Source& in, uint32_t n, const FrameSel& sel, uint
 // device, int16 [sample][scan position]; qns 1 .. 3, lambda2 <= kQnsLambda2Max.  sel and items as launch_forward's.
 void launch_qns_refine(const Source& in, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, int16_t* coef, const int16_t* basis_t,
                        uint32_t qns, uint32_t lambda2, hipStream_t s);
+// The rate probe (amv_encode_rate.hip, arithmetic in amv_rate_plan.h): the front half once per block, the trellis walk once
+// per lambda of the ladder on the same fdct outputs, and the bits the entropy coder would write for the frame's scan at each
+// -- DC and AC codes, magnitudes, ZRLs, EOBs, before padding and escaping -- ADDED to bits uint32 [n][rungs] (the caller
+// zeroes it).  offsets: the frames' noise-reduction offsets (launch_nr_chain's) or nullptr.  dc: workspace, int16 [n][blocks]
+// (the quantised DCs on their way from the probe kernel to the launch that adds the difference codes).
+struct RateLadder {
+    uint32_t lambda[16];
+    uint32_t rungs;
+};
+void launch_rate_probe(const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, const uint16_t* offsets, const RateLadder& ladder,
+                       int16_t* dc, uint32_t* bits, hipStream_t s);
+// The choice per frame (amv_rate_plan.h: rate_first_fit over the floors of the bits table).  budgets: uint32 [n] or nullptr
+// (then `budget` for every frame).  launch_rate_choose: every frame's first floor-fit -> rung[i] (kRateOver or-ed in and the
+// frame final where none fits: the last rung then), lambda[i] = the rung's.  launch_rate_check, after the frames of
+// list[0 .. *count) (list nullptr: all n) were coded and lens holds their lengths: a frame that is not final and is over its
+// budget moves to the next floor-fit (or to the last rung, flagged and final), gets that lambda and is appended to
+// next[0 .. *next_count) -- unless it is on the last rung already, where only the flag is set.  A frame is final when
+// rung[i] carries kRateOver.
+void launch_rate_choose(const uint32_t* bits, const RateLadder& ladder, const uint32_t* budgets, uint32_t budget, uint32_t n, uint32_t* rung,
+                        uint32_t* lambda, hipStream_t s);
+void launch_rate_check(const uint32_t* bits, const RateLadder& ladder, const uint32_t* budgets, uint32_t budget, uint32_t n, const uint32_t* lens,
+                       const uint32_t* list, const uint32_t* count, uint32_t* rung, uint32_t* lambda, uint32_t* next, uint32_t* next_count,
+                       hipStream_t s);
 // exclusive scan of lens -> offs (single workgroup), then gather tmp -> blob.  A chunk that would end past
 // blob_cap is not copied and its lens entry becomes 0; *overflow = 1 when the total exceeds blob_cap.
 void launch_compact(const uint8_t* tmp, uint32_t bound, uint32_t* lens, uint32_t n,

@@ -17,6 +17,7 @@
 #include "amv_kernels.h"
 #include "amv_nr_plan.h"
 #include "amv_qns_plan.h"
+#include "amv_rate_plan.h"
 #include "amv_trellis_plan.h"
 
 namespace amv {
@@ -57,6 +58,9 @@ struct amvhip_ctx {
     DevBuf nr_ws, nr_state;
     // the -qns entries: the basis of amv_qns_plan.h as the kernel reads it, int16 [sample][scan position], uploaded once
     DevBuf qns_basis;
+    // the rate entries: the bits table, the frames' lambdas, the redo lists, a probe's copy of the -nr state, the DCs
+    // (rate_plan of amv_host_plan.h)
+    DevBuf rate_ws;
     // the shim around the rescaler: the source as YUV420P, the rescaled YUV420P ahead of a last conversion, the decoder's planes
     DevBuf pix_in, pix_out, pix_dec;
     // the video front end: the deinterlaced (and cropped) source ahead of the shim
@@ -224,6 +228,20 @@ int qns_args_ok(amvhip_ctx* c, const QnsArg& qns);
 int encode_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, uint8_t* d_blob,
                        uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, hipStream_t stream, uint64_t* d_sse = nullptr,
                        const QnsArg& qns = kNoQns);
+// What a rate entry asks behind the request (amv_rate_plan.h): the ladder as the kernels take it, the uniform budget, the
+// budgets on the device (or nullptr).  rate_request_of: q and rate checked and turned into the request (a trellis one, its
+// lambda not read) and the RateArg -- everything but the sizes and the outputs, which the entry checks as encode_dev does.
+struct RateArg {
+    RateLadder ladder;
+    uint32_t budget;
+    const uint32_t* d_budget;
+};
+int rate_request_of(amvhip_ctx* c, const amvhip_quant* q, const amvhip_rate* rate, QuantRequest* req, RateArg* arg);
+// what is left to check once the size is known to be an encoder's: the request against it, the size against the bits' 32, d_rung
+int rate_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const QuantRequest& req, const uint32_t* d_rung);
+// the tail of the front-end rate entry: the w x h pictures it made as tight_420 in c->scaled, through rate_core
+int rate_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, const RateArg& rate,
+                     uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung, hipStream_t stream);
 int resample_launch(amvhip_ctx* c, const PixPicture& src, uint32_t src_w, uint32_t src_h, const PixPicture& dst, uint32_t dst_w, uint32_t dst_h,
                     uint32_t n, bool to_jpeg, hipStream_t st);
 

@@ -134,6 +134,9 @@ static Source frames_from(const Source& in, uint32_t base, const FrameGeom& g) {
 static Quantiser frames_from(const Quantiser& quant, uint32_t base) {   // (the offsets are 64 per frame)
     if (const uint16_t* const* o = std::get_if<const uint16_t*>(&quant)) return Quantiser{*o + (uint64_t)base * 64u};
     if (const NrTrellisArg* t = std::get_if<NrTrellisArg>(&quant)) return Quantiser{NrTrellisArg{t->offsets + (uint64_t)base * 64u, t->lambda}};
+    if (const TrellisFrames* t = std::get_if<TrellisFrames>(&quant)) return Quantiser{TrellisFrames{t->lambda + base}};   // (a lambda per frame)
+    if (const NrTrellisFrames* t = std::get_if<NrTrellisFrames>(&quant))
+        return Quantiser{NrTrellisFrames{t->offsets + (uint64_t)base * 64u, t->lambda + base}};
     return quant;
 }
 // qns (qns.qns > 0): every frame takes the two-stage route in both entropy modes, with the refinement (amv_encode_qns.hip)
@@ -226,14 +229,8 @@ static int encode_request(amvhip_ctx* c, const Source& in, uint32_t n, const Fra
     return encode_core(c, in, n, g, qbias, quant, qns, d_blob, blob_cap, d_offs, d_lens, d_sse, stream);
 }
 
-// Every device-pointer encoder whole: the checks of the live half of `in`, of the outputs and of the request, n == 0, the
-// device, the lock (held from the workspace's allocation to the last launch), the request's core.  req's state is on the device.
-// err: where a _psnr entry wants the frames' error (kNoError: not asked for).
-static int encode_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req,
-                      uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream, const ErrorSink& err = kNoError,
-                      const QnsArg& qns = kNoQns) {
-    if (!c) return AMVHIP_ERR_ARG;
-    const bool no_out = n && (!d_blob || !d_offs || !d_lens);
+// what every device-pointer encoder asks of the size, of the live half of `in` and of its outputs (no_out: one of them is null)
+static int source_args_ok(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, bool no_out) {
     if (in.planar) {
         if (!encode_size_ok(w, h, qbias) || in.yuv.y_stride < w || in.yuv.c_stride < w / 2 || (n && (!in.yuv.y || !in.yuv.cb || !in.yuv.cr)) || no_out)
             return fail(c, AMVHIP_ERR_ARG, "encode_yuv: bad argument (width/height must be even)");
@@ -242,6 +239,17 @@ static int encode_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, u
             return fail(c, AMVHIP_ERR_ARG, "encode: bad argument (width/height must be even)");
         if (no_out) return fail(c, AMVHIP_ERR_ARG, "encode: null output");
     }
+    return AMVHIP_OK;
+}
+
+// Every device-pointer encoder whole: the checks of the live half of `in`, of the outputs and of the request, n == 0, the
+// device, the lock (held from the workspace's allocation to the last launch), the request's core.  req's state is on the device.
+// err: where a _psnr entry wants the frames' error (kNoError: not asked for).
+static int encode_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req,
+                      uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, void* stream, const ErrorSink& err = kNoError,
+                      const QnsArg& qns = kNoQns) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (int r = source_args_ok(c, in, n, w, h, qbias, n && (!d_blob || !d_offs || !d_lens))) return r;
     if (int r = quant_args_ok(c, n, w, h, req)) return r;
     if (int r = error_sink_ok(c, n, err)) return r;
     if (int r = qns_args_ok(c, qns)) return r;
@@ -387,6 +395,209 @@ extern "C" int amvhip_encode_qns_coefs_dev(amvhip_ctx* c, const uint8_t* d_pix, 
         if (qns) launch_qns_refine(in, n, kAllFrames, n, g, d_coef, (const int16_t*)c->qns_basis.p, qns, lambda2, (hipStream_t)stream);
     }
     return check_launch(c, "forward + qns");
+}
+
+// ---- the rate entries: a byte budget per frame, met by a search over lambda (amv_rate_plan.h, amv_encode_rate.hip) --------
+int amv::rate_request_of(amvhip_ctx* c, const amvhip_quant* q, const amvhip_rate* rate, QuantRequest* req, RateArg* arg) {
+    if (int r = quant_request_of(c, q, req)) return r;
+    if (q->trellis != 1u) return fail(c, AMVHIP_ERR_ARG, "encode_rate: the search is over the trellis quantiser's lambda: trellis must be 1");
+    *req = NrTrellisRequest{q->nr, q->d_state, 0u};            // (q->lambda is not read)
+    if (!rate || !rate->ladder) return fail(c, AMVHIP_ERR_ARG, "encode_rate: the rate request or its ladder is null");
+    if (rate->rungs == 0u || rate->rungs > kRateRungsMax) return fail(c, AMVHIP_ERR_ARG, "encode_rate: a ladder has 1 .. %u rungs", kRateRungsMax);
+    if ((uintptr_t)rate->d_budget & 3u) return fail(c, AMVHIP_ERR_ARG, "encode_rate: d_budget is not 4-byte aligned");
+    *arg = RateArg{RateLadder{}, rate->budget, rate->d_budget};
+    arg->ladder.rungs = rate->rungs;
+    for (uint32_t r = 0; r < rate->rungs; ++r) {
+        if (rate->ladder[r] > trellis_lambda_max())
+            return fail(c, AMVHIP_ERR_ARG, "encode_rate: rung %u's lambda %u is more than amvhip_encode_trellis_lambda_max() = %u", r, rate->ladder[r],
+                        trellis_lambda_max());
+        arg->ladder.lambda[r] = rate->ladder[r];
+    }
+    return AMVHIP_OK;
+}
+int amv::rate_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const QuantRequest& req, const uint32_t* d_rung) {
+    if (int r = quant_args_ok(c, n, w, h, req)) return r;
+    if (!rate_blocks_ok(make_geom(w, h).blocks))
+        return fail(c, AMVHIP_ERR_ARG, "encode_rate: a picture of more than %u blocks (a frame's bits need not fit 32)", kRateBlocksMost);
+    if ((n && !d_rung) || ((uintptr_t)d_rung & 3u)) return fail(c, AMVHIP_ERR_ARG, "encode_rate: d_rung / d_bits is null or not 4-byte aligned");
+    return AMVHIP_OK;
+}
+
+// The bits of n frames at every rung, ADDED to bits [n][rungs] (the context is locked, c->rate_ws holds `plan`): the probe's
+// two launches, as many frames at a time as a grid takes.  offsets: the frames' -nr offsets, or nullptr.
+static int rate_probe(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, const uint16_t* offsets,
+                      const RateLadder& ladder, const RatePlan& plan, uint32_t* bits, hipStream_t stream) {
+    int16_t* const dc = (int16_t*)((uint8_t*)c->rate_ws.p + plan.dc);
+    const uint64_t segs = (uint64_t)g.mcu_rows * seg_split(g).nseg;
+    const uint32_t most = (uint32_t)((1ull << 30) / segs);      // frames per launch: >= 1 (a picture has at most 2^20 MCUs)
+    Timed t(c, AMVHIP_K_FDCT, stream);
+    for (uint32_t base = 0; base < n; base += most) {
+        const uint32_t items = n - base < most ? n - base : most;
+        launch_rate_probe(frames_from(in, base, g), items, g, qbias, offsets ? offsets + (uint64_t)base * 64u : nullptr, ladder,
+                          dc + (uint64_t)base * g.blocks, bits + (uint64_t)base * ladder.rungs, stream);
+    }
+    return check_launch(c, "rate probe");
+}
+
+// amvhip_encode_*_rate_probe_dev's core (the context is locked, the request checked, n > 0).  With nr > 0 the chain runs on a
+// copy of the state in the workspace: the caller's stays as it was.
+static int probe_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, uint32_t nr, const int32_t* d_state,
+                      const RateLadder& ladder, uint32_t* d_bits, hipStream_t stream) {
+    const RatePlan plan = rate_plan(n, ladder.rungs, g.blocks);
+    if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
+    HIP_TRY(c, hipMemsetAsync(d_bits, 0, (size_t)n * ladder.rungs * 4u, stream));
+    const uint16_t* offsets = nullptr;
+    if (nr) {
+        int32_t* const copy = (int32_t*)((uint8_t*)c->rate_ws.p + plan.state);
+        HIP_TRY(c, hipMemcpyAsync(copy, d_state, kNrStateWords * 4u, hipMemcpyDeviceToDevice, stream));
+        Quantiser quant;
+        if (int r = nr_quantiser(c, in, n, g, nr, copy, nullptr, &quant, stream)) return r;
+        offsets = std::get<const uint16_t*>(quant);
+    }
+    return rate_probe(c, in, n, g, qbias, offsets, ladder, plan, d_bits, stream);
+}
+
+// amvhip_encode_*_rate_stream_dev's core (the context is locked, the request checked, n > 0).  Everything is queued on
+// `stream`, nothing is read back:
+//   with nr > 0 passes A and B once, in front (the state moves as in _nr_trellis_stream); the probe -> the bits table;
+//   the choice: every frame's first floor-fit -> d_rung, the frame's lambda;
+//   the first pass: amv_forward_kernel with the frames' lambdas + amv_pack_kernel over all frames, a round of the coefficient
+//   workspace at a time (default launches over the round's part of the source); the check: a frame over its budget moves to
+//   its next floor-fit and joins a list;
+//   up to rungs - 1 redo passes over that list (FrameSel rounds: small launches, usually with nothing to do -- the host
+//   cannot know), each with its check behind it; the compaction.
+// The one-kernel encoder takes no part: it has no instantiation with a lambda per frame, so both entropy modes run this.
+static int rate_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, uint32_t nr, int32_t* d_state,
+                     const RateArg& rate, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung,
+                     hipStream_t stream) {
+    const uint32_t bound = amvhip_encode_bound(g.width, g.height);
+    const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
+    const uint32_t round = fallback_round(n, g, 1024u, 2u);
+    const uint32_t rungs = rate.ladder.rungs;
+    const RatePlan plan = rate_plan(n, rungs, g.blocks);
+    if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
+    if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
+    if (int r = ensure(c, c->flag, 16)) return r;
+    if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
+    uint8_t* const ws = (uint8_t*)c->rate_ws.p;
+    uint32_t* const counters = (uint32_t*)(ws + plan.counters);
+    uint32_t* const bits = (uint32_t*)(ws + plan.bits);
+    uint32_t* const lambda = (uint32_t*)(ws + plan.lambda);
+    uint32_t* const lists[2] = {(uint32_t*)(ws + plan.list[0]), (uint32_t*)(ws + plan.list[1])};
+    HIP_TRY(c, hipMemsetAsync(ws + plan.zero, 0, plan.zero_bytes, stream));
+    const uint16_t* offsets = nullptr;
+    if (nr) {
+        Quantiser with_offsets;
+        if (int r = nr_quantiser(c, in, n, g, nr, d_state, nullptr, &with_offsets, stream)) return r;
+        offsets = std::get<const uint16_t*>(with_offsets);
+    }
+    if (int r = rate_probe(c, in, n, g, qbias, offsets, rate.ladder, plan, bits, stream)) return r;
+    launch_rate_choose(bits, rate.ladder, rate.d_budget, rate.budget, n, d_rung, lambda, stream);
+    const Quantiser quant = offsets ? Quantiser{NrTrellisFrames{offsets, lambda}} : Quantiser{TrellisFrames{lambda}};
+    for (uint32_t base = 0; base < n; base += round) {
+        const uint32_t items = n - base < round ? n - base : round;
+        {
+            Timed t(c, AMVHIP_K_FDCT, stream);
+            launch_forward(frames_from(in, base, g), items, kAllFrames, items, g, qbias, frames_from(quant, base), (int16_t*)c->coef.p, stream);
+        }
+        {
+            Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
+            launch_pack((const int16_t*)c->coef.p, items, kAllFrames, items, g, book, (uint8_t*)c->tmp.p + (uint64_t)base * bound, bound,
+                        d_lens + base, stream);
+        }
+        if (int r = check_launch(c, "rate: forward + pack")) return r;
+    }
+    launch_rate_check(bits, rate.ladder, rate.d_budget, rate.budget, n, d_lens, nullptr, nullptr, d_rung, lambda, lists[0], counters + 1, stream);
+    for (uint32_t pass = 1; pass < rungs; ++pass) {
+        const uint32_t* const list = lists[(pass - 1u) & 1u];
+        const uint32_t* const count = counters + pass;
+        for (uint32_t base = 0; base < n; base += round) {
+            const uint32_t items = n - base < round ? n - base : round;
+            const FrameSel sel{list, count, base, items};
+            {
+                Timed t(c, AMVHIP_K_FDCT, stream);
+                launch_forward(in, n, sel, items, g, qbias, quant, (int16_t*)c->coef.p, stream);
+            }
+            {
+                Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
+                launch_pack((const int16_t*)c->coef.p, n, sel, items, g, book, (uint8_t*)c->tmp.p, bound, d_lens, stream);
+            }
+        }
+        launch_rate_check(bits, rate.ladder, rate.d_budget, rate.budget, n, d_lens, list, count, d_rung, lambda, lists[pass & 1u],
+                          counters + pass + 1u, stream);
+        if (int r = check_launch(c, "rate: redo pass")) return r;
+    }
+    {
+        Timed t(c, AMVHIP_K_COMPACT, stream);
+        launch_compact((const uint8_t*)c->tmp.p, bound, d_lens, n, d_offs, d_blob, blob_cap, (int32_t*)c->flag.p, stream);
+    }
+    return check_launch(c, "compact");
+}
+
+static const NrTrellisRequest& rate_nr_of(const QuantRequest& req) { return std::get<NrTrellisRequest>(req); }
+
+int amv::rate_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, const RateArg& rate,
+                          uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung, hipStream_t stream) {
+    return rate_core(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, rate_nr_of(req).nr,
+                     rate_nr_of(req).state, rate, d_blob, blob_cap, d_offs, d_lens, d_rung, stream);
+}
+
+static int rate_probe_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, const amvhip_quant* q, const uint32_t* ladder,
+                          uint32_t rungs, uint32_t* d_bits, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    const amvhip_rate as_rate{ladder, rungs, 0u, nullptr};
+    QuantRequest req;
+    RateArg rate;
+    if (int r = rate_request_of(c, q, &as_rate, &req, &rate)) return r;
+    if (int r = source_args_ok(c, in, n, w, h, q->qbias, false)) return r;
+    if (int r = rate_args_ok(c, n, w, h, req, d_bits)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return probe_core(c, in, n, make_geom(w, h), q->qbias, rate_nr_of(req).nr, rate_nr_of(req).state, rate.ladder, d_bits, (hipStream_t)stream);
+}
+
+static int rate_stream_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, const amvhip_quant* q, const amvhip_rate* rate_in,
+                           uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    QuantRequest req;
+    RateArg rate;
+    if (int r = rate_request_of(c, q, rate_in, &req, &rate)) return r;
+    if (int r = source_args_ok(c, in, n, w, h, q->qbias, n && (!d_blob || !d_offs || !d_lens))) return r;
+    if (int r = rate_args_ok(c, n, w, h, req, d_rung)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return rate_core(c, in, n, make_geom(w, h), q->qbias, rate_nr_of(req).nr, rate_nr_of(req).state, rate, d_blob, blob_cap, d_offs, d_lens, d_rung,
+                     (hipStream_t)stream);
+}
+
+extern "C" int amvhip_encode_rate_probe_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
+                                            const amvhip_quant* q, const uint32_t* ladder, uint32_t rungs, uint32_t* d_bits, void* stream) {
+    return rate_probe_dev(c, rgb_source(d_pix, pix_stride, is_bgr), n, w, h, q, ladder, rungs, d_bits, stream);
+}
+
+extern "C" int amvhip_encode_yuv420_rate_probe_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr, uint32_t y_stride,
+                                                   uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride, uint32_t n, uint32_t w,
+                                                   uint32_t h, const amvhip_quant* q, const uint32_t* ladder, uint32_t rungs, uint32_t* d_bits,
+                                                   void* stream) {
+    return rate_probe_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, q, ladder, rungs,
+                          d_bits, stream);
+}
+
+extern "C" int amvhip_encode_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
+                                             uint32_t h, const amvhip_quant* q, const amvhip_rate* rate, uint8_t* d_blob, uint64_t blob_cap,
+                                             uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung, void* stream) {
+    return rate_stream_dev(c, rgb_source(d_pix, pix_stride, is_bgr), n, w, h, q, rate, d_blob, blob_cap, d_offs, d_lens, d_rung, stream);
+}
+
+extern "C" int amvhip_encode_yuv420_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr,
+                                                    uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                                    uint32_t n, uint32_t w, uint32_t h, const amvhip_quant* q, const amvhip_rate* rate,
+                                                    uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung,
+                                                    void* stream) {
+    return rate_stream_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, q, rate, d_blob,
+                           blob_cap, d_offs, d_lens, d_rung, stream);
 }
 
 // the device-to-host half of the host-buffer encoders: offs/lens, then the chunks

@@ -829,6 +829,79 @@ int amvhip_encode_qns_coefs_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t 
                                 uint32_t width, uint32_t height, const amvhip_quant *q, uint32_t qns, uint32_t lambda2,
                                 int16_t *d_coef, void *stream);
 /*
+ * A byte budget per frame, met by a search over the trellis quantiser's lambda on the device (device-pointer forms only).
+ *
+ * AMV's quantiser tables are fixed and the reference fixes the qscale of its amv encoder (mpegvideo_enc.c:492-496), so `-b`
+ * does nothing there.  Of this encoder's levers the trellis lambda is the one that can differ from frame to frame: -nr is a
+ * stream state, and its offsets do not depend on lambda, so a request with nr > 0 keeps its one nr and the search runs
+ * behind it.
+ *
+ * A ladder is a host array of `rungs` lambdas, 1 <= rungs <= AMVHIP_RATE_RUNGS_MAX, each <= amvhip_encode_trellis_lambda_max(),
+ * in the caller's order of preference (ascending is usual; duplicates and descending orders are legal).  len_r(i) is the
+ * length (d_lens: SOI, EOI, padding and FF escapes included) of the chunk the request's trellis entry -- _trellis_batch for
+ * nr == 0, _nr_trellis_stream otherwise, same stream and state -- writes for frame i at lambda = ladder[r].  The budget B(i)
+ * is d_budget[i] (uint32 [n] on the device) when d_budget is not NULL, `budget` otherwise.  The chosen rung r(i) is the FIRST
+ * r, in ladder order, with len_r(i) <= B(i); if none fits it is the last rung and AMVHIP_RATE_OVER is set in d_rung[i].
+ * (Sizes are not monotone in lambda, so the definition says "first" and nothing bisects.)  The chunk written for frame i is
+ * byte for byte that entry's chunk at ladder[r(i)], in both entropy modes; d_offs, d_lens and the blob-capacity rule are the
+ * plain entries'.  With nr > 0 the state advances once per call: n frames in one call equal the same frames in any number
+ * of calls with the state carried, the rungs included.
+ *
+ * How: one front half per block and the trellis walk per rung on the same fdct outputs give, without packing a byte, the
+ * bits of the frame's scan at every rung; 4 + ceil(bits / 8) is a floor of the chunk's length (escapes come on top), so a
+ * frame starts at its first rung whose floor fits, is coded (amv_forward_kernel with the frame's own lambda, amv_pack_kernel:
+ * the two-stage route for every frame, as with qns), and moves on to its next floor-fit only where escapes pushed it over
+ * -- up to rungs - 1 small launches that usually find nothing.  No host synchronisation.
+ *
+ *   amvhip_encode_rate_probe_dev, amvhip_encode_yuv420_rate_probe_dev
+ *       the arguments of amvhip_encode_quant_psnr_stream_dev / amvhip_encode_yuv420_quant_psnr_stream_dev up to q, then the
+ *       ladder and d_bits, uint32 [n][rungs], 4-byte aligned: d_bits[i][r] = the bits the entropy coder writes for frame i's
+ *       scan at ladder[r] (DC codes and magnitudes, AC run/size codes, magnitudes, ZRLs, EOBs; before padding and escaping).
+ *       No chunk is written, q->d_state is read and never written: R(lambda) per frame, for a caller who allocates a total
+ *       over the frames themselves and hands the result back as d_budget.
+ *   amvhip_encode_rate_stream_dev (RGB24 / BGR24), amvhip_encode_yuv420_rate_stream_dev, amvhip_encode_frontend_rate_stream_dev
+ *       the _quant_psnr_stream_dev entries with `rate` behind q and d_rung, uint32 [n], 4-byte aligned, in the place of
+ *       d_sse: d_rung[i] = r(i), AMVHIP_RATE_OVER or-ed in where no rung fit.  It is written for every frame, a frame whose
+ *       chunk did not fit the blob included.
+ * In q, trellis must be 1 and lambda is not read; qbias, nr and d_state mean what they mean everywhere.  AMVHIP_ERR_ARG, with
+ * nothing queued and the state untouched: rate or ladder NULL, rungs 0 or above the maximum, a lambda above the bound,
+ * q->trellis != 1, a NULL or misaligned d_rung or d_bits, a misaligned d_budget, whatever the trellis entries refuse of q,
+ * and a picture of more than 349 525 MCUs (beyond it a frame's bits need not fit 32).  Not here: qns or d_sse in a rate call,
+ * 4:2:2 sources, host-buffer forms, the plain quantiser as a rung, a carry of unused bytes from frame to frame.  No kernel
+ * id was added: the probe is counted under AMVHIP_K_FDCT.
+ */
+#define AMVHIP_RATE_RUNGS_MAX 16
+#define AMVHIP_RATE_OVER 0x80000000u          /* in d_rung[i]: no rung met the budget; the chunk is the last rung's */
+typedef struct amvhip_rate {
+    const uint32_t *ladder;     /* host, `rungs` lambdas */
+    uint32_t rungs;
+    uint32_t budget;            /* bytes per chunk, read when d_budget is NULL */
+    const uint32_t *d_budget;   /* device, uint32[n], or NULL */
+} amvhip_rate;
+int amvhip_encode_rate_probe_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr, uint32_t n,
+                                 uint32_t width, uint32_t height, const amvhip_quant *q, const uint32_t *ladder, uint32_t rungs,
+                                 uint32_t *d_bits, void *stream);
+int amvhip_encode_yuv420_rate_probe_dev(amvhip_ctx *ctx, const uint8_t *d_y, const uint8_t *d_cb, const uint8_t *d_cr,
+                                        uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                        uint32_t n, uint32_t width, uint32_t height, const amvhip_quant *q,
+                                        const uint32_t *ladder, uint32_t rungs, uint32_t *d_bits, void *stream);
+int amvhip_encode_rate_stream_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr, uint32_t n,
+                                  uint32_t width, uint32_t height, const amvhip_quant *q, const amvhip_rate *rate,
+                                  uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens, uint32_t *d_rung,
+                                  void *stream);
+int amvhip_encode_yuv420_rate_stream_dev(amvhip_ctx *ctx, const uint8_t *d_y, const uint8_t *d_cb, const uint8_t *d_cr,
+                                         uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                         uint32_t n, uint32_t width, uint32_t height, const amvhip_quant *q,
+                                         const amvhip_rate *rate, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offs,
+                                         uint32_t *d_lens, uint32_t *d_rung, void *stream);
+int amvhip_encode_frontend_rate_stream_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1,
+                                           const uint8_t *d_src2, uint32_t src_stride, uint32_t src_c_stride,
+                                           uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_width,
+                                           uint32_t src_height, uint32_t n, const amvhip_frontend *fe, uint32_t width,
+                                           uint32_t height, const amvhip_quant *q, const amvhip_rate *rate, uint8_t *d_blob,
+                                           uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens, uint32_t *d_rung,
+                                           void *stream);
+/*
  * Decoder + back end in one call: the patched FFmpeg's amv decoder (AMVHIP_FLAG_FFMPEG, required: AMVHIP_ERR_ARG without)
  * into workspace planes, then img_convert YUVJ420P -> dst_fmt (yuvj420p_to_*, imgconvert.c:1977-1993; the planar route for
  * YUV420P; the gray route for GRAY8): what `ffmpeg -i x.amv [-pix_fmt rgb24|bgr24|rgb32|rgb565] out` hands its next stage

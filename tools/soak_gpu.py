@@ -18,6 +18,11 @@ line per mismatch and a summary, and exits non-zero if anything differed.
   qns LO HI      the -qns entry on random small geometries (up to ~1 000 blocks a seed: the model is Python), channel orders,
                  quantiser biases, qns 1 .. 3, lambda2 from 0 to the bound, behind the plain quantiser or the trellis, in
                  both entropy modes: chunks against the product mode of tests/qns_ref.py.
+  rate LO HI     the rate entries on random small geometries (up to ~600 blocks a seed and ladders of 1 .. 6 rungs in any
+                 order, duplicates included: the model is Python), quantiser biases, every third seed behind -nr from a seeded
+                 state, budgets drawn per frame around the model's own lengths and floors (so that frames land on every rung,
+                 take redo passes and run over), uniform every fourth seed, in both entropy modes: d_bits of the probe,
+                 chunks, d_rung and the state against tests/rate_ref.py.
 """
 import os
 import sys
@@ -296,15 +301,85 @@ def soak_qns(pkg, orc, lo, hi):
     return bad
 
 
+def soak_rate(pkg, orc, lo, hi):
+    import torch
+    import rate_ref as R
+    import test_gpu_parity as T
+    ctx = pkg.Context(0)
+    bad = frames_seen = redone = over = 0
+    for seed in range(lo, hi):
+        rng = np.random.default_rng(seed)
+        w, h = 2 * int(rng.integers(4, 60)), 2 * int(rng.integers(4, 50))
+        blocks = 6 * ((w + 15) // 16) * ((h + 15) // 16)
+        n = max(1, min(int(rng.integers(1, 7)), 600 // blocks))
+        qbias = int(rng.choice([0, 128, int(rng.integers(0, 256))]))
+        rungs = int(rng.integers(1, 7))
+        pool = [0, 400, 3481, 20000, R.T.LAMBDA_MAX, int(rng.integers(0, R.T.LAMBDA_MAX + 1)), int(rng.integers(0, 30000))]
+        ladder = [int(rng.choice(pool)) for _ in range(rungs)]
+        if seed & 1:
+            ladder.sort()
+        nr = int(rng.integers(1, ctx.encode_nr_max(w, h) + 1)) if seed % 3 == 0 else 0
+        state = None
+        if nr:
+            count = int(rng.integers(1, 65000))
+            state = np.concatenate([rng.integers(0, 200, 64) * count, [count]]).astype(np.int64)
+        frames = R.N.stream(w, h, [R.KINDS[int(rng.integers(0, 4))] for _ in range(n)], 1000 + seed)
+        bits = R.bits_table(frames, w, h, qbias, nr, state, ladder)
+        lens = R.lens_table(frames, w, h, qbias, nr, state, ladder)
+        B = []
+        for i in range(n):
+            r = int(rng.integers(0, rungs))
+            B.append(max(0, int(rng.choice([lens[i][r], lens[i][r] - 1, R.floor_bytes(int(bits[i][r])), R.floor_bytes(int(bits[i][r])) - 1, 7,
+                                            0xFFFFFFFF, int(rng.integers(0, int(lens[i].max()) + 2))]))))
+        uniform = seed % 4 == 3
+        if uniform:
+            B = [B[0]] * n
+        want, want_rungs, want_state = R.encode(frames, w, h, qbias, nr, state, ladder, B)
+        frames_seen += n
+        redone += sum(R.device_walk(bits[i], lens[i], B[i])[2] > 1 for i in range(n))
+        over += sum(1 for r in want_rungs if r & R.OVER)
+        n_pad = 8
+        Y = np.full((n, h, w + n_pad), 0xEE, np.uint8)
+        Cb, Cr = np.full((n, h // 2, w // 2 + n_pad), 0xEE, np.uint8), np.full((n, h // 2, w // 2 + n_pad), 0xEE, np.uint8)
+        for i, (y, cb, cr) in enumerate(frames):
+            Y[i, :, :w], Cb[i, :, :w // 2], Cr[i, :, :w // 2] = y, cb, cr
+        planes = (T._t(Y), T._t(Cb), T._t(Cr), w + n_pad, w // 2 + n_pad, h * (w + n_pad), (h // 2) * (w // 2 + n_pad), n, w, h)
+        cap = ctx.encode_bound(w, h) * n
+        for mode in (pkg.ENTROPY_AUTO, pkg.ENTROPY_SERIAL):
+            ctx.set_entropy_mode(mode)
+            d_state = None if state is None else T._t(state.astype(np.int32))
+            d_bits = torch.zeros((n, rungs), dtype=torch.int32, device="cuda:0")
+            ctx.encode_yuv420_rate_probe_dev(*planes, pkg.Quant(qbias, nr, 1, 0, d_state), ladder, d_bits)
+            d_blob = torch.zeros(cap, dtype=torch.uint8, device="cuda:0")
+            d_offs = torch.zeros(n, dtype=torch.int64, device="cuda:0")
+            d_lens = torch.zeros(n, dtype=torch.int32, device="cuda:0")
+            d_rung = torch.zeros(n, dtype=torch.int32, device="cuda:0")
+            d_budget = None if uniform else T._t(np.array(B, np.uint32))
+            ctx.encode_yuv420_rate_stream_dev(*planes, pkg.Quant(qbias, nr, 1, 0, d_state), pkg.Rate(ladder, budget=B[0], d_budget=d_budget),
+                                              d_blob, cap, d_offs, d_lens, d_rung)
+            torch.cuda.synchronize()
+            blob, offs, got_lens = d_blob.cpu().numpy(), d_offs.cpu().numpy(), d_lens.cpu().numpy()
+            ok = (d_bits.cpu().numpy().view(np.uint32) == bits).all() and d_rung.cpu().numpy().view(np.uint32).tolist() == want_rungs
+            ok = ok and (state is None or (d_state.cpu().numpy() == want_state).all())
+            ok = ok and all(int(got_lens[i]) == len(want[i]) and blob[int(offs[i]):int(offs[i]) + len(want[i])].tobytes() == want[i] for i in range(n))
+            if not ok:
+                bad += 1
+                print("MISMATCH rate seed", seed, w, h, n, "qbias", qbias, "nr", nr, "ladder", ladder, "budgets", B, "uniform", uniform, "mode", mode,
+                      flush=True)
+        ctx.set_entropy_mode(pkg.ENTROPY_AUTO)
+    print("frames", frames_seen, "coded more than once", redone, "over every rung", over)
+    return bad
+
+
 def main():
-    if len(sys.argv) != 4 or sys.argv[1] not in ("adpcm", "decode", "ffmpeg", "encode", "trellis", "qns"):
+    if len(sys.argv) != 4 or sys.argv[1] not in ("adpcm", "decode", "ffmpeg", "encode", "trellis", "qns", "rate"):
         raise SystemExit(__doc__)
     what, lo, hi = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
     pkg = entry.build()
     orc = entry.load_oracle()
     orc.lib()
     bad = {"adpcm": soak_adpcm, "decode": soak_decode, "ffmpeg": soak_ffmpeg, "encode": soak_encode, "trellis": soak_trellis,
-           "qns": soak_qns}[what](pkg, orc, lo, hi)
+           "qns": soak_qns, "rate": soak_rate}[what](pkg, orc, lo, hi)
     print("soak", what, "seeds", lo, "..", hi - 1, "mismatches:", bad)
     sys.exit(1 if bad else 0)
 
