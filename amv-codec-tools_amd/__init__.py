@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("AMVHIP_LIB") or os.path.join(_HERE, "libamvhip.so")  
 
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_SPACE = 0, -1, -2, -3, -4
 ST_FORMAT, ST_OVERRUN, ST_TRUNCATED = 1, 2, 4
+ST_RANGE = 8            # requant: a block outside the range the search is proved for
 FLAG_ZIGZAG_FIXED = 1
 FLAG_FFMPEG = 2
 FLAG_FFMPEG_KEEP = 4
@@ -165,6 +166,9 @@ SYMBOLS = {
     "amvhip_encode_rate_stream_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "amvhip_encode_yuv420_rate_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
     "amvhip_encode_frontend_rate_stream_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "amvhip_requant_stream_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "amvhip_requant_rate_probe_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp]),
+    "amvhip_requant_rate_stream_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "amvhip_decode_fmt_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
     "amvhip_lowres_dim": (_u32, [_u32, _u32]),
     "amvhip_lowres_frame_bytes": (_u64, [_u32, _u32, _u32]),
@@ -647,6 +651,24 @@ class Context:
         return self._check(self.lib.amvhip_encode_yuv420_rate_stream_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride, y_frame,
                                                                          c_frame, n, w, h, q, r, _ptr(blob), blob_cap, _ptr(offs), _ptr(lens),
                                                                          _ptr(rung), stream), "encode_yuv420_rate_stream_dev")
+
+    # chunks requantised in the coefficient domain: the decode entries' inputs up to h, then lambda / a ladder / a Rate
+    def requant_stream_dev(self, blob, blob_bytes, offs, lens, n, w, h, lam, out, out_cap, out_offs, out_lens, status, err=None, stream=None):
+        """the AC levels of every clean, in-range chunk searched at lam; err: None or uint64 [n][3] on the device"""
+        return self._check(self.lib.amvhip_requant_stream_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, lam, _ptr(out),
+                                                              out_cap, _ptr(out_offs), _ptr(out_lens), _ptr(status), _ptr(err), stream),
+                           "requant_stream_dev")
+
+    def requant_rate_probe_dev(self, blob, blob_bytes, offs, lens, n, w, h, ladder, bits, stream=None, rungs=None):
+        rate = Rate(ladder, rungs=rungs)
+        return self._check(self.lib.amvhip_requant_rate_probe_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, rate.ladder,
+                                                                  rate.rungs, _ptr(bits), stream), "requant_rate_probe_dev")
+
+    def requant_rate_stream_dev(self, blob, blob_bytes, offs, lens, n, w, h, rate, out, out_cap, out_offs, out_lens, status, rung, stream=None):
+        r = None if rate is None else ctypes.addressof(rate)
+        return self._check(self.lib.amvhip_requant_rate_stream_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, r, _ptr(out),
+                                                                   out_cap, _ptr(out_offs), _ptr(out_lens), _ptr(status), _ptr(rung), stream),
+                           "requant_rate_stream_dev")
 
     def encode_frontend_rate_stream_dev(self, src_fmt, src, src_w, src_h, n, fe, w, h, quant, rate, blob, blob_cap, offs, lens, rung,
                                         stream=None):

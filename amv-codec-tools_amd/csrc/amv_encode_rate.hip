@@ -97,9 +97,13 @@ void launch_rate_probe(const Source& in, uint32_t n, const FrameGeom& g, uint32_
             hipLaunchKernelGGL((amv_rate_probe_kernel<decltype(yuv)::value, false>), dim3((uint32_t)grid), dim3(kWave), 0, s, in, n, g, sp.nseg,
                                sp.per_seg, qbias, offsets, ladder, dc, bits);
     });
-    const uint32_t chunks = (g.blocks + kRateDcLanes - 1u) / kRateDcLanes;
-    hipLaunchKernelGGL(amv_rate_dc_kernel, dim3((uint32_t)((uint64_t)n * chunks)), dim3(kRateDcLanes), 0, s, dc, n, g.blocks, chunks, ladder.rungs,
-                       bits);
+    launch_rate_dc(dc, n, g.blocks, ladder.rungs, bits, s);
+}
+
+void launch_rate_dc(const int16_t* dc, uint32_t n, uint32_t blocks, uint32_t rungs, uint32_t* bits, hipStream_t s) {
+    if (n == 0) return;
+    const uint32_t chunks = (blocks + kRateDcLanes - 1u) / kRateDcLanes;
+    hipLaunchKernelGGL(amv_rate_dc_kernel, dim3((uint32_t)((uint64_t)n * chunks)), dim3(kRateDcLanes), 0, s, dc, n, blocks, chunks, rungs, bits);
 }
 
 // ---- the choice -----------------------------------------------------------------------------------------------------------

@@ -220,6 +220,30 @@ void launch_rate_choose(const uint32_t* bits, const RateLadder& ladder, const ui
 void launch_rate_check(const uint32_t* bits, const RateLadder& ladder, const uint32_t* budgets, uint32_t budget, uint32_t n, const uint32_t* lens,
                        const uint32_t* list, const uint32_t* count, uint32_t* rung, uint32_t* lambda, uint32_t* next, uint32_t* next_count,
                        hipStream_t s);
+// ... its second launch alone (a caller whose probe kernel is its own: amv_requant.hip)
+void launch_rate_dc(const int16_t* dc, uint32_t n, uint32_t blocks, uint32_t rungs, uint32_t* bits, hipStream_t s);
+// Chunks requantised in the coefficient domain (amv_requant.hip, arithmetic in amv_requant_plan.h).  coef: a round of dense
+// lines of levels as the entropy stage's kernels leave them (slot p - base of item p; sel and items as launch_forward's).
+// src: the entropy stage's status and nmcu_ok (whole MCUs) of the call's frames, and, in the pass over the frames in records
+// form, their rec_count -- a frame whose count is ~0 is not in the round (nullptr: every frame of sel is).  launch_requant: a
+// frame that is coded gets its AC levels searched at lambdas[f] (lambdas nullptr: `lambda`), in place, and its planes' error
+// ADDED to err [n][3] (nullptr: not wanted; the caller zeroes it); every other frame of sel, and every block out of range,
+// lines of zeros; flags[f] (zeroed by the caller) != 0 afterwards: the frame has a block out of range.
+// launch_requant_probe: the bits of the AC codes at every rung ADDED to bits [n][rungs], the DCs to dc [n][blocks] for
+// launch_rate_dc.  launch_requant_finish: d_status takes the range flag (and AMVHIP_ST_TRUNCATED where a decode stopped early
+// without saying why); a frame that is not coded gets lens 0, err 0, bits 0 and rung (rungs - 1) | kRateOver -- each where
+// the pointer is not null.
+struct RequantSource {
+    const int32_t* status;
+    const uint32_t* nmcu_ok;
+    const uint32_t* rec_count;
+};
+void launch_requant(int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const RequantSource& src, uint32_t lambda,
+                    const uint32_t* lambdas, uint32_t* flags, uint64_t* err, hipStream_t s);
+void launch_requant_probe(const int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const RequantSource& src,
+                          const RateLadder& ladder, uint32_t* flags, int16_t* dc, uint32_t* bits, hipStream_t s);
+void launch_requant_finish(uint32_t n, const FrameGeom& g, int32_t* status, const uint32_t* nmcu_ok, const uint32_t* flags, uint32_t* lens,
+                           uint64_t* err, uint32_t* rung, uint32_t* bits, uint32_t rungs, hipStream_t s);
 // exclusive scan of lens -> offs (single workgroup), then gather tmp -> blob.  A chunk that would end past
 // blob_cap is not copied and its lens entry becomes 0; *overflow = 1 when the total exceeds blob_cap.
 void launch_compact(const uint8_t* tmp, uint32_t bound, uint32_t* lens, uint32_t n,

@@ -18,6 +18,7 @@
 #include "amv_nr_plan.h"
 #include "amv_qns_plan.h"
 #include "amv_rate_plan.h"
+#include "amv_requant_plan.h"
 #include "amv_trellis_plan.h"
 
 namespace amv {
@@ -61,6 +62,8 @@ struct amvhip_ctx {
     // the rate entries: the bits table, the frames' lambdas, the redo lists, a probe's copy of the -nr state, the DCs
     // (rate_plan of amv_host_plan.h)
     DevBuf rate_ws;
+    // the requant entries: a flag per frame (a block out of range); the probe entry's statuses, which it does not hand out
+    DevBuf requant_flags, requant_status;
     // the shim around the rescaler: the source as YUV420P, the rescaled YUV420P ahead of a last conversion, the decoder's planes
     DevBuf pix_in, pix_out, pix_dec;
     // the video front end: the deinterlaced (and cropped) source ahead of the shim
@@ -180,6 +183,20 @@ inline YuvSource yuv_source_of(const PixPicture& p) {
 // ---- amvhip_decode.hip (the caller holds c->mu) ------------------------------------------------------------------------
 int decode_args_ok(amvhip_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n, uint32_t w,
                    uint32_t h, uint32_t flags, const uint8_t* d_out, const int32_t* d_status);
+// Frames the synchronising kernel does not decode go through amv_huffman_kernel, whose output is dense coefficient
+// lines: all of them in AMVHIP_ENTROPY_SERIAL mode (and for pictures of >= 16384 blocks), else the few it hands back
+// (oversize chunks, long FF runs, more records than the record space holds).  `items` bounds the work; with a list the
+// real count sits on the device.
+struct Fallback {
+    const uint32_t* list;
+    const uint32_t* count;
+    uint32_t items;
+};
+// The entropy stage of a decode call into the hand-over set b (the decode entries' and the requant entries' front): records
+// in `sinks`, statuses and nmcu_ok to d_status / d_nmcu_ok, fb = what is left for the serial kernel.
+int entropy_records(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n,
+                    const FrameGeom& g, bool ok_in_blocks, int32_t* d_status, uint32_t* d_nmcu_ok, DecodeSet& b, hipStream_t st, SyncSinks& sinks,
+                    Fallback& fb);
 int decode_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
                 uint32_t n, uint32_t w, uint32_t h, uint32_t flags, uint8_t* d_out, int32_t* d_status, DecodeSet& b,
                 hipStream_t front, hipStream_t back, uint32_t lowres = 0);   // lowres 1..3: the reduced planes (flags = AMVHIP_FLAG_FFMPEG)

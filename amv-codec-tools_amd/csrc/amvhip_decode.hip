@@ -4,16 +4,6 @@
 
 using namespace amv;
 
-// Frames the synchronising kernel does not decode go through amv_huffman_kernel, whose output is dense coefficient
-// lines: all of them in AMVHIP_ENTROPY_SERIAL mode (and for pictures of >= 16384 blocks), else the few it hands back
-// (oversize chunks, long FF runs, more records than the record space holds).  `items` bounds the work; with a list the
-// real count sits on the device.
-struct Fallback {
-    const uint32_t* list;
-    const uint32_t* count;
-    uint32_t items;
-};
-
 // unstuffing + the synchronising kernel into the records of `sinks`; fb says what is left for the serial kernel
 // lanes: lanes per frame of the synchronising kernel; heavy_lanes != 0 (a batch that gets ONE lane per frame):
 // frames whose chunk is over twice the batch's mean get that many lanes instead -- a wave's 64 frames finish together, and one
@@ -141,9 +131,9 @@ int amv::decode_args_ok(amvhip_ctx* c, const uint8_t* d_blob, const uint64_t* d_
 // The entropy stage of a decode call into the hand-over set b: sizes the record space, the segment bounds, the lane table
 // and the record counts, then runs entropy_front.  Statuses and nmcu_ok go to d_status / d_nmcu_ok (ok_in_blocks: nmcu_ok
 // counts whole blocks, AMVHIP_FLAG_FFMPEG_KEEP).  sinks: where the records are; its coef is left null.
-static int entropy_records(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
-                           uint32_t n, const FrameGeom& g, bool ok_in_blocks, int32_t* d_status, uint32_t* d_nmcu_ok, DecodeSet& b,
-                           hipStream_t st, SyncSinks& sinks, Fallback& fb) {
+int amv::entropy_records(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
+                         uint32_t n, const FrameGeom& g, bool ok_in_blocks, int32_t* d_status, uint32_t* d_nmcu_ok, DecodeSet& b,
+                         hipStream_t st, SyncSinks& sinks, Fallback& fb) {
     const EntropyPlan p = entropy_plan(n, blob_bytes, g);   // the record space and the unstuffed scans' window (amv_host_plan.h)
     const uint32_t lanes = (uint32_t)huffman_sync_lanes(n, c->cus, c->sync_lanes, (uint64_t)g.width * g.height);
     // a batch that gets one lane per frame gives its heavy frames kHeavyLanes (entropy_front); AMVHIP_SPLIT=0: every frame one

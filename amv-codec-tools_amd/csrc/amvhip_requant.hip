@@ -1,0 +1,267 @@
+// amvhip_requant.hip -- AMV chunks requantised in the coefficient domain behind the C ABI: chunks in, chunks out, no pixel in
+// between.  The decoder's entropy stage (amvhip_decode.hip: entropy_records, amv_huffman_kernel) in front, amv_requant.hip in
+// the place of the encoder's front half, the encoder's coder, choice and compaction behind it.
+#include "amvhip_ctx.h"
+
+using namespace amv;
+
+namespace {
+
+// what the three entries ask of their inputs and shared outputs: the decode entries' words, the encoder entries' for the outputs
+// (has_status false: the probe entry, which hands out no statuses)
+int requant_args_ok(amvhip_ctx* c, const uint8_t* d_blob, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h,
+                    const int32_t* d_status, bool has_status = true) {
+    if (!size_ok(w, h)) return fail(c, AMVHIP_ERR_ARG, "requant: bad size %ux%u", w, h);
+    if (n && (!d_blob || !d_offs || !d_lens || (has_status && !d_status))) return fail(c, AMVHIP_ERR_ARG, "requant: null argument");
+    if (((uintptr_t)d_blob & 3u) || ((uintptr_t)d_status & 3u) || ((uintptr_t)d_lens & 3u) || ((uintptr_t)d_offs & 7u))
+        return fail(c, AMVHIP_ERR_ARG, "requant: blob, lens and status must be 4-byte aligned, offs 8-byte");
+    return AMVHIP_OK;
+}
+int requant_outputs_ok(amvhip_ctx* c, uint32_t n, const uint8_t* d_out, const uint64_t* d_out_offs, const uint32_t* d_out_lens) {
+    if (n && (!d_out || !d_out_offs || !d_out_lens)) return fail(c, AMVHIP_ERR_ARG, "requant: null output");
+    if (((uintptr_t)d_out_offs & 7u) || ((uintptr_t)d_out_lens & 3u)) return fail(c, AMVHIP_ERR_ARG, "requant: out_offs must be 8-byte, out_lens 4-byte aligned");
+    return AMVHIP_OK;
+}
+int requant_lambda_ok(amvhip_ctx* c, uint32_t lambda) {
+    if (lambda > trellis_lambda_max())
+        return fail(c, AMVHIP_ERR_ARG, "requant: lambda %u is more than amvhip_encode_trellis_lambda_max() = %u", lambda, trellis_lambda_max());
+    return AMVHIP_OK;
+}
+int requant_ladder_of(amvhip_ctx* c, const uint32_t* ladder, uint32_t rungs, RateLadder* out) {
+    if (!ladder) return fail(c, AMVHIP_ERR_ARG, "requant_rate: the rate request or its ladder is null");
+    if (rungs == 0u || rungs > kRateRungsMax) return fail(c, AMVHIP_ERR_ARG, "requant_rate: a ladder has 1 .. %u rungs", kRateRungsMax);
+    *out = RateLadder{};
+    out->rungs = rungs;
+    for (uint32_t r = 0; r < rungs; ++r) {
+        if (ladder[r] > trellis_lambda_max())
+            return fail(c, AMVHIP_ERR_ARG, "requant_rate: rung %u's lambda %u is more than amvhip_encode_trellis_lambda_max() = %u", r, ladder[r],
+                        trellis_lambda_max());
+        out->lambda[r] = ladder[r];
+    }
+    return AMVHIP_OK;
+}
+int requant_rate_size_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const uint32_t* d_words) {
+    if (!rate_blocks_ok(make_geom(w, h).blocks))
+        return fail(c, AMVHIP_ERR_ARG, "requant_rate: a picture of more than %u blocks (a frame's bits need not fit 32)", kRateBlocksMost);
+    if ((n && !d_words) || ((uintptr_t)d_words & 3u)) return fail(c, AMVHIP_ERR_ARG, "requant_rate: d_rung / d_bits is null or not 4-byte aligned");
+    return AMVHIP_OK;
+}
+
+// A call's chunks, where the entropy stage left their levels, and the round of dense lines they pass through
+struct Front {
+    const uint8_t* blob;
+    uint64_t blob_bytes;
+    const uint64_t* offs;
+    const uint32_t* lens;
+    uint32_t n;
+    FrameGeom g;
+    int32_t* status;
+    uint32_t* nmcu;
+    uint32_t* flags;
+    SyncSinks sinks;
+    Fallback fb;
+    uint32_t round;
+    int16_t* coef;
+};
+
+// The entropy stage of a call and its workspace (the context is locked).  A round is a multiple of a wave's 64 frames unless
+// it is the whole batch: amv_huffman_kernel's last wave of a round takes whole waves of items.
+int front_of(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n,
+             const FrameGeom& g, int32_t* d_status, hipStream_t st, Front* f) {
+    uint32_t round = fallback_round(n, g, 1024u, 2u);
+    if (round < n) round = round >= 128u ? round & ~63u : 64u;
+    if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
+    if (int r = ensure(c, c->set[0].nmcu, (size_t)n * 4)) return r;
+    if (int r = ensure(c, c->requant_flags, (size_t)n * 4)) return r;
+    *f = Front{d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, (uint32_t*)c->set[0].nmcu.p, (uint32_t*)c->requant_flags.p, SyncSinks{},
+               Fallback{}, round, (int16_t*)c->coef.p};
+    HIP_TRY(c, hipMemsetAsync(f->flags, 0, (size_t)n * 4, st));
+    return entropy_records(c, d_blob, blob_bytes, d_offs, d_lens, n, g, false, d_status, f->nmcu, c->set[0], st, f->sinks, f->fb);
+}
+
+// The serial kernel's lines of the items base .. base + items of (list, count) -- without a list: of the frames themselves --
+// into the round
+int serial_round(amvhip_ctx* c, const Front& f, const uint32_t* list, const uint32_t* count, uint32_t base, uint32_t items, hipStream_t st) {
+    Timed t(c, AMVHIP_K_HUFFMAN_SERIAL, st);
+    launch_huffman(f.blob, f.blob_bytes, f.offs, f.lens, f.n, f.g, (const HuffDecodeImage*)c->d_dec.p, f.coef, f.status, f.nmcu, list, count, base,
+                   items, true, false, st);
+    return check_launch(c, "requant: huffman");
+}
+
+// Every frame of the call once, a round of dense lines at a time: the frames in records form first (expanded a round of
+// frames at a time: the sinks' per-frame arrays from `base` on -- a frame's records are found through them, and slot p of the
+// round is frame base + p), then what the serial kernel decodes (with a list the count is on the device: rounds past it find
+// nothing to do).  body(sel, items, src): the round's lines are in place.
+template <class Body>
+int each_round(amvhip_ctx* c, const Front& f, hipStream_t st, Body&& body) {
+    const FrameGeom& g = f.g;
+    if (f.fb.list) {
+        const uint32_t segs = segs_per_row(g) * g.mcu_rows;
+        for (uint32_t base = 0; base < f.n; base += f.round) {
+            const uint32_t items = f.n - base < f.round ? f.n - base : f.round;
+            SyncSinks part = f.sinks;
+            part.rec_line += base;
+            part.seg_start += (uint64_t)base * (segs + 1u) * 2u;
+            part.lane_tab += (uint64_t)base * part.lanes * 4u;
+            part.rec_count += base;
+            launch_expand_records(part, f.nmcu + base, items, g, f.coef, st);
+            if (int r = check_launch(c, "requant: expand_records")) return r;
+            if (int r = body(FrameSel{nullptr, nullptr, base, items}, items, RequantSource{f.status, f.nmcu, f.sinks.rec_count})) return r;
+        }
+    }
+    for (uint32_t base = 0; base < f.fb.items; base += f.round) {
+        const uint32_t items = f.fb.items - base < f.round ? f.fb.items - base : f.round;
+        if (int r = serial_round(c, f, f.fb.list, f.fb.count, base, items, st)) return r;
+        if (int r = body(FrameSel{f.fb.list, f.fb.count, base, items}, items, RequantSource{f.status, f.nmcu, nullptr})) return r;
+    }
+    return AMVHIP_OK;
+}
+
+// requant + pack of one round whose lines are in place
+int code_round(amvhip_ctx* c, const Front& f, const FrameSel& sel, uint32_t items, const RequantSource& src, uint32_t lambda,
+               const uint32_t* lambdas, uint64_t* d_err, uint32_t bound, uint32_t* d_lens, hipStream_t st) {
+    {
+        Timed t(c, AMVHIP_K_FDCT, st);
+        launch_requant(f.coef, f.n, sel, items, f.g, src, lambda, lambdas, f.flags, d_err, st);
+    }
+    {
+        Timed t(c, AMVHIP_K_PACK_SERIAL, st);
+        launch_pack(f.coef, f.n, sel, items, f.g, (const HuffEncodeImage*)c->d_enc.p, (uint8_t*)c->tmp.p, bound, d_lens, st);
+    }
+    return check_launch(c, "requant: search + pack");
+}
+
+int compact(amvhip_ctx* c, uint32_t n, uint32_t bound, uint32_t* d_lens, uint64_t* d_offs, uint8_t* d_out, uint64_t out_cap, hipStream_t st) {
+    Timed t(c, AMVHIP_K_COMPACT, st);
+    launch_compact((const uint8_t*)c->tmp.p, bound, d_lens, n, d_offs, d_out, out_cap, (int32_t*)c->flag.p, st);
+    return check_launch(c, "requant: compact");
+}
+
+// The bits of every frame at every rung into bits [n][rungs] (zeroed by the caller); rate_ws holds `plan`
+int probe_pass(amvhip_ctx* c, const Front& f, const RateLadder& ladder, const RatePlan& plan, uint32_t* bits, hipStream_t st) {
+    int16_t* const dc = (int16_t*)((uint8_t*)c->rate_ws.p + plan.dc);
+    if (int r = each_round(c, f, st, [&](const FrameSel& sel, uint32_t items, const RequantSource& src) {
+            Timed t(c, AMVHIP_K_FDCT, st);
+            launch_requant_probe(f.coef, f.n, sel, items, f.g, src, ladder, f.flags, dc, bits, st);
+            return check_launch(c, "requant: probe");
+        }))
+        return r;
+    Timed t(c, AMVHIP_K_FDCT, st);
+    launch_rate_dc(dc, f.n, f.g.blocks, ladder.rungs, bits, st);
+    return check_launch(c, "requant: probe (dc)");
+}
+
+}  // namespace
+
+extern "C" int amvhip_requant_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
+                                         uint32_t n, uint32_t w, uint32_t h, uint32_t lambda, uint8_t* d_out, uint64_t out_cap,
+                                         uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status, uint64_t* d_err, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (int r = requant_args_ok(c, d_blob, d_offs, d_lens, n, w, h, d_status)) return r;
+    if (int r = requant_outputs_ok(c, n, d_out, d_out_offs, d_out_lens)) return r;
+    if ((uintptr_t)d_err & 7u) return fail(c, AMVHIP_ERR_ARG, "requant: d_err is not 8-byte aligned");
+    if (int r = requant_lambda_ok(c, lambda)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t st = (hipStream_t)stream;
+    const FrameGeom g = make_geom(w, h);
+    const uint32_t bound = amvhip_encode_bound(w, h);
+    if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
+    if (int r = ensure(c, c->flag, 16)) return r;
+    Front f;
+    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, &f)) return r;
+    if (d_err) HIP_TRY(c, hipMemsetAsync(d_err, 0, (size_t)n * 24u, st));
+    if (int r = each_round(c, f, st, [&](const FrameSel& sel, uint32_t items, const RequantSource& src) {
+            return code_round(c, f, sel, items, src, lambda, nullptr, d_err, bound, d_out_lens, st);
+        }))
+        return r;
+    launch_requant_finish(n, g, d_status, f.nmcu, f.flags, d_out_lens, d_err, nullptr, nullptr, 0u, st);
+    if (int r = check_launch(c, "requant: finish")) return r;
+    return compact(c, n, bound, d_out_lens, d_out_offs, d_out, out_cap, st);
+}
+
+extern "C" int amvhip_requant_rate_probe_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                             const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const uint32_t* ladder, uint32_t rungs,
+                                             uint32_t* d_bits, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    RateLadder lad;
+    if (int r = requant_ladder_of(c, ladder, rungs, &lad)) return r;
+    if (int r = requant_args_ok(c, d_blob, d_offs, d_lens, n, w, h, nullptr, false)) return r;
+    if (int r = requant_rate_size_ok(c, n, w, h, d_bits)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t st = (hipStream_t)stream;
+    const FrameGeom g = make_geom(w, h);
+    const RatePlan plan = rate_plan(n, rungs, g.blocks);
+    if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
+    if (int r = ensure(c, c->requant_status, (size_t)n * 4)) return r;    // the entry hands out no statuses: a zero row says `not coded`
+    int32_t* const d_status = (int32_t*)c->requant_status.p;
+    Front f;
+    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, &f)) return r;
+    HIP_TRY(c, hipMemsetAsync(d_bits, 0, (size_t)n * rungs * 4u, st));
+    if (int r = probe_pass(c, f, lad, plan, d_bits, st)) return r;
+    launch_requant_finish(n, g, d_status, f.nmcu, f.flags, nullptr, nullptr, nullptr, d_bits, rungs, st);
+    return check_launch(c, "requant: finish");
+}
+
+// amv_encode_rate.hip's flow (amvhip_encode.hip: rate_core) with the chunks' levels as the source: the probe over every frame,
+// the choice, a first pass at the frames' lambdas, the check, and up to rungs - 1 redo passes over device-built lists.  A redo
+// pass takes its frames' lines from the serial kernel, whichever kernel decoded them first: it decodes any frame of the call
+// into any slot, and a list names few.
+extern "C" int amvhip_requant_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                              const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_rate* rate, uint8_t* d_out,
+                                              uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status, uint32_t* d_rung,
+                                              void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!rate) return fail(c, AMVHIP_ERR_ARG, "requant_rate: the rate request or its ladder is null");
+    RateLadder lad;
+    if (int r = requant_ladder_of(c, rate->ladder, rate->rungs, &lad)) return r;
+    if ((uintptr_t)rate->d_budget & 3u) return fail(c, AMVHIP_ERR_ARG, "requant_rate: d_budget is not 4-byte aligned");
+    if (int r = requant_args_ok(c, d_blob, d_offs, d_lens, n, w, h, d_status)) return r;
+    if (int r = requant_outputs_ok(c, n, d_out, d_out_offs, d_out_lens)) return r;
+    if (int r = requant_rate_size_ok(c, n, w, h, d_rung)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t st = (hipStream_t)stream;
+    const FrameGeom g = make_geom(w, h);
+    const uint32_t bound = amvhip_encode_bound(w, h), rungs = lad.rungs;
+    const RatePlan plan = rate_plan(n, rungs, g.blocks);
+    if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
+    if (int r = ensure(c, c->flag, 16)) return r;
+    if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
+    uint8_t* const ws = (uint8_t*)c->rate_ws.p;
+    uint32_t* const counters = (uint32_t*)(ws + plan.counters);
+    uint32_t* const bits = (uint32_t*)(ws + plan.bits);
+    uint32_t* const lambda = (uint32_t*)(ws + plan.lambda);
+    uint32_t* const lists[2] = {(uint32_t*)(ws + plan.list[0]), (uint32_t*)(ws + plan.list[1])};
+    Front f;
+    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, &f)) return r;
+    HIP_TRY(c, hipMemsetAsync(ws + plan.zero, 0, plan.zero_bytes, st));
+    if (int r = probe_pass(c, f, lad, plan, bits, st)) return r;
+    launch_rate_choose(bits, lad, rate->d_budget, rate->budget, n, d_rung, lambda, st);
+    if (int r = each_round(c, f, st, [&](const FrameSel& sel, uint32_t items, const RequantSource& src) {
+            return code_round(c, f, sel, items, src, 0u, lambda, nullptr, bound, d_out_lens, st);
+        }))
+        return r;
+    launch_rate_check(bits, lad, rate->d_budget, rate->budget, n, d_out_lens, nullptr, nullptr, d_rung, lambda, lists[0], counters + 1, st);
+    for (uint32_t pass = 1; pass < rungs; ++pass) {
+        const uint32_t* const list = lists[(pass - 1u) & 1u];
+        const uint32_t* const count = counters + pass;
+        for (uint32_t base = 0; base < n; base += f.round) {
+            const uint32_t items = n - base < f.round ? n - base : f.round;
+            if (int r = serial_round(c, f, list, count, base, items, st)) return r;
+            if (int r = code_round(c, f, FrameSel{list, count, base, items}, items, RequantSource{f.status, f.nmcu, nullptr}, 0u, lambda, nullptr,
+                                   bound, d_out_lens, st))
+                return r;
+        }
+        launch_rate_check(bits, lad, rate->d_budget, rate->budget, n, d_out_lens, list, count, d_rung, lambda, lists[pass & 1u], counters + pass + 1u,
+                          st);
+        if (int r = check_launch(c, "requant_rate: redo pass")) return r;
+    }
+    launch_requant_finish(n, g, d_status, f.nmcu, f.flags, d_out_lens, nullptr, d_rung, nullptr, rungs, st);
+    if (int r = check_launch(c, "requant: finish")) return r;
+    return compact(c, n, bound, d_out_lens, d_out_offs, d_out, out_cap, st);
+}

@@ -902,6 +902,59 @@ int amvhip_encode_frontend_rate_stream_dev(amvhip_ctx *ctx, int src_fmt, const u
                                            uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens, uint32_t *d_rung,
                                            void *stream);
 /*
+ * AMV chunks requantised in the coefficient domain, at one lambda or under a byte budget per frame (device-pointer forms
+ * only): chunks in, chunks out, and no pixel in between.
+ *
+ * AMV's quantiser tables are fixed, so a chunk's levels already are the coefficients the trellis quantiser searches on,
+ * level * Q.  The rule (csrc/amv_requant_plan.h), per frame whose entropy decode is clean, over its 6 * nmcu lines of levels
+ * in scan order as amvhip_huffman_decode_dev hands them out:
+ *   1. the DC level is carried unchanged;
+ *   2. the AC levels are searched as amvhip_encode_trellis_batch_dev searches fdct outputs, on c = level * 8 Q, with the
+ *      caller's lambda and the rounding term one half (the levels are rounded already: there is no qbias here).  A coded
+ *      position's first candidate is the chunk's own level; lambda = 0 returns the levels unchanged;
+ *   3. the lines are coded by the entropy coder of every encoder entry: SOI, the escaped scan, padding, EOI.  lambda = 0 is the
+ *      canonical re-coding of the chunk (a chunk this library's encoders wrote comes back byte for byte).
+ * A frame is coded only if its entropy decode reports nothing, reaches the last MCU, and every block is in range:
+ * |level| * 8 Q <= 8681 per AC coefficient, the sum of (level * 8 Q)^2 over a block's AC coefficients <= 2^30, |DC level| <=
+ * 1023 (every chunk an encoder of 8-bit samples writes with AMV's tables is inside; beyond, the search's int scores could wrap
+ * or the DC difference would have no code).  Otherwise d_status[i] is not zero -- the decode's AMVHIP_ST_* bits, or
+ * AMVHIP_ST_RANGE -- d_out_lens[i] is 0 and nothing is written for the frame: the caller keeps its own chunk.
+ *
+ * The input arguments are amvhip_decode_batch_dev's up to height (any width and height that entry takes: there are no pixels
+ * here and no evenness rule); chunks are written back to back into d_out as the encoder entries write them (d_out_offs,
+ * d_out_lens; a chunk that would end past out_cap is not written and its length is 0).  Asynchronous on `stream`, no host
+ * synchronisation, no launch per frame; both entropy modes give the same bytes.
+ *
+ *   amvhip_requant_stream_dev       the rule at `lambda` (<= amvhip_encode_trellis_lambda_max()).  d_err: NULL, or uint64 [n][3],
+ *       8-byte aligned: entry p of frame i = the sum of ((new - old) * Q)^2 over the AC positions of the blocks of plane p (Y:
+ *       blocks 0-3 of an MCU, Cb: block 4, Cr: block 5) -- by Parseval the unclipped pixel error between the two decodes.
+ *       Written for every frame, 0 for a frame that is not coded.
+ *   amvhip_requant_rate_probe_dev   d_bits [n][rungs] as amvhip_encode_rate_probe_dev's: the bits of the frame's scan at
+ *       ladder[r], before padding and escapes.  The row of a frame that is not coded is 0.  No chunk is written.
+ *   amvhip_requant_rate_stream_dev  the rate entries' definition above word for word, with amvhip_requant_stream_dev in the
+ *       place of the trellis entry: the first rung in ladder order whose chunk fits B(i), that rung's chunk byte for byte as
+ *       amvhip_requant_stream_dev writes it at that lambda, AMVHIP_RATE_OVER with the last rung where none fits.  A frame that
+ *       is not coded gets AMVHIP_RATE_OVER | (rungs - 1): d_status tells the two cases apart.  A ladder whose first rung is 0
+ *       leaves a frame that already fits as it is (re-coded canonically).
+ * AMVHIP_ERR_ARG with nothing queued: null or misaligned pointers (d_blob, d_lens, d_status, d_out_lens, d_rung, d_bits,
+ * d_budget: 4 bytes; d_offs, d_out_offs, d_err: 8), a lambda above the bound, rate or ladder NULL, rungs 0 or above
+ * AMVHIP_RATE_RUNGS_MAX, and for the two rate entries a picture of more than 349 525 MCUs.  n == 0 succeeds and queues nothing.
+ * Not here: -nr and -qns behind a coefficient source, host-buffer forms, writing the frames that are not coded through to
+ * d_out.  No kernel id was added: the search is counted under AMVHIP_K_FDCT, as the probe is.
+ */
+#define AMVHIP_ST_RANGE 8u     /* requant: a block's levels are outside the range the search is proved for */
+int amvhip_requant_stream_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_offs,
+                              const uint32_t *d_lens, uint32_t n, uint32_t width, uint32_t height, uint32_t lambda,
+                              uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offs, uint32_t *d_out_lens, int32_t *d_status,
+                              uint64_t *d_err, void *stream);
+int amvhip_requant_rate_probe_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_offs,
+                                  const uint32_t *d_lens, uint32_t n, uint32_t width, uint32_t height, const uint32_t *ladder,
+                                  uint32_t rungs, uint32_t *d_bits, void *stream);
+int amvhip_requant_rate_stream_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_offs,
+                                   const uint32_t *d_lens, uint32_t n, uint32_t width, uint32_t height, const amvhip_rate *rate,
+                                   uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offs, uint32_t *d_out_lens,
+                                   int32_t *d_status, uint32_t *d_rung, void *stream);
+/*
  * Decoder + back end in one call: the patched FFmpeg's amv decoder (AMVHIP_FLAG_FFMPEG, required: AMVHIP_ERR_ARG without)
  * into workspace planes, then img_convert YUVJ420P -> dst_fmt (yuvj420p_to_*, imgconvert.c:1977-1993; the planar route for
  * YUV420P; the gray route for GRAY8): what `ffmpeg -i x.amv [-pix_fmt rgb24|bgr24|rgb32|rgb565] out` hands its next stage

@@ -23,6 +23,11 @@ line per mismatch and a summary, and exits non-zero if anything differed.
                  state, budgets drawn per frame around the model's own lengths and floors (so that frames land on every rung,
                  take redo passes and run over), uniform every fourth seed, in both entropy modes: d_bits of the probe,
                  chunks, d_rung and the state against tests/rate_ref.py.
+  requant LO HI  the requant entries on seeded chunks of random small geometries, odd sizes included (up to ~600 blocks a seed:
+                 the model is Python): the oracle's synthetic frames and crafted blocks at the edges of the range rule, a third
+                 of the chunks damaged -- a flipped byte, a cut, junk behind the scan -- one lambda from 0 to the bound and a
+                 ladder of 1 .. 6 rungs in any order with budgets drawn per frame around the model's own lengths, in both
+                 entropy modes: chunks, offsets, d_status, d_err, d_bits and d_rung against tests/requant_ref.py.
 """
 import os
 import sys
@@ -371,15 +376,96 @@ def soak_rate(pkg, orc, lo, hi):
     return bad
 
 
+def soak_requant(pkg, orc, lo, hi):
+    import torch
+    import requant_ref as Q
+    import test_gpu_parity as T
+    ctx = pkg.Context(0)
+    bad = frames_seen = not_coded = out_of_range = 0
+    for seed in range(lo, hi):
+        rng = np.random.default_rng(seed)
+        w, h = int(rng.integers(1, 120)), int(rng.integers(1, 100))
+        blocks = Q.nblocks(w, h)
+        n = max(1, min(int(rng.integers(1, 9)), 600 // blocks))
+        chunks = Q.synth_chunks(w + (w & 1), h + (h & 1), n, seed=SEED + seed, qbias=int(rng.choice([0, 128])))
+        for i in range(n):
+            kind = int(rng.integers(0, 9))
+            c = bytearray(chunks[i])
+            if kind == 0 and len(c) > 8:                                    # a flipped byte inside the scan
+                c[int(rng.integers(2, len(c) - 2))] ^= 1 << int(rng.integers(0, 8))
+            elif kind == 1:                                                 # cut
+                c = c[: int(rng.integers(2, len(c)))]
+            elif kind == 2:                                                 # junk behind the scan
+                c = c[:-2] + bytes(rng.integers(0, 255, 3, dtype=np.uint8)) + b"\xff\xd9"
+            elif kind == 3:                                                 # a block at an edge of the range rule, in or out
+                zz = Q.decode(chunks[i], w, h)[0].copy()
+                b = int(rng.integers(0, blocks))
+                k = int(rng.integers(1, 64))
+                edge = Q.COEF_MOST // (8 * int(Q.T.QUANT[Q.comp_of(b)][k])) + int(rng.integers(0, 2))
+                zz[b, k] = edge if rng.integers(0, 2) else -edge
+                if rng.integers(0, 2) and Q.comp_of(b) == 0:
+                    zz[b] = Q.block_of({**Q.AT_ENERGY_MOST, 59: 15 + int(rng.integers(0, 2))}, dc=int(zz[b, 0]))
+                c = Q.N._chunk(zz)
+            chunks[i] = bytes(c)
+        lam = int(rng.choice([0, 200, 3481, 20000, Q.LAMBDA_MAX, int(rng.integers(0, Q.LAMBDA_MAX + 1))]))
+        rungs = int(rng.integers(1, 7))
+        ladder = [int(rng.choice([0, 1000, 3481, 20000, Q.LAMBDA_MAX, int(rng.integers(0, 60000))])) for _ in range(rungs)]
+        if seed & 1:
+            ladder.sort()
+        want, status, err = Q.requant(chunks, w, h, lam)
+        bits = Q.bits_table(chunks, w, h, ladder)
+        sizes = [[len(c) if c else 0 for c in Q.requant(chunks, w, h, x)[0]] for x in ladder]
+        B = [max(0, int(rng.choice([sizes[int(rng.integers(0, rungs))][i], sizes[int(rng.integers(0, rungs))][i] - 1, 7, 0xFFFFFFFF])))
+             for i in range(n)]
+        want_rate, _, want_rungs = Q.rate(chunks, w, h, ladder, B)
+        frames_seen += n
+        not_coded += sum(1 for x in status if x)
+        out_of_range += sum(1 for x in status if x == Q.ST_RANGE)
+        blob, offs, lens = Q.pack(chunks)
+        ins = (T._t(blob), int(lens.sum()), T._t(offs), T._t(lens), n, w, h)
+        cap = sum(len(c) for c in chunks) + 64
+
+        def same(d_blob, d_offs, d_lens, chunks_want):
+            got, o, ln = d_blob.cpu().numpy(), d_offs.cpu().numpy(), d_lens.cpu().numpy()
+            pos = 0
+            for i, c in enumerate(chunks_want):
+                size = len(c) if c else 0
+                if (int(o[i]), int(ln[i])) != (pos, size) or (size and got[pos: pos + size].tobytes() != c):
+                    return False
+                pos += size
+            return True
+
+        for mode in (pkg.ENTROPY_AUTO, pkg.ENTROPY_SERIAL):
+            ctx.set_entropy_mode(mode)
+            outs = [(torch.zeros(cap, dtype=torch.uint8, device="cuda:0"), torch.zeros(n, dtype=torch.int64, device="cuda:0"),
+                     torch.zeros(n, dtype=torch.int32, device="cuda:0"), torch.full((n,), -1, dtype=torch.int32, device="cuda:0")) for _ in range(2)]
+            d_err = torch.full((n, 3), -1, dtype=torch.int64, device="cuda:0")
+            d_bits = torch.full((n, rungs), -1, dtype=torch.int32, device="cuda:0")
+            d_rung = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
+            ctx.requant_stream_dev(*ins, lam, outs[0][0], cap, *outs[0][1:], d_err)
+            ctx.requant_rate_probe_dev(*ins, ladder, d_bits)
+            ctx.requant_rate_stream_dev(*ins, pkg.Rate(ladder, budget=1, d_budget=T._t(np.array(B, np.uint32))), outs[1][0], cap, *outs[1][1:], d_rung)
+            torch.cuda.synchronize()
+            ok = same(*outs[0][:3], want) and same(*outs[1][:3], want_rate) and d_err.cpu().numpy().tolist() == err
+            ok = ok and outs[0][3].cpu().numpy().tolist() == status and outs[1][3].cpu().numpy().tolist() == status
+            ok = ok and (d_bits.cpu().numpy().view(np.uint32) == bits).all() and d_rung.cpu().numpy().view(np.uint32).tolist() == want_rungs
+            if not ok:
+                bad += 1
+                print("MISMATCH requant seed", seed, w, h, n, "lambda", lam, "ladder", ladder, "budgets", B, "status", status, "mode", mode, flush=True)
+        ctx.set_entropy_mode(pkg.ENTROPY_AUTO)
+    print("frames", frames_seen, "not coded", not_coded, "of them out of range", out_of_range)
+    return bad
+
+
 def main():
-    if len(sys.argv) != 4 or sys.argv[1] not in ("adpcm", "decode", "ffmpeg", "encode", "trellis", "qns", "rate"):
+    if len(sys.argv) != 4 or sys.argv[1] not in ("adpcm", "decode", "ffmpeg", "encode", "trellis", "qns", "rate", "requant"):
         raise SystemExit(__doc__)
     what, lo, hi = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
     pkg = entry.build()
     orc = entry.load_oracle()
     orc.lib()
     bad = {"adpcm": soak_adpcm, "decode": soak_decode, "ffmpeg": soak_ffmpeg, "encode": soak_encode, "trellis": soak_trellis,
-           "qns": soak_qns, "rate": soak_rate}[what](pkg, orc, lo, hi)
+           "qns": soak_qns, "rate": soak_rate, "requant": soak_requant}[what](pkg, orc, lo, hi)
     print("soak", what, "seeds", lo, "..", hi - 1, "mismatches:", bad)
     sys.exit(1 if bad else 0)
 
