@@ -169,6 +169,10 @@ SYMBOLS = {
     "amvhip_requant_stream_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "amvhip_requant_rate_probe_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp]),
     "amvhip_requant_rate_stream_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_clip_stream_dev": (_int, [_vp, _vp, _u32, _int, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_yuv420_clip_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "amvhip_encode_frontend_clip_stream_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "amvhip_requant_clip_stream_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "amvhip_decode_fmt_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
     "amvhip_lowres_dim": (_u32, [_u32, _u32]),
     "amvhip_lowres_frame_bytes": (_u64, [_u32, _u32, _u32]),
@@ -213,6 +217,8 @@ SYMBOLS = {
     "amvhip_mux_open": (_vp, [ctypes.c_char_p, _u32, _u32, _u32, _u32, _u32, _u32]),
     "amvhip_mux_write_frame": (_int, [_vp, _u8p, _u32, _u8p, _u32]),
     "amvhip_mux_close": (_int, [_vp]),
+    "amvhip_mux_file_bytes": (_u64, [_u32, _u64, _u64]),
+    "amvhip_mux_video_total": (_u64, [_u64, _u32, _u64]),
 }
 
 _lib = None
@@ -677,6 +683,39 @@ class Context:
         return self._check(self.lib.amvhip_encode_frontend_rate_stream_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n, self._fe(fe), w,
                                                                            h, q, r, _ptr(blob), blob_cap, _ptr(offs), _ptr(lens), _ptr(rung),
                                                                            stream), "encode_frontend_rate_stream_dev")
+
+    # a byte budget per clip: the rate siblings' arguments with `total` behind rate and clip, uint64 [2] on the device, behind rung
+    def encode_clip_stream_dev(self, pix, pix_stride, is_bgr, n, w, h, quant, rate, total, blob, blob_cap, offs, lens, rung, clip, stream=None):
+        """the n frames in at most `total` bytes: clip[0] = the clip rung (RATE_OVER or-ed in where none fit), clip[1] = the sum"""
+        q = None if quant is None else ctypes.addressof(quant)
+        r = None if rate is None else ctypes.addressof(rate)
+        return self._check(self.lib.amvhip_encode_clip_stream_dev(self.h, _ptr(pix), pix_stride, is_bgr, n, w, h, q, r, total, _ptr(blob),
+                                                                  blob_cap, _ptr(offs), _ptr(lens), _ptr(rung), _ptr(clip), stream),
+                           "encode_clip_stream_dev")
+
+    def encode_yuv420_clip_stream_dev(self, y, cb, cr, y_stride, c_stride, y_frame, c_frame, n, w, h, quant, rate, total, blob, blob_cap, offs,
+                                      lens, rung, clip, stream=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        r = None if rate is None else ctypes.addressof(rate)
+        return self._check(self.lib.amvhip_encode_yuv420_clip_stream_dev(self.h, _ptr(y), _ptr(cb), _ptr(cr), y_stride, c_stride, y_frame,
+                                                                         c_frame, n, w, h, q, r, total, _ptr(blob), blob_cap, _ptr(offs),
+                                                                         _ptr(lens), _ptr(rung), _ptr(clip), stream),
+                           "encode_yuv420_clip_stream_dev")
+
+    def encode_frontend_clip_stream_dev(self, src_fmt, src, src_w, src_h, n, fe, w, h, quant, rate, total, blob, blob_cap, offs, lens, rung,
+                                        clip, stream=None):
+        q = None if quant is None else ctypes.addressof(quant)
+        r = None if rate is None else ctypes.addressof(rate)
+        return self._check(self.lib.amvhip_encode_frontend_clip_stream_dev(self.h, src_fmt, *self._pic(src), src_w, src_h, n, self._fe(fe), w,
+                                                                           h, q, r, total, _ptr(blob), blob_cap, _ptr(offs), _ptr(lens),
+                                                                           _ptr(rung), _ptr(clip), stream), "encode_frontend_clip_stream_dev")
+
+    def requant_clip_stream_dev(self, blob, blob_bytes, offs, lens, n, w, h, rate, total, out, out_cap, out_offs, out_lens, status, rung, clip,
+                                stream=None):
+        r = None if rate is None else ctypes.addressof(rate)
+        return self._check(self.lib.amvhip_requant_clip_stream_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, r, total,
+                                                                   _ptr(out), out_cap, _ptr(out_offs), _ptr(out_lens), _ptr(status), _ptr(rung),
+                                                                   _ptr(clip), stream), "requant_clip_stream_dev")
 
     def picture_sse_supported(self, fmt, w, h):
         return picture_sse_supported(fmt, w, h)

@@ -605,4 +605,21 @@ inline RatePlan rate_plan(uint32_t n, uint32_t rungs, uint32_t blocks) {
     return p;
 }
 
+// ---- video encode: what a clip entry's workspace holds beyond the rate plan (amv_clip_plan.h; clip_core) -------------------
+// All of it zeroed by a call: the counters of the passes -- word p, p = 1 .. clip_passes_most - 1: the frames redo pass p codes
+// again; the word behind the last takes what the last check and settle append, which is nothing -- the floor sums uint64 [16]
+// and the clip's state (ClipState, amv_kernels.h).  The rate plan's own counters lie idle in a clip call.
+struct ClipPlan {
+    uint64_t counters, F, state;   // byte offsets
+    uint64_t bytes;                // the whole
+};
+inline ClipPlan clip_plan() {
+    ClipPlan p;
+    p.counters = 0;
+    p.F = 160u * 4u;               // >= clip_passes_most(16) + 1 = 137 words
+    p.state = p.F + 16u * 8u;
+    p.bytes = p.state + 16u;
+    return p;
+}
+
 }  // namespace amv

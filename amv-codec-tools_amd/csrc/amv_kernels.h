@@ -222,6 +222,32 @@ void launch_rate_check(const uint32_t* bits, const RateLadder& ladder, const uin
                        hipStream_t s);
 // ... its second launch alone (a caller whose probe kernel is its own: amv_requant.hip)
 void launch_rate_dc(const int16_t* dc, uint32_t n, uint32_t blocks, uint32_t rungs, uint32_t* bits, hipStream_t s);
+// The choice per clip (amv_encode_clip.hip, arithmetic in amv_clip_plan.h), above the choice per frame.  fr: which frames are
+// coded at all -- status nullptr: every one; else the requant entry's status, whole MCUs and range flags (a frame that is not
+// coded adds nothing to a sum, starts on the last rung flagged and stays).  state: the clip rung the frames stand at and
+// whether the clip is final (zeroed by the caller).  launch_clip_floor: the floor sums ADDED to F uint64 [rungs] (the caller
+// zeroes it).  launch_clip_start: the first rung whose floor sum fits `total` -> state->c, every frame's record and lambda
+// there (in launch_rate_choose's place).  launch_clip_settle, behind each launch_rate_check with that check's next /
+// next_count: a list was left or the clip is final -> nothing; else the sum of lens against total: final -> clip[0] = the
+// rung (kRateOver or-ed in when over), clip[1] = the sum, state->done; or the clip moves on and the frames below its new
+// rung get their records and lambdas there and form next[0 .. *next_count).
+struct ClipFrames {
+    const int32_t* status;
+    const uint32_t* nmcu_ok;
+    const uint32_t* flags;
+    uint32_t mcus;
+};
+constexpr ClipFrames kClipAllFrames{nullptr, nullptr, nullptr, 0u};
+struct ClipState {
+    uint32_t c, done, unused[2];
+};
+void launch_clip_floor(const uint32_t* bits, uint32_t rungs, const uint32_t* budgets, uint32_t budget, uint32_t n, const ClipFrames& fr,
+                       uint64_t* F, hipStream_t s);
+void launch_clip_start(const uint32_t* bits, const RateLadder& ladder, const uint32_t* budgets, uint32_t budget, uint32_t n, const ClipFrames& fr,
+                       const uint64_t* F, uint64_t total, ClipState* state, uint32_t* rung, uint32_t* lambda, hipStream_t s);
+void launch_clip_settle(const uint32_t* bits, const RateLadder& ladder, const uint32_t* budgets, uint32_t budget, uint32_t n, const ClipFrames& fr,
+                        const uint32_t* lens, const uint64_t* F, uint64_t total, ClipState* state, uint32_t* rung, uint32_t* lambda, uint32_t* next,
+                        uint32_t* next_count, uint64_t* clip, hipStream_t s);
 // Chunks requantised in the coefficient domain (amv_requant.hip, arithmetic in amv_requant_plan.h).  coef: a round of dense
 // lines of levels as the entropy stage's kernels leave them (slot p - base of item p; sel and items as launch_forward's).
 // src: the entropy stage's status and nmcu_ok (whole MCUs) of the call's frames, and, in the pass over the frames in records

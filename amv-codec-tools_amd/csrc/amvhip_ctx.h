@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "amv_clip_plan.h"
 #include "amv_host_plan.h"
 #include "amv_kernels.h"
 #include "amv_nr_plan.h"
@@ -62,6 +63,8 @@ struct amvhip_ctx {
     // the rate entries: the bits table, the frames' lambdas, the redo lists, a probe's copy of the -nr state, the DCs
     // (rate_plan of amv_host_plan.h)
     DevBuf rate_ws;
+    // the clip entries, beside rate_ws: the passes' counters, the floor sums, the clip's state (clip_plan of amv_host_plan.h)
+    DevBuf clip_ws;
     // the requant entries: a flag per frame (a block out of range); the probe entry's statuses, which it does not hand out
     DevBuf requant_flags, requant_status;
     // the shim around the rescaler: the source as YUV420P, the rescaled YUV420P ahead of a last conversion, the decoder's planes
@@ -259,6 +262,16 @@ int rate_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const QuantR
 // the tail of the front-end rate entry: the w x h pictures it made as tight_420 in c->scaled, through rate_core
 int rate_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, const RateArg& rate,
                      uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung, hipStream_t stream);
+// What a clip entry asks beyond its rate sibling (amv_clip_plan.h): the bytes of the whole clip and where the clip record goes.
+// clip_args_ok: d_clip.  clip_scaled_tail: rate_scaled_tail's counterpart through clip_core.
+struct ClipArg {
+    uint64_t total;
+    uint64_t* d_clip;
+};
+int clip_args_ok(amvhip_ctx* c, uint32_t n, const uint64_t* d_clip);
+int clip_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, const RateArg& rate,
+                     const ClipArg& clip, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung,
+                     hipStream_t stream);
 int resample_launch(amvhip_ctx* c, const PixPicture& src, uint32_t src_w, uint32_t src_h, const PixPicture& dst, uint32_t dst_w, uint32_t dst_h,
                     uint32_t n, bool to_jpeg, hipStream_t st);
 

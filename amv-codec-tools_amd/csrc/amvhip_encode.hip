@@ -600,6 +600,139 @@ extern "C" int amvhip_encode_yuv420_rate_stream_dev(amvhip_ctx* c, const uint8_t
                            blob_cap, d_offs, d_lens, d_rung, stream);
 }
 
+// ---- the clip entries: a byte budget for the whole call, above the one per frame (amv_clip_plan.h, amv_encode_clip.hip) ---
+int amv::clip_args_ok(amvhip_ctx* c, uint32_t n, const uint64_t* d_clip) {
+    if ((n && !d_clip) || ((uintptr_t)d_clip & 7u)) return fail(c, AMVHIP_ERR_ARG, "encode_clip: d_clip is null or not 8-byte aligned");
+    return AMVHIP_OK;
+}
+
+// amvhip_encode_*_clip_stream_dev's core (the context is locked, the request checked, n > 0): rate_core with the choice per
+// clip above the choice per frame.  Everything is queued on `stream`, nothing is read back:
+//   passes A and B and the probe as in rate_core; the floor sums; the start: the first clip rung whose floor sum fits, every
+//   frame's record and lambda there; the first pass over all frames; the check, and behind it the settle: with every frame
+//   inside its budget the lengths are summed, and the clip is final or moves on and lists the frames it takes along;
+//   clip_passes_most - 1 redo passes over the lists (FrameSel rounds as in rate_core, nearly all with nothing to do), each
+//   with its check and settle behind it; the compaction.
+static int clip_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, uint32_t nr, int32_t* d_state,
+                     const RateArg& rate, const ClipArg& clip, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
+                     uint32_t* d_rung, hipStream_t stream) {
+    const uint32_t bound = amvhip_encode_bound(g.width, g.height);
+    const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
+    const uint32_t round = fallback_round(n, g, 1024u, 2u);
+    const uint32_t rungs = rate.ladder.rungs;
+    const RatePlan plan = rate_plan(n, rungs, g.blocks);
+    const ClipPlan cplan = clip_plan();
+    if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
+    if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
+    if (int r = ensure(c, c->flag, 16)) return r;
+    if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
+    if (int r = ensure(c, c->clip_ws, cplan.bytes)) return r;
+    uint8_t* const ws = (uint8_t*)c->rate_ws.p;
+    uint8_t* const cws = (uint8_t*)c->clip_ws.p;
+    uint32_t* const counters = (uint32_t*)(cws + cplan.counters);
+    uint64_t* const F = (uint64_t*)(cws + cplan.F);
+    ClipState* const state = (ClipState*)(cws + cplan.state);
+    uint32_t* const bits = (uint32_t*)(ws + plan.bits);
+    uint32_t* const lambda = (uint32_t*)(ws + plan.lambda);
+    uint32_t* const lists[2] = {(uint32_t*)(ws + plan.list[0]), (uint32_t*)(ws + plan.list[1])};
+    HIP_TRY(c, hipMemsetAsync(ws + plan.zero, 0, plan.zero_bytes, stream));
+    HIP_TRY(c, hipMemsetAsync(cws, 0, cplan.bytes, stream));
+    const uint16_t* offsets = nullptr;
+    if (nr) {
+        Quantiser with_offsets;
+        if (int r = nr_quantiser(c, in, n, g, nr, d_state, nullptr, &with_offsets, stream)) return r;
+        offsets = std::get<const uint16_t*>(with_offsets);
+    }
+    if (int r = rate_probe(c, in, n, g, qbias, offsets, rate.ladder, plan, bits, stream)) return r;
+    launch_clip_floor(bits, rungs, rate.d_budget, rate.budget, n, kClipAllFrames, F, stream);
+    launch_clip_start(bits, rate.ladder, rate.d_budget, rate.budget, n, kClipAllFrames, F, clip.total, state, d_rung, lambda, stream);
+    if (int r = check_launch(c, "clip: floor + start")) return r;
+    const Quantiser quant = offsets ? Quantiser{NrTrellisFrames{offsets, lambda}} : Quantiser{TrellisFrames{lambda}};
+    for (uint32_t base = 0; base < n; base += round) {
+        const uint32_t items = n - base < round ? n - base : round;
+        {
+            Timed t(c, AMVHIP_K_FDCT, stream);
+            launch_forward(frames_from(in, base, g), items, kAllFrames, items, g, qbias, frames_from(quant, base), (int16_t*)c->coef.p, stream);
+        }
+        {
+            Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
+            launch_pack((const int16_t*)c->coef.p, items, kAllFrames, items, g, book, (uint8_t*)c->tmp.p + (uint64_t)base * bound, bound,
+                        d_lens + base, stream);
+        }
+        if (int r = check_launch(c, "clip: forward + pack")) return r;
+    }
+    launch_rate_check(bits, rate.ladder, rate.d_budget, rate.budget, n, d_lens, nullptr, nullptr, d_rung, lambda, lists[0], counters + 1, stream);
+    launch_clip_settle(bits, rate.ladder, rate.d_budget, rate.budget, n, kClipAllFrames, d_lens, F, clip.total, state, d_rung, lambda, lists[0],
+                       counters + 1, clip.d_clip, stream);
+    for (uint32_t pass = 1; pass < clip_passes_most(rungs); ++pass) {
+        const uint32_t* const list = lists[(pass - 1u) & 1u];
+        const uint32_t* const count = counters + pass;
+        for (uint32_t base = 0; base < n; base += round) {
+            const uint32_t items = n - base < round ? n - base : round;
+            const FrameSel sel{list, count, base, items};
+            {
+                Timed t(c, AMVHIP_K_FDCT, stream);
+                launch_forward(in, n, sel, items, g, qbias, quant, (int16_t*)c->coef.p, stream);
+            }
+            {
+                Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
+                launch_pack((const int16_t*)c->coef.p, n, sel, items, g, book, (uint8_t*)c->tmp.p, bound, d_lens, stream);
+            }
+        }
+        launch_rate_check(bits, rate.ladder, rate.d_budget, rate.budget, n, d_lens, list, count, d_rung, lambda, lists[pass & 1u],
+                          counters + pass + 1u, stream);
+        launch_clip_settle(bits, rate.ladder, rate.d_budget, rate.budget, n, kClipAllFrames, d_lens, F, clip.total, state, d_rung, lambda,
+                           lists[pass & 1u], counters + pass + 1u, clip.d_clip, stream);
+        if (int r = check_launch(c, "clip: redo pass")) return r;
+    }
+    {
+        Timed t(c, AMVHIP_K_COMPACT, stream);
+        launch_compact((const uint8_t*)c->tmp.p, bound, d_lens, n, d_offs, d_blob, blob_cap, (int32_t*)c->flag.p, stream);
+    }
+    return check_launch(c, "compact");
+}
+
+int amv::clip_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, const RateArg& rate,
+                          const ClipArg& clip, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung,
+                          hipStream_t stream) {
+    return clip_core(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, rate_nr_of(req).nr,
+                     rate_nr_of(req).state, rate, clip, d_blob, blob_cap, d_offs, d_lens, d_rung, stream);
+}
+
+static int clip_stream_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, const amvhip_quant* q, const amvhip_rate* rate_in,
+                           uint64_t total, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung,
+                           uint64_t* d_clip, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    QuantRequest req;
+    RateArg rate;
+    if (int r = rate_request_of(c, q, rate_in, &req, &rate)) return r;
+    if (int r = source_args_ok(c, in, n, w, h, q->qbias, n && (!d_blob || !d_offs || !d_lens))) return r;
+    if (int r = rate_args_ok(c, n, w, h, req, d_rung)) return r;
+    if (int r = clip_args_ok(c, n, d_clip)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return clip_core(c, in, n, make_geom(w, h), q->qbias, rate_nr_of(req).nr, rate_nr_of(req).state, rate, ClipArg{total, d_clip}, d_blob, blob_cap,
+                     d_offs, d_lens, d_rung, (hipStream_t)stream);
+}
+
+extern "C" int amvhip_encode_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,
+                                             uint32_t h, const amvhip_quant* q, const amvhip_rate* rate, uint64_t total, uint8_t* d_blob,
+                                             uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung, uint64_t* d_clip,
+                                             void* stream) {
+    return clip_stream_dev(c, rgb_source(d_pix, pix_stride, is_bgr), n, w, h, q, rate, total, d_blob, blob_cap, d_offs, d_lens, d_rung, d_clip,
+                           stream);
+}
+
+extern "C" int amvhip_encode_yuv420_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_y, const uint8_t* d_cb, const uint8_t* d_cr,
+                                                    uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                                    uint32_t n, uint32_t w, uint32_t h, const amvhip_quant* q, const amvhip_rate* rate,
+                                                    uint64_t total, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
+                                                    uint32_t* d_rung, uint64_t* d_clip, void* stream) {
+    return clip_stream_dev(c, yuv_source({d_y, d_cb, d_cr, y_stride, c_stride, y_frame_stride, c_frame_stride, 0u}), n, w, h, q, rate, total,
+                           d_blob, blob_cap, d_offs, d_lens, d_rung, d_clip, stream);
+}
+
 // the device-to-host half of the host-buffer encoders: offs/lens, then the chunks
 static int encode_fetch(amvhip_ctx* c, hipStream_t hs, uint32_t n, uint8_t* blob, uint64_t blob_cap, uint64_t* offs, uint32_t* lens) {
     int32_t overflow = 0;

@@ -609,6 +609,34 @@ extern "C" int amvhip_encode_frontend_rate_stream_dev(amvhip_ctx* c, int src_fmt
     return rate_scaled_tail(c, n, w, h, q->qbias, req, rate, d_blob, blob_cap, d_offs, d_lens, d_rung, (hipStream_t)stream);
 }
 
+// ... with a byte budget for the whole call above it (amv_clip_plan.h): the same, through clip_core
+extern "C" int amvhip_encode_frontend_clip_stream_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2,
+                                                      uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride,
+                                                      uint64_t src_c_frame_stride, uint32_t src_w, uint32_t src_h, uint32_t n,
+                                                      const amvhip_frontend* fe, uint32_t w, uint32_t h, const amvhip_quant* q,
+                                                      const amvhip_rate* rate_in, uint64_t total, uint8_t* d_blob, uint64_t blob_cap,
+                                                      uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung, uint64_t* d_clip, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    QuantRequest req;
+    RateArg rate;
+    if (int r = rate_request_of(c, q, rate_in, &req, &rate)) return r;
+    if (!encode_size_ok(w, h, q->qbias) || (n && (!d_blob || !d_offs || !d_lens)))
+        return fail(c, AMVHIP_ERR_ARG, "encode_frontend: bad argument (width/height must be even)");
+    if (int r = rate_args_ok(c, n, w, h, req, d_rung)) return r;
+    if (int r = clip_args_ok(c, n, d_clip)) return r;
+    const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    FrontPlan p;
+    if (int r = frontend_args_ok(c, src_fmt, src, src_w, src_h, fe, w, h, &p)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    // the padded picture is the context's: the lock is held from its allocation to the last launch that reads it
+    std::lock_guard<std::mutex> lk(c->mu);
+    if (int r = ensure(c, c->scaled, p.padded_frame_bytes * n)) return r;
+    if (int r = frontend_core(c, src_fmt, src, n, fe, p, tight_420((uint8_t*)c->scaled.p, w, h), (hipStream_t)stream)) return r;
+    return clip_scaled_tail(c, n, w, h, q->qbias, req, rate, ClipArg{total, d_clip}, d_blob, blob_cap, d_offs, d_lens, d_rung,
+                            (hipStream_t)stream);
+}
+
 // ---- `-psnr`: the host arithmetic, and picture against picture ------------------------------------------------------------
 extern "C" double amvhip_psnr_db(uint64_t sse, uint64_t samples) { return psnr_db(sse, samples); }
 

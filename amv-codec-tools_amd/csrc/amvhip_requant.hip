@@ -265,3 +265,76 @@ extern "C" int amvhip_requant_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_bl
     if (int r = check_launch(c, "requant: finish")) return r;
     return compact(c, n, bound, d_out_lens, d_out_offs, d_out, out_cap, st);
 }
+
+// amvhip_requant_rate_stream_dev's flow with the choice per clip above the choice per frame (amvhip_encode.hip: clip_core;
+// amv_clip_plan.h): the probe, the floor sums and the start over the frames that are coded, the first pass, and behind every
+// check the settle; clip_passes_most - 1 redo passes.  A frame that is not coded adds nothing to a sum.
+extern "C" int amvhip_requant_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                              const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_rate* rate, uint64_t total,
+                                              uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status,
+                                              uint32_t* d_rung, uint64_t* d_clip, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!rate) return fail(c, AMVHIP_ERR_ARG, "requant_rate: the rate request or its ladder is null");
+    RateLadder lad;
+    if (int r = requant_ladder_of(c, rate->ladder, rate->rungs, &lad)) return r;
+    if ((uintptr_t)rate->d_budget & 3u) return fail(c, AMVHIP_ERR_ARG, "requant_rate: d_budget is not 4-byte aligned");
+    if (int r = requant_args_ok(c, d_blob, d_offs, d_lens, n, w, h, d_status)) return r;
+    if (int r = requant_outputs_ok(c, n, d_out, d_out_offs, d_out_lens)) return r;
+    if (int r = requant_rate_size_ok(c, n, w, h, d_rung)) return r;
+    if (int r = clip_args_ok(c, n, d_clip)) return r;
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t st = (hipStream_t)stream;
+    const FrameGeom g = make_geom(w, h);
+    const uint32_t bound = amvhip_encode_bound(w, h), rungs = lad.rungs;
+    const RatePlan plan = rate_plan(n, rungs, g.blocks);
+    const ClipPlan cplan = clip_plan();
+    if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
+    if (int r = ensure(c, c->flag, 16)) return r;
+    if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
+    if (int r = ensure(c, c->clip_ws, cplan.bytes)) return r;
+    uint8_t* const ws = (uint8_t*)c->rate_ws.p;
+    uint8_t* const cws = (uint8_t*)c->clip_ws.p;
+    uint32_t* const counters = (uint32_t*)(cws + cplan.counters);
+    uint64_t* const F = (uint64_t*)(cws + cplan.F);
+    ClipState* const state = (ClipState*)(cws + cplan.state);
+    uint32_t* const bits = (uint32_t*)(ws + plan.bits);
+    uint32_t* const lambda = (uint32_t*)(ws + plan.lambda);
+    uint32_t* const lists[2] = {(uint32_t*)(ws + plan.list[0]), (uint32_t*)(ws + plan.list[1])};
+    Front f;
+    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, &f)) return r;
+    HIP_TRY(c, hipMemsetAsync(ws + plan.zero, 0, plan.zero_bytes, st));
+    HIP_TRY(c, hipMemsetAsync(cws, 0, cplan.bytes, st));
+    if (int r = probe_pass(c, f, lad, plan, bits, st)) return r;
+    const ClipFrames coded{f.status, f.nmcu, f.flags, g.mcus};       // (the probe has set the range flags)
+    launch_clip_floor(bits, rungs, rate->d_budget, rate->budget, n, coded, F, st);
+    launch_clip_start(bits, lad, rate->d_budget, rate->budget, n, coded, F, total, state, d_rung, lambda, st);
+    if (int r = check_launch(c, "requant_clip: floor + start")) return r;
+    if (int r = each_round(c, f, st, [&](const FrameSel& sel, uint32_t items, const RequantSource& src) {
+            return code_round(c, f, sel, items, src, 0u, lambda, nullptr, bound, d_out_lens, st);
+        }))
+        return r;
+    launch_rate_check(bits, lad, rate->d_budget, rate->budget, n, d_out_lens, nullptr, nullptr, d_rung, lambda, lists[0], counters + 1, st);
+    launch_clip_settle(bits, lad, rate->d_budget, rate->budget, n, coded, d_out_lens, F, total, state, d_rung, lambda, lists[0], counters + 1, d_clip,
+                       st);
+    for (uint32_t pass = 1; pass < clip_passes_most(rungs); ++pass) {
+        const uint32_t* const list = lists[(pass - 1u) & 1u];
+        const uint32_t* const count = counters + pass;
+        for (uint32_t base = 0; base < n; base += f.round) {
+            const uint32_t items = n - base < f.round ? n - base : f.round;
+            if (int r = serial_round(c, f, list, count, base, items, st)) return r;
+            if (int r = code_round(c, f, FrameSel{list, count, base, items}, items, RequantSource{f.status, f.nmcu, nullptr}, 0u, lambda, nullptr,
+                                   bound, d_out_lens, st))
+                return r;
+        }
+        launch_rate_check(bits, lad, rate->d_budget, rate->budget, n, d_out_lens, list, count, d_rung, lambda, lists[pass & 1u], counters + pass + 1u,
+                          st);
+        launch_clip_settle(bits, lad, rate->d_budget, rate->budget, n, coded, d_out_lens, F, total, state, d_rung, lambda, lists[pass & 1u],
+                           counters + pass + 1u, d_clip, st);
+        if (int r = check_launch(c, "requant_clip: redo pass")) return r;
+    }
+    launch_requant_finish(n, g, d_status, f.nmcu, f.flags, d_out_lens, nullptr, d_rung, nullptr, rungs, st);
+    if (int r = check_launch(c, "requant: finish")) return r;
+    return compact(c, n, bound, d_out_lens, d_out_offs, d_out, out_cap, st);
+}

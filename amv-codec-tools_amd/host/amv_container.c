@@ -190,6 +190,24 @@ int amvhip_mux_close(amvhip_muxer *m)
     return rc;
 }
 
+/* The size of what open / write_frame x n / close leave: everything up to and including "movi" (the 304-byte header, the
+ * movi list's tag and size, the word itself), a tag and a size in front of each of the 2 n payloads, which are not padded,
+ * and "AMV_END_". */
+#define AMV_MUX_FIXED_BYTES (0x138u + 4u + 8u)
+#define AMV_MUX_FRAME_BYTES 16u
+uint64_t amvhip_mux_file_bytes(uint32_t n, uint64_t video_bytes, uint64_t audio_bytes)
+{
+    return AMV_MUX_FIXED_BYTES + (uint64_t)n * AMV_MUX_FRAME_BYTES + video_bytes + audio_bytes;
+}
+
+/* ... and back: the most video bytes with which n frames and audio_bytes of audio stay inside file_bytes; 0 if there are none */
+uint64_t amvhip_mux_video_total(uint64_t file_bytes, uint32_t n, uint64_t audio_bytes)
+{
+    const uint64_t fixed = AMV_MUX_FIXED_BYTES + (uint64_t)n * AMV_MUX_FRAME_BYTES;   /* < 2^37 */
+    if (file_bytes < fixed || file_bytes - fixed < audio_bytes) return 0;
+    return file_bytes - fixed - audio_bytes;
+}
+
 /* ---------------------------------------------------------------------------------------------
  * AMV audio framing of the reference's encoder and muxer, in host arithmetic (no device work)
  * ------------------------------------------------------------------------------------------- */

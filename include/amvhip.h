@@ -955,6 +955,65 @@ int amvhip_requant_rate_stream_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint6
                                    uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offs, uint32_t *d_out_lens,
                                    int32_t *d_status, uint32_t *d_rung, void *stream);
 /*
+ * A byte budget per CLIP -- "these n frames in at most `total` bytes" -- settled on the device (device-pointer forms only).
+ *
+ * The terms are the rate section's: the ladder, len_r(i), B(i) (d_budget[i], or `budget`; a caller who wants no cap per frame
+ * passes budget = 0xffffffff) and AMVHIP_RATE_OVER.
+ *   Per frame.  For a clip rung c in 0 .. rungs - 1, frame i is coded at r_c(i): the FIRST r >= c, in ladder order, with
+ *               len_r(i) <= B(i); if none fits, the last rung, flagged AMVHIP_RATE_OVER.
+ *   The sum.    S(c) = the sum over i of len_{r_c(i)}(i), a uint64.
+ *   The clip.   The chosen clip rung c* is the FIRST c with S(c) <= total; if none fits, c* = rungs - 1 and AMVHIP_RATE_OVER
+ *               is or-ed into the clip record.  (S is not monotone in c, and duplicate and descending ladders have a meaning
+ *               too: "first", and nothing bisects.)
+ *   Chunks.     Byte for byte those of the rate sibling called with ladder + c* and rungs - c*: that trellis or requant
+ *               entry's chunks at ladder[r(i)], in both entropy modes; d_offs, d_lens and the blob-capacity rule as there.
+ *   d_rung[i]   indexes the caller's full ladder: c* + that call's rung, AMVHIP_RATE_OVER as in that call.
+ *   d_clip      uint64 [2] on the device, 8-byte aligned: [0] = c*, AMVHIP_RATE_OVER or-ed in when no clip rung fit;
+ *               [1] = S(c*).  S is taken over the lengths the coder produced, before the blob-capacity rule drops a chunk: a
+ *               blob that is too small changes neither c*, d_rung nor d_clip.
+ *   -nr         the state advances once per call, as in the rate entries.
+ * One lambda for the whole clip is the equal-slope allocation of a total (the trellis walk minimises distortion + lambda *
+ * bits per block); the first fit per frame on top of it is the guard against a chunk a player stalls on.
+ *
+ * How: the probe's bits give, without packing a byte, a lower bound F(c) of S(c) (csrc/amv_clip_plan.h), so the clip starts
+ * at the first c whose bound fits and passes every later c whose bound does not; at a clip rung the frames are coded and
+ * moved along their floor-fits as in a rate call, the lengths are summed on the device, and the clip is final or moves to
+ * the next c, taking along only the frames that stand below it.  The passes are queued without knowing their counts, at
+ * most rungs * (rungs + 1) / 2 of them, nearly all of which find nothing to do.  No host synchronisation.
+ *
+ *   amvhip_encode_clip_stream_dev (RGB24 / BGR24), amvhip_encode_yuv420_clip_stream_dev, amvhip_encode_frontend_clip_stream_dev
+ *       the arguments of the _rate_stream_dev sibling with `total` behind rate and d_clip behind d_rung.
+ *   amvhip_requant_clip_stream_dev
+ *       amvhip_requant_rate_stream_dev's likewise.  A frame that is not coded contributes 0 to S, keeps AMVHIP_RATE_OVER |
+ *       (rungs - 1) and d_out_lens 0: its bytes are the caller's, who subtracts them from `total`.
+ * AMVHIP_ERR_ARG with nothing queued and the state untouched: whatever the rate sibling refuses (the picture of more than
+ * 349 525 MCUs included), and a NULL or misaligned d_clip.  n == 0 succeeds and queues nothing (d_clip is not written).
+ * Not here: spending the slack between S(c*) and total on single frames, a carry of unused bytes from frame to frame, a
+ * total split over several calls, host-buffer forms, 4:2:2 sources, qns in a clip call.
+ *
+ * From a file size to `total` and back: amvhip_mux_file_bytes / amvhip_mux_video_total beside the muxer below.
+ */
+int amvhip_encode_clip_stream_dev(amvhip_ctx *ctx, const uint8_t *d_pix, uint32_t pix_stride, int is_bgr, uint32_t n,
+                                  uint32_t width, uint32_t height, const amvhip_quant *q, const amvhip_rate *rate,
+                                  uint64_t total, uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens,
+                                  uint32_t *d_rung, uint64_t *d_clip, void *stream);
+int amvhip_encode_yuv420_clip_stream_dev(amvhip_ctx *ctx, const uint8_t *d_y, const uint8_t *d_cb, const uint8_t *d_cr,
+                                         uint32_t y_stride, uint32_t c_stride, uint64_t y_frame_stride, uint64_t c_frame_stride,
+                                         uint32_t n, uint32_t width, uint32_t height, const amvhip_quant *q,
+                                         const amvhip_rate *rate, uint64_t total, uint8_t *d_blob, uint64_t blob_cap,
+                                         uint64_t *d_offs, uint32_t *d_lens, uint32_t *d_rung, uint64_t *d_clip, void *stream);
+int amvhip_encode_frontend_clip_stream_dev(amvhip_ctx *ctx, int src_fmt, const uint8_t *d_src0, const uint8_t *d_src1,
+                                           const uint8_t *d_src2, uint32_t src_stride, uint32_t src_c_stride,
+                                           uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint32_t src_width,
+                                           uint32_t src_height, uint32_t n, const amvhip_frontend *fe, uint32_t width,
+                                           uint32_t height, const amvhip_quant *q, const amvhip_rate *rate, uint64_t total,
+                                           uint8_t *d_blob, uint64_t blob_cap, uint64_t *d_offs, uint32_t *d_lens,
+                                           uint32_t *d_rung, uint64_t *d_clip, void *stream);
+int amvhip_requant_clip_stream_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_offs,
+                                   const uint32_t *d_lens, uint32_t n, uint32_t width, uint32_t height, const amvhip_rate *rate,
+                                   uint64_t total, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offs, uint32_t *d_out_lens,
+                                   int32_t *d_status, uint32_t *d_rung, uint64_t *d_clip, void *stream);
+/*
  * Decoder + back end in one call: the patched FFmpeg's amv decoder (AMVHIP_FLAG_FFMPEG, required: AMVHIP_ERR_ARG without)
  * into workspace planes, then img_convert YUVJ420P -> dst_fmt (yuvj420p_to_*, imgconvert.c:1977-1993; the planar route for
  * YUV420P; the gray route for GRAY8): what `ffmpeg -i x.amv [-pix_fmt rgb24|bgr24|rgb32|rgb565] out` hands its next stage
@@ -1172,6 +1231,14 @@ amvhip_muxer *amvhip_mux_open(const char *path, uint32_t width, uint32_t height,
 int amvhip_mux_write_frame(amvhip_muxer *m, const uint8_t *video, uint32_t video_len, const uint8_t *audio,
                            uint32_t audio_len);
 int amvhip_mux_close(amvhip_muxer *m);
+/*
+ * amvhip_mux_file_bytes: exactly the size of the file open / write_frame x n / close leave for payloads of video_bytes and
+ * audio_bytes in all -- the header, "movi", a tag and a size per chunk, the unpadded payloads, the trailer.
+ * amvhip_mux_video_total: its inverse, the largest video_bytes with amvhip_mux_file_bytes(n, video_bytes, audio_bytes) <=
+ * file_bytes, or 0 if there is none: the `total` of a clip entry for a caller whose card has file_bytes left.
+ */
+uint64_t amvhip_mux_file_bytes(uint32_t n, uint64_t video_bytes, uint64_t audio_bytes);
+uint64_t amvhip_mux_video_total(uint64_t file_bytes, uint32_t n, uint64_t audio_bytes);
 
 /*
  * Kernel timing with HIP events recorded on the launch stream around every kernel

@@ -28,6 +28,11 @@ line per mismatch and a summary, and exits non-zero if anything differed.
                  of the chunks damaged -- a flipped byte, a cut, junk behind the scan -- one lambda from 0 to the bound and a
                  ladder of 1 .. 6 rungs in any order with budgets drawn per frame around the model's own lengths, in both
                  entropy modes: chunks, offsets, d_status, d_err, d_bits and d_rung against tests/requant_ref.py.
+  clip LO HI     the clip entries on soak_rate's geometries, ladders, -nr states and budgets per frame (a third without a cap),
+                 every fifth seed through the requant entry on chunks of which a quarter are cut; the total drawn around the
+                 model's own S(c) and F(c), 0 and 2^64 - 1 among them (so that clips stay, move after coding, pass rungs on their
+                 floor sums and run over), in both entropy modes: chunks, offsets, d_rung, d_clip, d_status and the state against
+                 tests/clip_ref.py, and the model's device walk against its definition.
 """
 import os
 import sys
@@ -457,15 +462,119 @@ def soak_requant(pkg, orc, lo, hi):
     return bad
 
 
+def soak_clip(pkg, orc, lo, hi):
+    import torch
+    import clip_ref as C
+    import rate_ref as R
+    import requant_ref as Q
+    import test_gpu_parity as T
+    ctx = pkg.Context(0)
+    bad = frames_seen = bumps = flagged = passes_most = 0
+    for seed in range(lo, hi):
+        rng = np.random.default_rng(seed)
+        w, h = 2 * int(rng.integers(4, 60)), 2 * int(rng.integers(4, 50))
+        blocks = 6 * ((w + 15) // 16) * ((h + 15) // 16)
+        n = max(1, min(int(rng.integers(1, 7)), 600 // blocks))
+        qbias = int(rng.choice([0, 128, int(rng.integers(0, 256))]))
+        rungs = int(rng.integers(1, 7))
+        pool = [0, 400, 3481, 20000, R.T.LAMBDA_MAX, int(rng.integers(0, R.T.LAMBDA_MAX + 1)), int(rng.integers(0, 30000))]
+        ladder = [int(rng.choice(pool)) for _ in range(rungs)]
+        if seed & 1:
+            ladder.sort()
+        nr = int(rng.integers(1, ctx.encode_nr_max(w, h) + 1)) if seed % 3 == 0 else 0
+        state = None
+        if nr:
+            count = int(rng.integers(1, 65000))
+            state = np.concatenate([rng.integers(0, 200, 64) * count, [count]]).astype(np.int64)
+        frames = R.N.stream(w, h, [R.KINDS[int(rng.integers(0, 4))] for _ in range(n)], 1000 + seed)
+        requant_source = seed % 5 == 4                                   # every fifth seed: chunks in, some of them damaged
+        if requant_source:
+            chunks = Q.synth_chunks(w, h, n, seed=SEED + seed, qbias=int(rng.choice([0, 128])))
+            for i in range(n):
+                if rng.integers(0, 4) == 0:
+                    chunks[i] = chunks[i][: int(rng.integers(2, len(chunks[i])))]
+            lens, coded = C.requant_lens(chunks, w, h, ladder)
+            bits = Q.bits_table(chunks, w, h, ladder)
+        else:
+            bits = R.bits_table(frames, w, h, qbias, nr, state, ladder)
+            lens, coded = R.lens_table(frames, w, h, qbias, nr, state, ladder), None
+        B = []
+        for i in range(n):
+            r = int(rng.integers(0, rungs))
+            B.append(max(0, int(rng.choice([lens[i][r], lens[i][r] - 1, R.floor_bytes(int(bits[i][r])), 7, 0xFFFFFFFF, 0xFFFFFFFF,
+                                            int(rng.integers(0, int(lens[i].max()) + 2))]))))
+        uniform = seed % 4 == 3
+        if uniform:
+            B = [B[0]] * n
+        S, F = C.sums(lens, B, coded), C.floor_sums(bits, B, coded)
+        totals = [x + d for x in S + F for d in (-1, 0, 1)] + [0, C.U64_MAX, int(rng.integers(0, max(S) + 2))]
+        total = max(0, totals[int(rng.integers(0, len(totals)))])        # (picked by index: 2^64 - 1 is no numpy integer)
+        walk = C.device_walk(bits, lens, B, total, coded)
+        frames_seen += n
+        bumps += len(walk[6]) - 1
+        flagged += int(walk[1])
+        passes_most = max(passes_most, walk[4])
+        cap = ctx.encode_bound(w, h) * n
+        d_budget = None if uniform else T._t(np.array(B, np.uint32))      # (kept alive here: the Rate holds the address alone)
+        rate = pkg.Rate(ladder, budget=B[0], d_budget=d_budget)
+        if requant_source:
+            want, status, want_rungs, want_clip = C.requant(chunks, w, h, ladder, B, total)
+            blob, offs, in_lens = Q.pack(chunks)
+            ins = (T._t(blob), int(in_lens.sum()), T._t(offs), T._t(in_lens), n, w, h)
+        else:
+            want, want_rungs, want_clip, want_state = C.encode(frames, w, h, qbias, nr, state, ladder, B, total)
+            n_pad = 8
+            Y = np.full((n, h, w + n_pad), 0xEE, np.uint8)
+            Cb, Cr = np.full((n, h // 2, w // 2 + n_pad), 0xEE, np.uint8), np.full((n, h // 2, w // 2 + n_pad), 0xEE, np.uint8)
+            for i, (y, cb, cr) in enumerate(frames):
+                Y[i, :, :w], Cb[i, :, :w // 2], Cr[i, :, :w // 2] = y, cb, cr
+            planes = (T._t(Y), T._t(Cb), T._t(Cr), w + n_pad, w // 2 + n_pad, h * (w + n_pad), (h // 2) * (w // 2 + n_pad), n, w, h)
+        for mode in (pkg.ENTROPY_AUTO, pkg.ENTROPY_SERIAL):
+            ctx.set_entropy_mode(mode)
+            d_blob = torch.zeros(cap, dtype=torch.uint8, device="cuda:0")
+            d_offs = torch.zeros(n, dtype=torch.int64, device="cuda:0")
+            d_lens = torch.zeros(n, dtype=torch.int32, device="cuda:0")
+            d_rung = torch.zeros(n, dtype=torch.int32, device="cuda:0")
+            d_clip = torch.full((2,), -1, dtype=torch.int64, device="cuda:0")
+            if requant_source:
+                d_status = torch.full((n,), -1, dtype=torch.int32, device="cuda:0")
+                ctx.requant_clip_stream_dev(*ins, rate, total, d_blob, cap, d_offs, d_lens, d_status, d_rung, d_clip)
+            else:
+                d_state = None if state is None else T._t(state.astype(np.int32))
+                ctx.encode_yuv420_clip_stream_dev(*planes, pkg.Quant(qbias, nr, 1, 0, d_state), rate, total, d_blob, cap, d_offs, d_lens, d_rung,
+                                                  d_clip)
+            torch.cuda.synchronize()
+            blob_got, offs_got, got_lens = d_blob.cpu().numpy(), d_offs.cpu().numpy(), d_lens.cpu().numpy()
+            ok = d_rung.cpu().numpy().view(np.uint32).tolist() == want_rungs
+            ok = ok and [int(x) for x in d_clip.cpu().numpy().view(np.uint64)] == list(want_clip)
+            ok = ok and (walk[0] | (R.OVER if walk[1] else 0), walk[2]) == tuple(want_clip) and walk[3] == want_rungs
+            if requant_source:
+                ok = ok and d_status.cpu().numpy().tolist() == status
+            else:
+                ok = ok and (state is None or (d_state.cpu().numpy() == want_state).all())
+            pos = 0
+            for i, c in enumerate(want):
+                size = len(c) if c else 0
+                ok = ok and (int(offs_got[i]), int(got_lens[i])) == (pos, size) and (not size or blob_got[pos: pos + size].tobytes() == c)
+                pos += size
+            if not ok:
+                bad += 1
+                print("MISMATCH clip seed", seed, w, h, n, "requant" if requant_source else "encode", "qbias", qbias, "nr", nr, "ladder", ladder,
+                      "budgets", B, "uniform", uniform, "total", total, "mode", mode, flush=True)
+        ctx.set_entropy_mode(pkg.ENTROPY_AUTO)
+    print("frames", frames_seen, "moves of the clip", bumps, "clips over every rung", flagged, "the most passes of a call", passes_most)
+    return bad
+
+
 def main():
-    if len(sys.argv) != 4 or sys.argv[1] not in ("adpcm", "decode", "ffmpeg", "encode", "trellis", "qns", "rate", "requant"):
+    if len(sys.argv) != 4 or sys.argv[1] not in ("adpcm", "decode", "ffmpeg", "encode", "trellis", "qns", "rate", "requant", "clip"):
         raise SystemExit(__doc__)
     what, lo, hi = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
     pkg = entry.build()
     orc = entry.load_oracle()
     orc.lib()
     bad = {"adpcm": soak_adpcm, "decode": soak_decode, "ffmpeg": soak_ffmpeg, "encode": soak_encode, "trellis": soak_trellis,
-           "qns": soak_qns, "rate": soak_rate, "requant": soak_requant}[what](pkg, orc, lo, hi)
+           "qns": soak_qns, "rate": soak_rate, "requant": soak_requant, "clip": soak_clip}[what](pkg, orc, lo, hi)
     print("soak", what, "seeds", lo, "..", hi - 1, "mismatches:", bad)
     sys.exit(1 if bad else 0)
 
