@@ -583,7 +583,7 @@ __device__ __forceinline__ void fast_skip(Stream& win, uint32_t ringb, FastState
 }  // namespace
 
 // dynamic LDS: [ the four tables, 32 KB | staged records, 2 * kFlush slots per wave (a stride's eight, alternating) |
-//                DC sums, 4 slots per wave | rings, 17 slots per wave ]
+//                DC sums, 4 slots per wave (three sums; the fourth says where the wave stands in its task) | rings, 17 slots per wave ]
 template <uint32_t kFlush>
 __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
     const uint32_t* __restrict__ ws, const uint32_t* __restrict__ ws_bytes, uint32_t n,
@@ -601,6 +601,12 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
         uint4* dst = reinterpret_cast<uint4*>(s_mem);
         for (uint32_t i = threadIdx.x; i < kFastTableBytes / 16u; i += blockDim.x) dst[i] = src[i];
     }
+    // Where the wave stands in its task, for the waves it shares a SIMD with (the task loop keeps pace by it): the fourth slot of the wave's
+    // DC sums, which the walk never touches (three components), word 0.
+    const uint32_t simd = (__builtin_amdgcn_s_getreg((31 << 11) | 4) >> 4) & 3u;   // HW_ID bits 4-5
+    volatile uint32_t* const pace = reinterpret_cast<volatile uint32_t*>(s_mem + kFastTableBytes + nwaves * fast_stage_bytes(kFlush) + 3u * kSlot);
+    constexpr uint32_t kPaceStep = kFastSumBytes / 4u;   // words from a wave's to the next one's
+    if (lane == 0) pace[wave * kPaceStep] = simd;
     __syncthreads();   // the only workgroup-wide barrier; from here the waves are on their own
     // lds_get takes raw LDS addresses: the dynamic segment must begin at 0.  Should a toolchain ever put something in
     // front of it, the kernel decodes nothing and hands its frames to the serial kernel instead.
@@ -616,7 +622,18 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
         uint32_t task = 0;
         if (lane == 0) task = atomicAdd(queue, 1u);
         task = __shfl(task, 0);
-        if (task >= ntasks) return;
+        if (task >= ntasks) {
+            if (lane == 0) pace[wave * kPaceStep] = kNever;   // out of the others' way
+            return;
+        }
+        // optional (amvhip_entropy_stats): the task's own line (amvhip_entropy_trace), as amv_huffman_sync2_kernel's.  When it
+        // began goes to the line at once, so that nothing of it is held in registers across the walk.
+        const bool tracing = stats != nullptr && lane == 0 && task < kTraceTasks;
+        if (tracing) {
+            unsigned long long* tr = stats + kTraceBase + (unsigned long long)task * 8ull;
+            tr[0] = wall_clock64();                         // constant-rate clock, 100 MHz
+            tr[2] = clock64();                              // shader clocks
+        }
         const uint32_t idx = task * kWave + lane;
         const uint32_t frame = idx < n ? (list ? list[idx] : idx) : kNever;
         uint32_t total = frame != kNever ? ws_bytes[frame] : kNever;   // kNever: handed to the serial kernel
@@ -661,6 +678,16 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
 #pragma unroll
         for (uint32_t q = 0; q < 2u * kFlush; ++q) stage_put<kFlush>(stage, q, kDummyRecord);
         if (__ballot(alive) != 0ull) do {
+            {   // Keep pace with the SIMD's other waves.  The issue arbiter serves the oldest wave first, so the waves of a
+                // SIMD finish one after the other and the last of them ends the launch on a unit that is mostly empty
+                // (profiles/r23_fast_contexts_trace_160k.json).  Once per line group a wave says where it stands; the one
+                // that is not ahead of a SIMD-mate by more than a line group takes the higher priority.
+                if (lane == 0) pace[wave * kPaceStep] = (stride_no << 2) | simd;
+                const uint32_t peer = lane < nwaves ? pace[lane * kPaceStep] : kNever;
+                const bool ahead_of = peer != kNever && lane != wave && (peer & 3u) == simd && (peer >> 2) + 4u < stride_no;
+                if (__ballot(ahead_of) != 0ull) __builtin_amdgcn_s_setprio(0);
+                else __builtin_amdgcn_s_setprio(3);
+            }
             const bool line_live = alive;   // records of this lane may come in these four strides
             uint4 line[8];
 #pragma unroll
@@ -734,6 +761,17 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
                 nmcu_ok[frame] = out.ok_in_blocks ? end_blocks : end_blocks / 6u;
                 out.rec_count[frame] = recpos;
             }
+        }
+        if (stats != nullptr && lane == 0 && task < kTraceTasks) {   // ... and when it ended
+            unsigned long long* tr = stats + kTraceBase + (unsigned long long)task * 8ull;
+            tr[1] = wall_clock64();
+            tr[2] = clock64() - tr[2];                      // shader clocks of the task
+            tr[3] = stride_no;                              // strides of its longest frame
+            tr[4] = 0ull;
+            // where the wave ran: HW_ID (SIMD in bits 4-5, compute unit 8-11, shader array 12, engine 13-15) and XCC_ID
+            tr[5] = (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) | (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32;
+            tr[6] = 0ull;                                   // (no rounds, no share)
+            tr[7] = (unsigned long long)blockIdx.x << 32 | (unsigned long long)wave << 16 | 1ull;
         }
     }   // next task
 }

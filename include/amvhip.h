@@ -299,6 +299,8 @@ int amvhip_entropy_stats(amvhip_ctx *ctx, int enable, uint64_t out[10]);
  * synchronisation rounds, the strict pass, the DC pass, rounds of the wave's worst frame | share length in bits << 32,
  * workgroup << 32 | wave << 16 | lanes per frame}.  out: 8 * tasks words; returns the lines copied (< 0: error).  Lines behind
  * the launch's tasks are zero when no launch since gathering went on had more (amvhip_entropy_stats clears them then).
+ * The one-lane-per-frame kernel writes the same line per task of 64 frames, with {shader clocks of the task, strides of its
+ * longest frame, 0, HW_ID | XCC_ID << 32 (the SIMD the wave ran on is bits 4-5), 0} in words 2 - 6 and 1 as its lanes per frame.
  * What a launch one generation of waves deep lasts as long as: its slowest task (tools/time_kernels.py --trace). */
 int amvhip_entropy_trace(amvhip_ctx *ctx, uint64_t *out, uint32_t tasks);
 /* A batch large enough to give every frame ONE entropy lane (a wave's 64 frames then finish together) gives the frames

@@ -22,7 +22,7 @@ ap.add_argument("--serial", action="store_true")
 ap.add_argument("--noise", action="store_true", help="white-noise frames (every coefficient of every block non-zero)")
 ap.add_argument("--mixed", type=int, default=0, help="every k-th frame white noise")
 ap.add_argument("--same", type=int, default=-1, help="every frame of the batch is a copy of this frame (no spread in sync rounds)")
-ap.add_argument("--trace", default="", help="write the per-wave lines of the several-lanes-per-frame launch (amvhip_entropy_trace) to this file")
+ap.add_argument("--trace", default="", help="write the per-task lines of the entropy launch (amvhip_entropy_trace: the several-lanes-per-frame kernels and the one-lane kernel) to this file")
 a = ap.parse_args()
 pkg = entry.load_package()
 ctx = pkg.Context(0)
@@ -88,7 +88,12 @@ if a.trace:
         rounds = (tr[:, 6] & np.uint64(0xffffffff)).astype(np.int64)
         share = (tr[:, 6] >> np.uint64(32)).astype(np.int64)
         order = np.argsort(-end)
-        res["trace"] = {"waves": int(len(tr)), "launch_us": float(end.max()), "begin_us_p50_max": [float(np.median(beg)), float(beg.max())],
+        wave = ((tr[:, 7] >> np.uint64(16)) & np.uint64(0xffff)).astype(np.int64)
+        res["trace"] = {"waves": int(len(tr)), "lanes_per_frame": int(tr[0, 7] & np.uint64(0xffff)),
+                        # by wave number inside the workgroup: [wave, tasks, mean duration, last end] (us)
+                        "by_wave_number": [[int(k), int((wave == k).sum()), round(float(dur[wave == k].mean()), 1), round(float(end[wave == k].max()), 1)]
+                                           for k in np.unique(wave)],
+                        "launch_us": float(end.max()), "begin_us_p50_max": [float(np.median(beg)), float(beg.max())],
                         "duration_us_p50_p99_max": [float(np.percentile(dur, q)) for q in (50, 99, 100)],
                         "rounds_hist": {int(k): int((rounds == k).sum()) for k in np.unique(rounds)},
                         "last_to_end": [{"end_us": float(end[i]), "begin_us": float(beg[i]), "rounds": int(rounds[i]), "share_bits": int(share[i]),
