@@ -15,6 +15,8 @@ LIB_PATH = os.environ.get("AMVHIP_LIB") or os.path.join(_HERE, "libamvhip.so")  
 OK, ERR_ARG, ERR_DEVICE, ERR_NOMEM, ERR_SPACE = 0, -1, -2, -3, -4
 ST_FORMAT, ST_OVERRUN, ST_TRUNCATED = 1, 2, 4
 ST_RANGE = 8            # requant: a block outside the range the search is proved for
+ST_TABLE = 16           # retable: the frame's table index names no table
+RETABLE_TABLES_MAX = 64
 FLAG_ZIGZAG_FIXED = 1
 FLAG_FFMPEG = 2
 FLAG_FFMPEG_KEEP = 4
@@ -173,6 +175,11 @@ SYMBOLS = {
     "amvhip_encode_yuv420_clip_stream_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "amvhip_encode_frontend_clip_stream_dev": (_int, [_vp, _int, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
     "amvhip_requant_clip_stream_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "amvhip_retable_stream_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "amvhip_retable_rate_probe_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "amvhip_retable_rate_stream_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp, _vp, _vp]),
+    "amvhip_retable_clip_stream_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u64, _vp, _u64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "amvhip_ffmpeg_amv_tables": (_int, [_u32, _vp]),
     "amvhip_decode_fmt_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
     "amvhip_lowres_dim": (_u32, [_u32, _u32]),
     "amvhip_lowres_frame_bytes": (_u64, [_u32, _u32, _u32]),
@@ -282,6 +289,29 @@ class Rate(ctypes.Structure):
         at = None if self._ladder is None else ctypes.addressof(self._ladder)
         own = 0 if ladder is None else len(ladder)
         super().__init__(at, int(own if rungs is None else rungs), int(budget), _ptr(d_budget))
+
+
+class Retable(ctypes.Structure):
+    """amvhip_retable of include/amvhip.h: the tables the chunks were written against (host) and the frames' table indices
+    (uint8 [n] on the device, or None: table 0 for every frame)"""
+    _fields_ = [("tables", _vp), ("count", _u32), ("d_table_of", _vp)]
+
+    def __init__(self, tables, d_table_of=None, count=None):
+        """tables: uint8 [count][2][64] (anything numpy takes; kept alive here as a C array), or None for NULL; count: the
+        count handed over where it is not the tables' own; d_table_of: a tensor or an address the caller keeps alive"""
+        flat = None if tables is None else [int(x) for t in tables for comp in t for x in comp]
+        self._tables = None if flat is None else (ctypes.c_uint8 * max(len(flat), 1))(*flat)
+        at = None if self._tables is None else ctypes.addressof(self._tables)
+        own = 0 if flat is None else len(flat) // 128
+        super().__init__(at, int(own if count is None else count), _ptr(d_table_of))
+
+
+def ffmpeg_amv_tables(qscale):
+    """the reference encoder's tables at -qscale 1 .. 31 -> [2][64] lists, scan order (None outside); needs no device"""
+    out = (ctypes.c_uint8 * 128)()
+    if load_library().amvhip_ffmpeg_amv_tables(int(qscale), ctypes.cast(out, ctypes.c_void_p)) != OK:
+        return None
+    return [list(out[:64]), list(out[64:])]
 
 
 def pad_color_from_rgb(rrggbb):
@@ -716,6 +746,34 @@ class Context:
         return self._check(self.lib.amvhip_requant_clip_stream_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, r, total,
                                                                    _ptr(out), out_cap, _ptr(out_offs), _ptr(out_lens), _ptr(status), _ptr(rung),
                                                                    _ptr(clip), stream), "requant_clip_stream_dev")
+
+    # re-table: the requant entries with a Retable (the tables the chunks were written against) behind h
+    def retable_stream_dev(self, blob, blob_bytes, offs, lens, n, w, h, rt, lam, out, out_cap, out_offs, out_lens, status, err=None, stream=None):
+        t = None if rt is None else ctypes.addressof(rt)
+        return self._check(self.lib.amvhip_retable_stream_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, t, lam, _ptr(out),
+                                                              out_cap, _ptr(out_offs), _ptr(out_lens), _ptr(status), _ptr(err), stream),
+                           "retable_stream_dev")
+
+    def retable_rate_probe_dev(self, blob, blob_bytes, offs, lens, n, w, h, rt, ladder, bits, stream=None, rungs=None):
+        t = None if rt is None else ctypes.addressof(rt)
+        rate = Rate(ladder, rungs=rungs)
+        return self._check(self.lib.amvhip_retable_rate_probe_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, t, rate.ladder,
+                                                                  rate.rungs, _ptr(bits), stream), "retable_rate_probe_dev")
+
+    def retable_rate_stream_dev(self, blob, blob_bytes, offs, lens, n, w, h, rt, rate, out, out_cap, out_offs, out_lens, status, rung, stream=None):
+        t = None if rt is None else ctypes.addressof(rt)
+        r = None if rate is None else ctypes.addressof(rate)
+        return self._check(self.lib.amvhip_retable_rate_stream_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, t, r, _ptr(out),
+                                                                   out_cap, _ptr(out_offs), _ptr(out_lens), _ptr(status), _ptr(rung), stream),
+                           "retable_rate_stream_dev")
+
+    def retable_clip_stream_dev(self, blob, blob_bytes, offs, lens, n, w, h, rt, rate, total, out, out_cap, out_offs, out_lens, status, rung,
+                                clip, stream=None):
+        t = None if rt is None else ctypes.addressof(rt)
+        r = None if rate is None else ctypes.addressof(rate)
+        return self._check(self.lib.amvhip_retable_clip_stream_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, t, r, total,
+                                                                   _ptr(out), out_cap, _ptr(out_offs), _ptr(out_lens), _ptr(status), _ptr(rung),
+                                                                   _ptr(clip), stream), "retable_clip_stream_dev")
 
     def picture_sse_supported(self, fmt, w, h):
         return picture_sse_supported(fmt, w, h)

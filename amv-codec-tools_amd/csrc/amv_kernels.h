@@ -270,6 +270,21 @@ void launch_requant_probe(const int16_t* coef, uint32_t n, const FrameSel& sel, 
                           const RateLadder& ladder, uint32_t* flags, int16_t* dc, uint32_t* bits, hipStream_t s);
 void launch_requant_finish(uint32_t n, const FrameGeom& g, int32_t* status, const uint32_t* nmcu_ok, const uint32_t* flags, uint32_t* lens,
                            uint64_t* err, uint32_t* rung, uint32_t* bits, uint32_t rungs, hipStream_t s);
+// Chunks re-tabled (amv_retable.hip, arithmetic in amv_retable_plan.h): launch_requant / launch_requant_probe with the tables
+// the chunks were written against.  tables: uint8 [count][2][64] on the device (luma then chroma, scan order, entries 1 ..
+// 255), count 1 .. 64; table_of: uint8 [n] on the device, a frame's table (nullptr: table 0).  The line's DC and dc[] are the
+// NEW DC; err sums over all 64 positions.  flags[f] bit 0: a block out of range; bit 1: table_of[f] names no table (the frame
+// is not coded).  launch_retable_status, behind launch_requant_finish: such a frame's status becomes AMVHIP_ST_TABLE.
+struct RetableTables {
+    const uint8_t* tables;
+    uint32_t count;
+    const uint8_t* table_of;
+};
+void launch_retable(int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const RequantSource& src,
+                    const RetableTables& rt, uint32_t lambda, const uint32_t* lambdas, uint32_t* flags, uint64_t* err, hipStream_t s);
+void launch_retable_probe(const int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const RequantSource& src,
+                          const RetableTables& rt, const RateLadder& ladder, uint32_t* flags, int16_t* dc, uint32_t* bits, hipStream_t s);
+void launch_retable_status(uint32_t n, int32_t* status, const uint32_t* flags, hipStream_t s);
 // exclusive scan of lens -> offs (single workgroup), then gather tmp -> blob.  A chunk that would end past
 // blob_cap is not copied and its lens entry becomes 0; *overflow = 1 when the total exceeds blob_cap.
 void launch_compact(const uint8_t* tmp, uint32_t bound, uint32_t* lens, uint32_t n,

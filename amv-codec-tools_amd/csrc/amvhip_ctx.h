@@ -20,6 +20,7 @@
 #include "amv_qns_plan.h"
 #include "amv_rate_plan.h"
 #include "amv_requant_plan.h"
+#include "amv_retable_plan.h"
 #include "amv_trellis_plan.h"
 
 namespace amv {
@@ -67,6 +68,8 @@ struct amvhip_ctx {
     DevBuf clip_ws;
     // the requant entries: a flag per frame (a block out of range); the probe entry's statuses, which it does not hand out
     DevBuf requant_flags, requant_status;
+    // the re-table entries: the call's source tables, uint8 [count][2][64]
+    DevBuf retable_tables;
     // the shim around the rescaler: the source as YUV420P, the rescaled YUV420P ahead of a last conversion, the decoder's planes
     DevBuf pix_in, pix_out, pix_dec;
     // the video front end: the deinterlaced (and cropped) source ahead of the shim

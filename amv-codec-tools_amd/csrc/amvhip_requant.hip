@@ -1,6 +1,7 @@
 // amvhip_requant.hip -- AMV chunks requantised in the coefficient domain behind the C ABI: chunks in, chunks out, no pixel in
 // between.  The decoder's entropy stage (amvhip_decode.hip: entropy_records, amv_huffman_kernel) in front, amv_requant.hip in
-// the place of the encoder's front half, the encoder's coder, choice and compaction behind it.
+// the place of the encoder's front half, the encoder's coder, choice and compaction behind it.  The re-table entries are the
+// same four bodies with amv_retable.hip in amv_requant.hip's place: chunks written against foreign tables, made AMV's.
 #include "amvhip_ctx.h"
 
 using namespace amv;
@@ -62,19 +63,44 @@ struct Front {
     Fallback fb;
     uint32_t round;
     int16_t* coef;
+    RetableTables rt;             // the re-table entries: the call's tables on the device (tables nullptr: a requant entry)
 };
+
+// The four entries come in two forms, requant and re-table (amv_retable_plan.h): one body each, `rt` the re-table form's
+// argument and nullptr for the requant form.  What the re-table form asks beyond its sibling:
+struct Retable {
+    const amvhip_retable* rt;
+    bool wanted;
+};
+constexpr Retable kNoRetable{nullptr, false};
+int retable_args_ok(amvhip_ctx* c, const Retable& t) {
+    if (!t.wanted) return AMVHIP_OK;
+    const amvhip_retable* rt = t.rt;
+    if (!rt || !rt->tables) return fail(c, AMVHIP_ERR_ARG, "retable: the request or its tables are null");
+    if (rt->count == 0u || rt->count > kRetableTablesMax) return fail(c, AMVHIP_ERR_ARG, "retable: a request has 1 .. %u tables", kRetableTablesMax);
+    for (uint32_t i = 0; i < rt->count * kRetableTableBytes; ++i)
+        if (rt->tables[i] == 0u)
+            return fail(c, AMVHIP_ERR_ARG, "retable: table %u has a step of 0 (component %u, scan position %u)", i / kRetableTableBytes, i / 64u % 2u,
+                        i % 64u);
+    return AMVHIP_OK;
+}
 
 // The entropy stage of a call and its workspace (the context is locked).  A round is a multiple of a wave's 64 frames unless
 // it is the whole batch: amv_huffman_kernel's last wave of a round takes whole waves of items.
 int front_of(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n,
-             const FrameGeom& g, int32_t* d_status, hipStream_t st, Front* f) {
+             const FrameGeom& g, int32_t* d_status, hipStream_t st, const Retable& t, Front* f) {
     uint32_t round = fallback_round(n, g, 1024u, 2u);
     if (round < n) round = round >= 128u ? round & ~63u : 64u;
     if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
     if (int r = ensure(c, c->set[0].nmcu, (size_t)n * 4)) return r;
     if (int r = ensure(c, c->requant_flags, (size_t)n * 4)) return r;
     *f = Front{d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, (uint32_t*)c->set[0].nmcu.p, (uint32_t*)c->requant_flags.p, SyncSinks{},
-               Fallback{}, round, (int16_t*)c->coef.p};
+               Fallback{}, round, (int16_t*)c->coef.p, RetableTables{nullptr, 0u, nullptr}};
+    if (t.wanted) {
+        const size_t bytes = (size_t)t.rt->count * kRetableTableBytes;
+        if (int r = stage(c, c->retable_tables, bytes, t.rt->tables, bytes, st)) return r;
+        f->rt = RetableTables{(const uint8_t*)c->retable_tables.p, t.rt->count, t.rt->d_table_of};
+    }
     HIP_TRY(c, hipMemsetAsync(f->flags, 0, (size_t)n * 4, st));
     return entropy_records(c, d_blob, blob_bytes, d_offs, d_lens, n, g, false, d_status, f->nmcu, c->set[0], st, f->sinks, f->fb);
 }
@@ -122,7 +148,8 @@ int code_round(amvhip_ctx* c, const Front& f, const FrameSel& sel, uint32_t item
                const uint32_t* lambdas, uint64_t* d_err, uint32_t bound, uint32_t* d_lens, hipStream_t st) {
     {
         Timed t(c, AMVHIP_K_FDCT, st);
-        launch_requant(f.coef, f.n, sel, items, f.g, src, lambda, lambdas, f.flags, d_err, st);
+        if (f.rt.tables) launch_retable(f.coef, f.n, sel, items, f.g, src, f.rt, lambda, lambdas, f.flags, d_err, st);
+        else launch_requant(f.coef, f.n, sel, items, f.g, src, lambda, lambdas, f.flags, d_err, st);
     }
     {
         Timed t(c, AMVHIP_K_PACK_SERIAL, st);
@@ -142,7 +169,8 @@ int probe_pass(amvhip_ctx* c, const Front& f, const RateLadder& ladder, const Ra
     int16_t* const dc = (int16_t*)((uint8_t*)c->rate_ws.p + plan.dc);
     if (int r = each_round(c, f, st, [&](const FrameSel& sel, uint32_t items, const RequantSource& src) {
             Timed t(c, AMVHIP_K_FDCT, st);
-            launch_requant_probe(f.coef, f.n, sel, items, f.g, src, ladder, f.flags, dc, bits, st);
+            if (f.rt.tables) launch_retable_probe(f.coef, f.n, sel, items, f.g, src, f.rt, ladder, f.flags, dc, bits, st);
+            else launch_requant_probe(f.coef, f.n, sel, items, f.g, src, ladder, f.flags, dc, bits, st);
             return check_launch(c, "requant: probe");
         }))
         return r;
@@ -151,16 +179,22 @@ int probe_pass(amvhip_ctx* c, const Front& f, const RateLadder& ladder, const Ra
     return check_launch(c, "requant: probe (dc)");
 }
 
-}  // namespace
+// what every entry ends its frames' records with (each pointer where the entry has it)
+int finish(amvhip_ctx* c, const Front& f, uint32_t* d_lens, uint64_t* d_err, uint32_t* d_rung, uint32_t* d_bits, uint32_t rungs, hipStream_t st) {
+    launch_requant_finish(f.n, f.g, f.status, f.nmcu, f.flags, d_lens, d_err, d_rung, d_bits, rungs, st);
+    if (f.rt.tables) launch_retable_status(f.n, f.status, f.flags, st);
+    return check_launch(c, "requant: finish");
+}
 
-extern "C" int amvhip_requant_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
+int stream_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
                                          uint32_t n, uint32_t w, uint32_t h, uint32_t lambda, uint8_t* d_out, uint64_t out_cap,
-                                         uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status, uint64_t* d_err, void* stream) {
+                                         uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status, uint64_t* d_err, void* stream, const Retable& t) {
     if (!c) return AMVHIP_ERR_ARG;
     if (int r = requant_args_ok(c, d_blob, d_offs, d_lens, n, w, h, d_status)) return r;
     if (int r = requant_outputs_ok(c, n, d_out, d_out_offs, d_out_lens)) return r;
     if ((uintptr_t)d_err & 7u) return fail(c, AMVHIP_ERR_ARG, "requant: d_err is not 8-byte aligned");
     if (int r = requant_lambda_ok(c, lambda)) return r;
+    if (int r = retable_args_ok(c, t)) return r;
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -170,25 +204,25 @@ extern "C" int amvhip_requant_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, u
     if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
     if (int r = ensure(c, c->flag, 16)) return r;
     Front f;
-    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, &f)) return r;
+    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, t, &f)) return r;
     if (d_err) HIP_TRY(c, hipMemsetAsync(d_err, 0, (size_t)n * 24u, st));
     if (int r = each_round(c, f, st, [&](const FrameSel& sel, uint32_t items, const RequantSource& src) {
             return code_round(c, f, sel, items, src, lambda, nullptr, d_err, bound, d_out_lens, st);
         }))
         return r;
-    launch_requant_finish(n, g, d_status, f.nmcu, f.flags, d_out_lens, d_err, nullptr, nullptr, 0u, st);
-    if (int r = check_launch(c, "requant: finish")) return r;
+    if (int r = finish(c, f, d_out_lens, d_err, nullptr, nullptr, 0u, st)) return r;
     return compact(c, n, bound, d_out_lens, d_out_offs, d_out, out_cap, st);
 }
 
-extern "C" int amvhip_requant_rate_probe_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+int probe_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
                                              const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const uint32_t* ladder, uint32_t rungs,
-                                             uint32_t* d_bits, void* stream) {
+                                             uint32_t* d_bits, void* stream, const Retable& t) {
     if (!c) return AMVHIP_ERR_ARG;
     RateLadder lad;
     if (int r = requant_ladder_of(c, ladder, rungs, &lad)) return r;
     if (int r = requant_args_ok(c, d_blob, d_offs, d_lens, n, w, h, nullptr, false)) return r;
     if (int r = requant_rate_size_ok(c, n, w, h, d_bits)) return r;
+    if (int r = retable_args_ok(c, t)) return r;
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -199,21 +233,20 @@ extern "C" int amvhip_requant_rate_probe_dev(amvhip_ctx* c, const uint8_t* d_blo
     if (int r = ensure(c, c->requant_status, (size_t)n * 4)) return r;    // the entry hands out no statuses: a zero row says `not coded`
     int32_t* const d_status = (int32_t*)c->requant_status.p;
     Front f;
-    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, &f)) return r;
+    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, t, &f)) return r;
     HIP_TRY(c, hipMemsetAsync(d_bits, 0, (size_t)n * rungs * 4u, st));
     if (int r = probe_pass(c, f, lad, plan, d_bits, st)) return r;
-    launch_requant_finish(n, g, d_status, f.nmcu, f.flags, nullptr, nullptr, nullptr, d_bits, rungs, st);
-    return check_launch(c, "requant: finish");
+    return finish(c, f, nullptr, nullptr, nullptr, d_bits, rungs, st);
 }
 
 // amv_encode_rate.hip's flow (amvhip_encode.hip: rate_core) with the chunks' levels as the source: the probe over every frame,
 // the choice, a first pass at the frames' lambdas, the check, and up to rungs - 1 redo passes over device-built lists.  A redo
 // pass takes its frames' lines from the serial kernel, whichever kernel decoded them first: it decodes any frame of the call
 // into any slot, and a list names few.
-extern "C" int amvhip_requant_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+int rate_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
                                               const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_rate* rate, uint8_t* d_out,
                                               uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status, uint32_t* d_rung,
-                                              void* stream) {
+                                              void* stream, const Retable& t) {
     if (!c) return AMVHIP_ERR_ARG;
     if (!rate) return fail(c, AMVHIP_ERR_ARG, "requant_rate: the rate request or its ladder is null");
     RateLadder lad;
@@ -222,6 +255,7 @@ extern "C" int amvhip_requant_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_bl
     if (int r = requant_args_ok(c, d_blob, d_offs, d_lens, n, w, h, d_status)) return r;
     if (int r = requant_outputs_ok(c, n, d_out, d_out_offs, d_out_lens)) return r;
     if (int r = requant_rate_size_ok(c, n, w, h, d_rung)) return r;
+    if (int r = retable_args_ok(c, t)) return r;
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -238,7 +272,7 @@ extern "C" int amvhip_requant_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_bl
     uint32_t* const lambda = (uint32_t*)(ws + plan.lambda);
     uint32_t* const lists[2] = {(uint32_t*)(ws + plan.list[0]), (uint32_t*)(ws + plan.list[1])};
     Front f;
-    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, &f)) return r;
+    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, t, &f)) return r;
     HIP_TRY(c, hipMemsetAsync(ws + plan.zero, 0, plan.zero_bytes, st));
     if (int r = probe_pass(c, f, lad, plan, bits, st)) return r;
     launch_rate_choose(bits, lad, rate->d_budget, rate->budget, n, d_rung, lambda, st);
@@ -261,18 +295,17 @@ extern "C" int amvhip_requant_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_bl
                           st);
         if (int r = check_launch(c, "requant_rate: redo pass")) return r;
     }
-    launch_requant_finish(n, g, d_status, f.nmcu, f.flags, d_out_lens, nullptr, d_rung, nullptr, rungs, st);
-    if (int r = check_launch(c, "requant: finish")) return r;
+    if (int r = finish(c, f, d_out_lens, nullptr, d_rung, nullptr, rungs, st)) return r;
     return compact(c, n, bound, d_out_lens, d_out_offs, d_out, out_cap, st);
 }
 
 // amvhip_requant_rate_stream_dev's flow with the choice per clip above the choice per frame (amvhip_encode.hip: clip_core;
 // amv_clip_plan.h): the probe, the floor sums and the start over the frames that are coded, the first pass, and behind every
 // check the settle; clip_passes_most - 1 redo passes.  A frame that is not coded adds nothing to a sum.
-extern "C" int amvhip_requant_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+int clip_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
                                               const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_rate* rate, uint64_t total,
                                               uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status,
-                                              uint32_t* d_rung, uint64_t* d_clip, void* stream) {
+                                              uint32_t* d_rung, uint64_t* d_clip, void* stream, const Retable& t) {
     if (!c) return AMVHIP_ERR_ARG;
     if (!rate) return fail(c, AMVHIP_ERR_ARG, "requant_rate: the rate request or its ladder is null");
     RateLadder lad;
@@ -282,6 +315,7 @@ extern "C" int amvhip_requant_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_bl
     if (int r = requant_outputs_ok(c, n, d_out, d_out_offs, d_out_lens)) return r;
     if (int r = requant_rate_size_ok(c, n, w, h, d_rung)) return r;
     if (int r = clip_args_ok(c, n, d_clip)) return r;
+    if (int r = retable_args_ok(c, t)) return r;
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
@@ -303,7 +337,7 @@ extern "C" int amvhip_requant_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_bl
     uint32_t* const lambda = (uint32_t*)(ws + plan.lambda);
     uint32_t* const lists[2] = {(uint32_t*)(ws + plan.list[0]), (uint32_t*)(ws + plan.list[1])};
     Front f;
-    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, &f)) return r;
+    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, t, &f)) return r;
     HIP_TRY(c, hipMemsetAsync(ws + plan.zero, 0, plan.zero_bytes, st));
     HIP_TRY(c, hipMemsetAsync(cws, 0, cplan.bytes, st));
     if (int r = probe_pass(c, f, lad, plan, bits, st)) return r;
@@ -334,7 +368,64 @@ extern "C" int amvhip_requant_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_bl
                            counters + pass + 1u, d_clip, st);
         if (int r = check_launch(c, "requant_clip: redo pass")) return r;
     }
-    launch_requant_finish(n, g, d_status, f.nmcu, f.flags, d_out_lens, nullptr, d_rung, nullptr, rungs, st);
-    if (int r = check_launch(c, "requant: finish")) return r;
+    if (int r = finish(c, f, d_out_lens, nullptr, d_rung, nullptr, rungs, st)) return r;
     return compact(c, n, bound, d_out_lens, d_out_offs, d_out, out_cap, st);
+}
+
+}  // namespace
+
+extern "C" int amvhip_requant_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
+                                         uint32_t n, uint32_t w, uint32_t h, uint32_t lambda, uint8_t* d_out, uint64_t out_cap,
+                                         uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status, uint64_t* d_err, void* stream) {
+    return stream_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, lambda, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_err, stream, kNoRetable);
+}
+extern "C" int amvhip_requant_rate_probe_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                             const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const uint32_t* ladder, uint32_t rungs,
+                                             uint32_t* d_bits, void* stream) {
+    return probe_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, ladder, rungs, d_bits, stream, kNoRetable);
+}
+extern "C" int amvhip_requant_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                              const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_rate* rate, uint8_t* d_out,
+                                              uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status, uint32_t* d_rung,
+                                              void* stream) {
+    return rate_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, stream, kNoRetable);
+}
+extern "C" int amvhip_requant_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                              const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_rate* rate, uint64_t total,
+                                              uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status,
+                                              uint32_t* d_rung, uint64_t* d_clip, void* stream) {
+    return clip_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, total, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, d_clip, stream,
+                     kNoRetable);
+}
+
+// ---- the re-table form: the siblings above with the tables the chunks were written against behind `height` ----------------------
+extern "C" int amvhip_retable_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
+                                         uint32_t n, uint32_t w, uint32_t h, const amvhip_retable* rt, uint32_t lambda, uint8_t* d_out,
+                                         uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status, uint64_t* d_err,
+                                         void* stream) {
+    return stream_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, lambda, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_err, stream,
+                       Retable{rt, true});
+}
+extern "C" int amvhip_retable_rate_probe_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                             const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_retable* rt,
+                                             const uint32_t* ladder, uint32_t rungs, uint32_t* d_bits, void* stream) {
+    return probe_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, ladder, rungs, d_bits, stream, Retable{rt, true});
+}
+extern "C" int amvhip_retable_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                              const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_retable* rt,
+                                              const amvhip_rate* rate, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens,
+                                              int32_t* d_status, uint32_t* d_rung, void* stream) {
+    return rate_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, stream,
+                     Retable{rt, true});
+}
+extern "C" int amvhip_retable_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
+                                              const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_retable* rt,
+                                              const amvhip_rate* rate, uint64_t total, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offs,
+                                              uint32_t* d_out_lens, int32_t* d_status, uint32_t* d_rung, uint64_t* d_clip, void* stream) {
+    return clip_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, total, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, d_clip, stream,
+                     Retable{rt, true});
+}
+
+extern "C" int amvhip_ffmpeg_amv_tables(uint32_t qscale, uint8_t tables[2][64]) {
+    return retable_ffmpeg_amv_tables(qscale, tables) ? AMVHIP_OK : AMVHIP_ERR_ARG;
 }

@@ -1016,6 +1016,71 @@ int amvhip_requant_clip_stream_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint6
                                    uint64_t total, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offs, uint32_t *d_out_lens,
                                    int32_t *d_status, uint32_t *d_rung, uint64_t *d_clip, void *stream);
 /*
+ * Re-table: chunks whose levels were written against quantiser tables that are not AMV's, made AMV's (device-pointer forms
+ * only): chunks in, chunks out, and no pixel in between.
+ *
+ * Every AMV decoder dequantises with AMV's fixed tables Qd.  The reference's own amv encoder quantises with
+ * clip8(ff_mpeg1_default_intra_matrix[i] * qscale >> 3), entry 0 = 8, one matrix for luma and chroma
+ * (mpegvideo_enc.c:2866-2877): its files MEAN level * Qs and are READ as level * Qd.  The rule (csrc/amv_retable_plan.h), per
+ * frame whose entropy decode is clean, over its lines of levels in scan order as amvhip_huffman_decode_dev hands them out,
+ * with Qs the frame's source table:
+ *   1. DC: the new level is level * Qs[0] / Qd[0], rounded to nearest, halves away from zero (Qs[0] 9 against 8: level 4 is
+ *      36 / 8 and comes out as 5); with Qs[0] == Qd[0] the level is carried unchanged;
+ *   2. AC: c[k] = level[k] * 8 Qs[k] is searched as amvhip_requant_stream_dev searches level * 8 Qd: against AMV's tables, the
+ *      rounding term one half, the caller's lambda.  At lambda = 0 every position comes back within half an AMV step of what
+ *      the chunk meant: |new * 8 Qd - c| <= 4 Qd + 1;
+ *   3. the lines are coded by the entropy coder of every encoder entry.
+ * With source tables equal to AMV's the entries are their requant siblings (but for the range rule's cap, below).
+ * A frame is coded only if its entropy decode reports nothing, reaches the last MCU, its table index names a table, and every
+ * block is in range: |level| * 8 Qs <= 8193 per AC coefficient (what the search's fits are proved for with arbitrary
+ * coefficients; requant's 8681 rests on multiples of 8 Qd), the sum of (level * 8 Qs)^2 over a block's AC coefficients <= 2^30,
+ * |NEW DC level| <= 1023.  Otherwise d_status[i] is not zero -- the decode's AMVHIP_ST_* bits, AMVHIP_ST_RANGE, or
+ * AMVHIP_ST_TABLE -- d_out_lens[i] is 0 and nothing is written for the frame.
+ *
+ * amvhip_retable: tables = HOST memory, uint8 [count][2][64], luma then chroma, scan order, every entry 1 .. 255; copied
+ * during the call by a hipMemcpyAsync queued on `stream` into the context's workspace (that call's rules say when the memory
+ * is the caller's again: pageable memory at return, pinned memory once the stream has reached the copy).  count 1 ..
+ * AMVHIP_RETABLE_TABLES_MAX.  d_table_of: NULL = table 0 for every frame, else uint8 [n] on the device, frame i's table (the
+ * reference's default rate-controlled runs vary qscale per frame: the q= column of its -vstats log).
+ *
+ * The four entries are amvhip_requant_stream_dev, _rate_probe_dev, _rate_stream_dev and _clip_stream_dev with `rt` behind
+ * height; every other argument, the definitions of rate and clip, d_bits, d_rung and d_clip are the siblings' word for word,
+ * with amvhip_retable_stream_dev in amvhip_requant_stream_dev's place.  d_err: entry p of frame i = the sum over ALL 64
+ * positions (the DC included) of the blocks of plane p of (new * Qd - old * Qs)^2 -- by Parseval the unclipped pixel error
+ * between what the chunk meant and what the new chunk decodes to.
+ * AMVHIP_ERR_ARG with nothing queued: whatever the sibling refuses; rt or rt->tables NULL; count 0 or above the maximum; a
+ * table entry of 0.
+ *
+ * amvhip_ffmpeg_amv_tables: the reference encoder's tables at -qscale `qscale` (1 .. 31) in scan order, host arithmetic, no
+ * context.  Returns AMVHIP_OK, or AMVHIP_ERR_ARG for a qscale outside 1 .. 31, for which nothing is written.
+ * Not here: decoding WITH a caller's tables, the 4:2:2 scans of the reference's encoder, MJPEG (unflipped) sources, host-buffer
+ * forms, the plugin.
+ */
+#define AMVHIP_RETABLE_TABLES_MAX 64
+#define AMVHIP_ST_TABLE 0x10u  /* 16: retable: d_table_of[i] >= count, the frame is not coded */
+typedef struct amvhip_retable {
+    const uint8_t *tables;      /* host: [count][2][64], luma then chroma, scan order, entries 1..255 */
+    uint32_t count;             /* 1 .. AMVHIP_RETABLE_TABLES_MAX */
+    const uint8_t *d_table_of;  /* device: NULL = table 0 for every frame, else uint8 [n] */
+} amvhip_retable;
+int amvhip_retable_stream_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_offs,
+                              const uint32_t *d_lens, uint32_t n, uint32_t width, uint32_t height, const amvhip_retable *rt,
+                              uint32_t lambda, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offs, uint32_t *d_out_lens,
+                              int32_t *d_status, uint64_t *d_err, void *stream);
+int amvhip_retable_rate_probe_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_offs,
+                                  const uint32_t *d_lens, uint32_t n, uint32_t width, uint32_t height, const amvhip_retable *rt,
+                                  const uint32_t *ladder, uint32_t rungs, uint32_t *d_bits, void *stream);
+int amvhip_retable_rate_stream_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_offs,
+                                   const uint32_t *d_lens, uint32_t n, uint32_t width, uint32_t height, const amvhip_retable *rt,
+                                   const amvhip_rate *rate, uint8_t *d_out, uint64_t out_cap, uint64_t *d_out_offs,
+                                   uint32_t *d_out_lens, int32_t *d_status, uint32_t *d_rung, void *stream);
+int amvhip_retable_clip_stream_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes, const uint64_t *d_offs,
+                                   const uint32_t *d_lens, uint32_t n, uint32_t width, uint32_t height, const amvhip_retable *rt,
+                                   const amvhip_rate *rate, uint64_t total, uint8_t *d_out, uint64_t out_cap,
+                                   uint64_t *d_out_offs, uint32_t *d_out_lens, int32_t *d_status, uint32_t *d_rung,
+                                   uint64_t *d_clip, void *stream);
+int amvhip_ffmpeg_amv_tables(uint32_t qscale, uint8_t tables[2][64]);
+/*
  * Decoder + back end in one call: the patched FFmpeg's amv decoder (AMVHIP_FLAG_FFMPEG, required: AMVHIP_ERR_ARG without)
  * into workspace planes, then img_convert YUVJ420P -> dst_fmt (yuvj420p_to_*, imgconvert.c:1977-1993; the planar route for
  * YUV420P; the gray route for GRAY8): what `ffmpeg -i x.amv [-pix_fmt rgb24|bgr24|rgb32|rgb565] out` hands its next stage

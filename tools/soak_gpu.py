@@ -28,6 +28,12 @@ line per mismatch and a summary, and exits non-zero if anything differed.
                  of the chunks damaged -- a flipped byte, a cut, junk behind the scan -- one lambda from 0 to the bound and a
                  ladder of 1 .. 6 rungs in any order with budgets drawn per frame around the model's own lengths, in both
                  entropy modes: chunks, offsets, d_status, d_err, d_bits and d_rung against tests/requant_ref.py.
+  retable LO HI  the re-table entries on seeded 48x32-or-smaller pictures coded as the reference's encoder codes them
+                 (tests/retable_ref.reference_chunks) at a qscale drawn per frame, and on the oracle's synthetic chunks read against
+                 seeded tables of steps 1 .. 40: 1 .. 4 tables a call named by d_table_of (a bad index among them every fourth
+                 seed), a fifth of the chunks cut, one lambda from 0 to the bound, a ladder of 1 .. 5 rungs with budgets per
+                 frame around the model's lengths and a total around its sums, in both entropy modes: chunks, offsets, d_status,
+                 d_err, d_bits, d_rung and d_clip against tests/retable_ref.py.
   clip LO HI     the clip entries on soak_rate's geometries, ladders, -nr states and budgets per frame (a third without a cap),
                  every fifth seed through the requant entry on chunks of which a quarter are cut; the total drawn around the
                  model's own S(c) and F(c), 0 and 2^64 - 1 among them (so that clips stay, move after coding, pass rungs on their
@@ -462,6 +468,92 @@ def soak_requant(pkg, orc, lo, hi):
     return bad
 
 
+def soak_retable(pkg, orc, lo, hi):
+    import torch
+    import clip_ref as C
+    import retable_ref as RT
+    import test_gpu_parity as T
+    ctx = pkg.Context(0)
+    bad = frames_seen = not_coded = bad_index = 0
+    for seed in range(lo, hi):
+        rng = np.random.default_rng(seed)
+        n = int(rng.integers(1, 7))
+        count = int(rng.integers(1, 5))
+        table_of = [int(rng.integers(0, count)) for _ in range(n)]
+        if seed % 3:                                                        # the reference's encoder, a qscale per table
+            w, h = 16 * int(rng.integers(1, 4)), 16 * int(rng.integers(1, 3))
+            qscales = [int(rng.integers(1, 32)) for _ in range(count)]
+            tables = [RT.reference_tables(q) for q in qscales]
+            frames = RT.N.stream(w, h, [str(rng.choice(["ramp", "texture", "noise", "flat"])) for _ in range(n)], 5000 + seed)
+            chunks = [RT.reference_chunks([frames[i]], w, h, qscales[table_of[i]])[0] for i in range(n)]
+        else:                                                               # the oracle's chunks read against seeded tables
+            w, h = int(rng.integers(1, 60)), int(rng.integers(1, 50))
+            tables = [[[int(x) for x in rng.integers(1, 41, 64)] for _ in range(2)] for _ in range(count)]
+            chunks = RT.Q.synth_chunks(w + (w & 1), h + (h & 1), n, seed=SEED + seed)
+        for i in range(n):
+            if rng.integers(0, 5) == 0:
+                chunks[i] = chunks[i][: int(rng.integers(2, len(chunks[i])))]
+        if seed % 4 == 0:
+            table_of[int(rng.integers(0, n))] = count + int(rng.integers(0, 200))
+        d_table_of = None if count == 1 and seed % 4 else T._t(np.array(table_of, np.uint8))
+        if d_table_of is None:
+            table_of = None
+        lam = int(rng.choice([0, 200, 3481, 20000, RT.LAMBDA_MAX, int(rng.integers(0, RT.LAMBDA_MAX + 1))]))
+        rungs = int(rng.integers(1, 6))
+        ladder = sorted(int(rng.choice([0, 1000, 3481, 20000, RT.LAMBDA_MAX, int(rng.integers(0, 60000))])) for _ in range(rungs))
+        want, status, err = RT.retable(chunks, w, h, tables, table_of, lam)
+        bits = RT.bits_table(chunks, w, h, tables, table_of, ladder)
+        lens, coded = RT.clip_lens(chunks, w, h, tables, table_of, ladder)
+        B = [max(0, int(rng.choice([lens[i][int(rng.integers(0, rungs))], lens[i][int(rng.integers(0, rungs))] - 1, 7, 0xFFFFFFFF]))) for i in range(n)]
+        want_rate, _, want_rungs = RT.rate(chunks, w, h, tables, table_of, ladder, B)
+        S = C.sums(lens, B, coded)
+        total = max(0, int(rng.choice(S)) - int(rng.integers(0, 2)))
+        want_clip = RT.clip(chunks, w, h, tables, table_of, ladder, B, total)
+        frames_seen += n
+        not_coded += sum(1 for x in status if x)
+        bad_index += sum(1 for x in status if x == RT.ST_TABLE)
+        blob, offs, lens_in = RT.Q.pack(chunks)
+        ins = (T._t(blob), int(lens_in.sum()), T._t(offs), T._t(lens_in), n, w, h)
+        cap = 4 * sum(len(c) for c in chunks) + 64 * n + 64
+
+        def same(d_blob, d_offs, d_lens, chunks_want):
+            got, o, ln = d_blob.cpu().numpy(), d_offs.cpu().numpy(), d_lens.cpu().numpy()
+            pos = 0
+            for i, c in enumerate(chunks_want):
+                size = len(c) if c else 0
+                if (int(o[i]), int(ln[i])) != (pos, size) or (size and got[pos: pos + size].tobytes() != c):
+                    return False
+                pos += size
+            return True
+
+        for mode in (pkg.ENTROPY_AUTO, pkg.ENTROPY_SERIAL):
+            ctx.set_entropy_mode(mode)
+            outs = [(torch.zeros(cap, dtype=torch.uint8, device="cuda:0"), torch.zeros(n, dtype=torch.int64, device="cuda:0"),
+                     torch.zeros(n, dtype=torch.int32, device="cuda:0"), torch.full((n,), -1, dtype=torch.int32, device="cuda:0")) for _ in range(3)]
+            d_err = torch.full((n, 3), -1, dtype=torch.int64, device="cuda:0")
+            d_bits = torch.full((n, rungs), -1, dtype=torch.int32, device="cuda:0")
+            d_rung = [torch.full((n,), -1, dtype=torch.int32, device="cuda:0") for _ in range(2)]
+            d_clip = torch.full((2,), -1, dtype=torch.int64, device="cuda:0")
+            rt = pkg.Retable(tables, d_table_of)
+            rate = pkg.Rate(ladder, budget=1, d_budget=T._t(np.array(B, np.uint32)))
+            ctx.retable_stream_dev(*ins, rt, lam, outs[0][0], cap, *outs[0][1:], d_err)
+            ctx.retable_rate_probe_dev(*ins, rt, ladder, d_bits)
+            ctx.retable_rate_stream_dev(*ins, rt, rate, outs[1][0], cap, *outs[1][1:], d_rung[0])
+            ctx.retable_clip_stream_dev(*ins, rt, rate, total, outs[2][0], cap, *outs[2][1:], d_rung[1], d_clip)
+            torch.cuda.synchronize()
+            ok = same(*outs[0][:3], want) and same(*outs[1][:3], want_rate) and same(*outs[2][:3], want_clip[0]) and d_err.cpu().numpy().tolist() == err
+            ok = ok and all(o[3].cpu().numpy().tolist() == status for o in outs)
+            ok = ok and (d_bits.cpu().numpy().view(np.uint32) == bits).all() and d_rung[0].cpu().numpy().view(np.uint32).tolist() == want_rungs
+            ok = ok and d_rung[1].cpu().numpy().view(np.uint32).tolist() == want_clip[2] and d_clip.cpu().numpy().view(np.uint64).tolist() == list(want_clip[3])
+            if not ok:
+                bad += 1
+                print("MISMATCH retable seed", seed, w, h, n, "tables", count, table_of, "lambda", lam, "ladder", ladder, "budgets", B, "total", total,
+                      "status", status, "mode", mode, flush=True)
+        ctx.set_entropy_mode(pkg.ENTROPY_AUTO)
+    print("frames", frames_seen, "not coded", not_coded, "of them with a bad index", bad_index)
+    return bad
+
+
 def soak_clip(pkg, orc, lo, hi):
     import torch
     import clip_ref as C
@@ -567,14 +659,14 @@ def soak_clip(pkg, orc, lo, hi):
 
 
 def main():
-    if len(sys.argv) != 4 or sys.argv[1] not in ("adpcm", "decode", "ffmpeg", "encode", "trellis", "qns", "rate", "requant", "clip"):
+    if len(sys.argv) != 4 or sys.argv[1] not in ("adpcm", "decode", "ffmpeg", "encode", "trellis", "qns", "rate", "requant", "retable", "clip"):
         raise SystemExit(__doc__)
     what, lo, hi = sys.argv[1], int(sys.argv[2]), int(sys.argv[3])
     pkg = entry.build()
     orc = entry.load_oracle()
     orc.lib()
     bad = {"adpcm": soak_adpcm, "decode": soak_decode, "ffmpeg": soak_ffmpeg, "encode": soak_encode, "trellis": soak_trellis,
-           "qns": soak_qns, "rate": soak_rate, "requant": soak_requant, "clip": soak_clip}[what](pkg, orc, lo, hi)
+           "qns": soak_qns, "rate": soak_rate, "requant": soak_requant, "retable": soak_retable, "clip": soak_clip}[what](pkg, orc, lo, hi)
     print("soak", what, "seeds", lo, "..", hi - 1, "mismatches:", bad)
     sys.exit(1 if bad else 0)
 
