@@ -13,6 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "libamvoracle.so")
 REF = os.path.join(HERE, "_ref", "libamvref.so")
 AVCREF = os.path.join(HERE, "_ref", "libavcref.so")
+ARREF = os.path.join(HERE, "_ref", "libarref.so")     # the reference's audio resampler: the fixtures' producer only
+REF_SOURCES = ("ref_harness.c", "ref_harness_imgconvert.c", "ref_harness_audio.c", "Makefile")
 
 ST_FORMAT, ST_OVERRUN, ST_TRUNCATED = 1, 2, 4
 FLAG_ZIGZAG_FIXED = 1
@@ -35,7 +37,7 @@ def build(force=False):
     import fcntl
     want_lib = force or _stale(LIB, ("amv_oracle.c", "amv_oracle.h", "Makefile"))
     want_ref = os.path.isdir("/root/reference") and (force or not os.path.exists(REF) or
-                                                     _stale(AVCREF, ("ref_harness.c", "ref_harness_imgconvert.c", "Makefile")))
+                                                     _stale(AVCREF, REF_SOURCES) or _stale(ARREF, REF_SOURCES))
     if not (want_lib or want_ref):
         return
     with open(os.path.join(HERE, ".build.lock"), "w") as lock:
@@ -43,7 +45,7 @@ def build(force=False):
         if force or _stale(LIB, ("amv_oracle.c", "amv_oracle.h", "Makefile")):
             subprocess.run(["make", "-C", HERE, "-s", "libamvoracle.so"], check=True)
         if os.path.isdir("/root/reference") and (force or not os.path.exists(REF) or
-                                                 _stale(AVCREF, ("ref_harness.c", "ref_harness_imgconvert.c", "Makefile"))):
+                                                 _stale(AVCREF, REF_SOURCES) or _stale(ARREF, REF_SOURCES)):
             subprocess.run(["make", "-C", HERE, "-s", "ref"], check=True)
 
 

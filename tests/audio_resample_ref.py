@@ -96,16 +96,20 @@ def _bessel(x):
     return v
 
 
-@functools.lru_cache(maxsize=None)
-def _bank_rows(in_rate, out_rate):
-    factor = min(out_rate * CUTOFF / in_rate, 1.0)
-    fl = filter_length(in_rate, out_rate)
-    center = (fl - 1) // 2
-    if factor > 1.0:
-        factor = 1.0
-    scale = 1 << FILTER_SHIFT
-    rows = []
-    for ph in range(PHASES):
+class _Bank:
+    """the 1024 rows of one rate pair, each built when it is first asked for (a pair whose positions are periodic uses one
+    row, or a few: 192000 -> 1000 reads row 0 of 1024 rows of 3840 taps) and kept"""
+
+    def __init__(self, in_rate, out_rate):
+        self.factor = min(out_rate * CUTOFF / in_rate, 1.0)
+        self.fl = filter_length(in_rate, out_rate)
+        self.table = np.zeros((PHASES, self.fl), np.int16)
+        self.built = np.zeros(PHASES, bool)
+
+    def _row(self, ph):
+        factor, fl = self.factor, self.fl
+        center = (fl - 1) // 2
+        scale = 1 << FILTER_SHIFT
         tab, norm = [], 0.0
         for i in range(fl):
             x = math.pi * (float(i - center) - ph / PHASES) * factor
@@ -119,13 +123,24 @@ def _bank_rows(in_rate, out_rate):
         for y in tab:
             v = round(float(np.float32(y * scale / norm)))      # lrintf: to float, then to nearest, ties to even
             row.append(min(max(v, -32768), 32767))
-        rows.append(row)
-    return np.array(rows, np.int16)
+        return row
+
+    def rows(self, phases):
+        """the table, with (at least) the rows `phases` names built"""
+        for ph in np.unique(phases)[~self.built[np.unique(phases)]]:
+            self.table[ph] = self._row(int(ph))
+            self.built[ph] = True
+        return self.table
+
+
+@functools.lru_cache(maxsize=None)
+def _bank(in_rate, out_rate):
+    return _Bank(in_rate, out_rate)
 
 
 def filter_bank(in_rate, out_rate):
-    """1024 x fl int16 (the wrap row of resample2.c:194-195 serves the linear mode only)"""
-    return _bank_rows(in_rate, out_rate)
+    """1024 x fl int16, every row built (the wrap row of resample2.c:194-195 serves the linear mode only)"""
+    return _bank(in_rate, out_rate).rows(np.arange(PHASES))
 
 
 # ---- positions and counts ------------------------------------------------------------------------------------------------
@@ -183,10 +198,10 @@ def _wrap32(v):
 
 def filter_channel(x, in_rate, out_rate, I):
     """av_resample's sums for positions I over the channel x (the call's whole buffer: src_size = len(x))"""
-    bank = filter_bank(in_rate, out_rate)
-    fl = bank.shape[1]
     if len(I) == 0:
         return np.zeros(0, np.int16)
+    bank = _bank(in_rate, out_rate).rows(I & (PHASES - 1))       # the rows these positions read
+    fl = bank.shape[1]
     out, x64 = [], x.astype(np.int64)
     step = max(1, (1 << 21) // fl)                                 # rows per pass: bounded memory at any filter length
     for a in range(0, len(I), step):
