@@ -18,6 +18,9 @@ quantiser modes share the two functions:
 
 Both entropy-code with scan_builder.  Python ints do not wrap: the model is the reference wherever the reference's int
 arithmetic does not wrap, which is what the product's argument bound (amv_nr_plan.h) guarantees.
+
+frame_start, denoise_blocks and encode_stream take `faults` (faults_of): named wrong implementations, none by default, with
+which tests/test_nr_builder.py proves that the crafted corpus of tests/nr_builder.py would notice each of them.
 """
 import os
 import sys
@@ -55,24 +58,103 @@ def _cdiv(a, b):
     return np.where((a < 0) != (b < 0), -q, q)
 
 
-def frame_start(state, nr, truncate=True, halve=True):
+FAULTS = ("signed_offsets", "swapped_pair", "untransposed", "dead_zone_plus_1", "dead_zone_minus_1", "sign_lost", "dc_unshifted",
+          "dc_unclamped", "dc_sum_unshifted", "no_truncation", "no_halving", "halve_at_65536", "halve_rounds_up", "padding_not_summed",
+          "magnitude_pair_swapped")
+
+
+def faults_of(faults):
+    """Named faults: each one wrong implementation a kernel could plausibly be, for proving that a corpus would notice it
+    (tests/nr_builder.py).  `faults` is a collection of names, or a dict name -> where: dead_zone_plus_1 / dead_zone_minus_1
+    take (position, sign, component) -- row-major position, sign +1 / -1 of the coefficient, component 0 luma / 1 chroma --
+    to confine the fault to that one; None is everywhere.  -> dict.
+
+      signed_offsets      an offset of 32768 or more is taken as offset - 65536 (the halves of a word read as signed)
+      swapped_pair        the two offsets of one 32-bit word, as the column pass consumes them (entry c * 8 + r: rows r
+                          and r ^ 1 of a column), change places
+      untransposed        position r * 8 + c takes the offset of c * 8 + r
+      dead_zone_plus_1    abs(x) - offset + 1 (AC positions)
+      dead_zone_minus_1   abs(x) - offset - 1 (AC positions)
+      sign_lost           a negative output comes back positive
+      dc_unshifted        the DC is denoised as x, not as x + 8192
+      dc_unclamped        D - offset is not held at 0
+      dc_sum_unshifted    the DC sum takes abs(x)
+      no_truncation       the offset is not stored as uint16_t (truncate=False)
+      no_halving          no halving (halve=False)
+      halve_at_65536      halves at count >= 65536
+      halve_rounds_up     halves with (v + 1) >> 1
+      padding_not_summed  blocks wholly outside the picture do not enter sums or count
+      magnitude_pair_swapped  the fault chosen in how the sums kernel packs its 16-bit magnitudes: the two magnitudes of a
+                          32-bit word of the block's line (positions r * 8 + c and r * 8 + (c ^ 1)) change places on the way
+                          to the sums -- pack16's arguments the wrong way round, or the halves read in the other byte order
+    """
+    f = dict(faults) if isinstance(faults, dict) else {k: None for k in faults}
+    assert set(f) <= set(FAULTS), sorted(set(f) - set(FAULTS))
+    return f
+
+
+_I = np.arange(64)
+_TRANSPOSED = (_I % 8) * 8 + _I // 8
+_PAIR_IN_COLUMN = ((_I // 8) ^ 1) * 8 + _I % 8
+_PAIR_IN_ROW = _I ^ 1
+
+
+def frame_start(state, nr, truncate=True, halve=True, faults=()):
     """update_noise_reduction: halve sums and count when the count is above 65536, then the 64 offsets.  state changes in
-    place; truncate=False leaves out the uint16_t store, halve=False the halving (what the fixtures' maker tells apart)"""
-    if halve and state[64] > HALVE_ABOVE:
+    place; truncate=False leaves out the uint16_t store, halve=False the halving (what the fixtures' maker tells apart;
+    the faults no_truncation and no_halving are the same switches)"""
+    f = faults_of(faults)
+    truncate, halve = truncate and "no_truncation" not in f, halve and "no_halving" not in f
+    if halve and (state[64] >= HALVE_ABOVE if "halve_at_65536" in f else state[64] > HALVE_ABOVE):
+        if "halve_rounds_up" in f:
+            state[:] += 1
         state[:] >>= 1
     off = _cdiv(nr * state[64] + _cdiv(state[:64], np.int64(2)), state[:64] + 1)
     return off & 0xFFFF if truncate else off
 
 
-def denoise_blocks(state, offsets, coef, dc_shift=0):
-    """denoise_dct_c over the blocks of one frame (coef [B, 64] fdct outputs, row-major; position 0 is the reference's
-    when dc_shift is added): state changes in place, the denoised outputs come back"""
+def denoise_blocks(state, offsets, coef, dc_shift=0, faults=(), outside=None):
+    """denoise_dct_c over the blocks of one frame (coef [B, 64] fdct outputs, row-major, MCU order; position 0 is the
+    reference's when dc_shift is added): state changes in place, the denoised outputs come back.  outside: [B] bool, the
+    blocks wholly outside the picture (the fault padding_not_summed alone asks for it)"""
+    f = faults_of(faults)
     c = np.asarray(coef, np.int64).copy()
     c[:, 0] += dc_shift
     mag = np.abs(c)
-    state[:64] += mag.sum(axis=0)
-    state[64] += c.shape[0]
-    out = np.sign(c) * np.maximum(mag - offsets[None, :], 0)
+    summed = mag.copy()
+    if "dc_sum_unshifted" in f:
+        summed[:, 0] = np.abs(c[:, 0] - dc_shift)
+    if "magnitude_pair_swapped" in f:
+        summed = summed[:, _PAIR_IN_ROW]
+    if "padding_not_summed" in f:
+        summed = summed[~np.asarray(outside, bool)]
+    state[:64] += summed.sum(axis=0)
+    state[64] += summed.shape[0]
+    offsets = np.asarray(offsets, np.int64)
+    if "signed_offsets" in f:
+        offsets = np.where(offsets >= 32768, offsets - 65536, offsets)
+    if "swapped_pair" in f:
+        offsets = offsets[_PAIR_IN_COLUMN]
+    if "untransposed" in f:
+        offsets = offsets[_TRANSPOSED]
+    kept = mag - offsets[None, :]
+    for name, step in (("dead_zone_plus_1", 1), ("dead_zone_minus_1", -1)):
+        if name in f:
+            where = np.ones(c.shape, bool)
+            if f[name] is not None:
+                pos, sign, comp = f[name]
+                where[:] = False
+                where[:, pos] = (np.sign(c[:, pos]) == sign) & ((np.arange(c.shape[0]) % 6 >= 4) == bool(comp))
+            where[:, 0] = False
+            kept = kept + step * where
+    out = np.sign(c) * np.maximum(kept, 0)
+    if "sign_lost" in f:
+        out = np.abs(out)
+    if "dc_unclamped" in f:
+        out[:, 0] = kept[:, 0]
+    if "dc_unshifted" in f:
+        x = c[:, 0] - dc_shift
+        out[:, 0] = np.sign(x) * np.maximum(np.abs(x) - offsets[0], 0) + dc_shift
     out[:, 0] -= dc_shift
     return out
 
@@ -138,6 +220,18 @@ def frame_blocks(y, cb, cr, w, h, shift):
     return out.reshape(-1, 64)
 
 
+def outside_blocks(w, h):
+    """[blocks] bool, MCU order: the blocks wholly outside the picture (every sample a repeated edge sample)"""
+    mcw, mch = (w + 15) // 16, (h + 15) // 16
+    out = np.zeros((mch, mcw, 6), bool)
+    for my in range(mch):
+        for mx in range(mcw):
+            for k in range(4):
+                out[my, mx, k] = my * 16 + (k >> 1) * 8 >= h or mx * 16 + (k & 1) * 8 >= w
+            out[my, mx, 4:] = my * 8 >= h // 2 or mx * 8 >= w // 2
+    return out.reshape(-1)
+
+
 # ---- the two encoders ------------------------------------------------------------------------------------------------------
 
 def _chunk(zz):
@@ -164,18 +258,27 @@ def quantize_product(coef, qbias=0):
     return zz
 
 
-def encode_stream(frames, w, h, nr, state=None, mode="product", qbias=0, truncate=True, halve=True, want_coef=False):
+def _int16(coef):
+    """what the quantiser is handed: DCTELEM (only a faulty model's outputs ever leave it)"""
+    return _s16(np.asarray(coef, np.int64))
+
+
+def encode_stream(frames, w, h, nr, state=None, mode="product", qbias=0, truncate=True, halve=True, want_coef=False, faults=()):
     """frames: [(y, cb, cr)] planes of 2-D uint8 -> the chunks (or, want_coef, the zig-zag lines per frame); state (65
-    int64, new_state() when None) changes in place.  nr = 0 leaves it alone, as the reference allocates nothing then."""
+    int64, new_state() when None) changes in place.  nr = 0 leaves it alone, as the reference allocates nothing then.
+    faults: see faults_of; none by default"""
     if state is None:
         state = new_state()
     ref = mode == "reference"
+    outside = outside_blocks(w, h) if "padding_not_summed" in faults_of(faults) else None
     out = []
     for y, cb, cr in frames:
         coef = fdct(frame_blocks(y, cb, cr, w, h, 0 if ref else 128))
         if nr:
-            offsets = frame_start(state, nr, truncate, halve)
-            coef = denoise_blocks(state, offsets, coef, 0 if ref else DC_SHIFT)
+            offsets = frame_start(state, nr, truncate, halve, faults)
+            coef = denoise_blocks(state, offsets, coef, 0 if ref else DC_SHIFT, faults, outside)
+            if faults:
+                coef = _int16(coef)
         zz = quantize_reference(coef) if ref else quantize_product(coef, qbias)
         out.append(zz if want_coef else _chunk(zz))
     return out

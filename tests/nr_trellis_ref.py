@@ -25,17 +25,20 @@ import nr_ref as N
 import trellis_ref as T
 
 
-def encode_stream(frames, w, h, nr, lam, state=None, qbias=0, truncate=True, halve=True, want_coef=False):
+def encode_stream(frames, w, h, nr, lam, state=None, qbias=0, truncate=True, halve=True, want_coef=False, faults=()):
     """frames: [(y, cb, cr)] planes of 2-D uint8 -> the chunks (or, want_coef, the zig-zag lines per frame); state (65 int64,
     N.new_state() when None) changes in place.  nr = 0 leaves it alone and gives T.encode_frames.  truncate / halve: as in
-    N.frame_start"""
+    N.frame_start; faults: N.faults_of, handed on"""
     if state is None:
         state = N.new_state()
+    outside = N.outside_blocks(w, h) if "padding_not_summed" in N.faults_of(faults) else None
     out = []
     for y, cb, cr in frames:
         coef = N.fdct(N.frame_blocks(y, cb, cr, w, h, 128))
         if nr:
-            coef = N.denoise_blocks(state, N.frame_start(state, nr, truncate, halve), coef, N.DC_SHIFT)
+            coef = N.denoise_blocks(state, N.frame_start(state, nr, truncate, halve, faults), coef, N.DC_SHIFT, faults, outside)
+            if faults:
+                coef = N._int16(coef)
         zz = T.quantize_trellis(coef, qbias, lam)
         out.append(zz if want_coef else N._chunk(zz))
     return out
