@@ -186,6 +186,11 @@ SYMBOLS = {
     "amvhip_decode_lowres_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp]),
     "amvhip_decode_lowres_batch": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp]),
     "amvhip_reconstruct_lowres_dev": (_int, [_vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp]),
+    "amvhip_pp_mode_parse": (_int, [ctypes.c_char_p, _int, _vp]),
+    "amvhip_postprocess_supported": (_int, [_u32, _u32]),
+    "amvhip_postprocess_dev": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp, _vp]),
+    "amvhip_postprocess": (_int, [_vp, _int, _vp, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _vp, _vp, _vp, _u32, _u32, _u64, _u64, _u32, _u32, _u32, _vp]),
+    "amvhip_decode_pp_batch_dev": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _u32, _int, _vp, _u32, _vp, _vp, _vp, _vp]),
     "amvhip_audio_resample_out_samples": (_u64, [_u32, _u32, _u64]),
     "amvhip_audio_resample_batch_dev": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _u32, _vp]),
     "amvhip_audio_resample_batch": (_int, [_vp, _vp, _u64, _vp, _vp, _u32, _u32, _u32, _vp, _u64, _vp, _u32, _u32]),
@@ -257,6 +262,26 @@ def load_library():
 
 class AmvHipError(RuntimeError):
     pass
+
+
+PP_V_DEBLOCK, PP_H_DEBLOCK, PP_DERING, PP_FORCE_QUANT = 0x01, 0x02, 0x04, 0x200000
+
+
+class PpMode(ctypes.Structure):
+    """amvhip_pp_mode of include/amvhip.h: what amvhip_pp_mode_parse makes of a libpostproc mode string"""
+    _fields_ = [("lum_mode", ctypes.c_int32), ("chrom_mode", ctypes.c_int32), ("base_dc_diff", ctypes.c_int32),
+                ("flatness_threshold", ctypes.c_int32), ("forced_quant", ctypes.c_int32)]
+
+    def __init__(self, lum_mode=0, chrom_mode=0, base_dc_diff=32, flatness_threshold=39, forced_quant=0):
+        super().__init__(lum_mode, chrom_mode, base_dc_diff, flatness_threshold, forced_quant)
+
+
+def pp_mode_parse(name, quality=6):
+    """a libpostproc mode string (hb, vb, dr, fq, de and their options) -> PpMode; AmvHipError for anything else"""
+    mode = PpMode()
+    if load_library().amvhip_pp_mode_parse(name.encode(), quality, ctypes.byref(mode)) != OK:
+        raise AmvHipError("pp_mode_parse: %r is not a mode of hb, vb, dr, fq, de" % name)
+    return mode
 
 
 class Frontend(ctypes.Structure):
@@ -797,6 +822,22 @@ class Context:
 
     def lowres_frame_bytes(self, w, h, lowres):
         return self.lib.amvhip_lowres_frame_bytes(w, h, lowres)
+
+    # decode-side postprocessing (the reference's libpostproc: hb, vb, dr).  mode: a PpMode; src / dst: pictures as in deinterlace_dev
+    def postprocess_supported(self, w, h):
+        return self.lib.amvhip_postprocess_supported(w, h)
+
+    def postprocess_dev(self, fmt, mode, src, dst, w, h, n, qp=None, stream=None):
+        return self._check(self.lib.amvhip_postprocess_dev(self.h, fmt, ctypes.byref(mode), *self._pic(src), *self._pic(dst), w, h, n, _ptr(qp), stream),
+                           "postprocess_dev")
+
+    def postprocess(self, fmt, mode, src, dst, w, h, n, qp=None):
+        return self._check(self.lib.amvhip_postprocess(self.h, fmt, ctypes.byref(mode), *self._pic(src), *self._pic(dst), w, h, n, _ptr(qp)), "postprocess")
+
+    def decode_pp_batch_dev(self, blob, blob_bytes, offs, lens, n, w, h, flags, dst_fmt, out, out_stride, status, mode, qp=None, stream=None):
+        return self._check(self.lib.amvhip_decode_pp_batch_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, flags, dst_fmt,
+                                                               _ptr(out), out_stride, _ptr(status), ctypes.byref(mode), _ptr(qp), stream),
+                           "decode_pp_batch_dev")
 
     def decode_lowres_batch_dev(self, blob, blob_bytes, offs, lens, n, w, h, flags, lowres, dst_fmt, out, out_stride, status, stream=None):
         return self._check(self.lib.amvhip_decode_lowres_batch_dev(self.h, _ptr(blob), blob_bytes, _ptr(offs), _ptr(lens), n, w, h, flags,

@@ -371,6 +371,21 @@ struct DeintPlane {         // one plane: the window x0, y0, w, h of a source pl
 };
 struct DeintJobs { DeintPlane j[3]; uint32_t count; };
 void launch_deinterlace(const DeintJobs& jobs, uint32_t n, hipStream_t s);
+
+// ---- decode-side postprocessing (amv_postprocess.hip): the reference's hb / vb / dr on tight planes ------------------------
+struct PpPlaneJob {         // one plane of every frame: pitch = w on both sides; mode 0: the plane is copied
+    const uint8_t* src;
+    uint8_t* dst;
+    uint64_t sframe, dframe;
+    uint32_t w, h;
+    int mode;               // kPpVDeblock | kPpHDeblock | kPpDering of amv_pp_plan.h
+};
+struct PpJobs {
+    PpPlaneJob j[3];
+    int qp, base_dc_diff, flat_thr;
+    const uint8_t* d_qp;    // a QP per frame, or nullptr: qp for all
+};
+void launch_postprocess(const PpJobs& jobs, uint32_t n, hipStream_t s);
 struct PadBandPlane {       // one padded plane: geometry as PadPlane of amv_host_plan.h (the items are counted and placed there)
     uint8_t* dst;
     uint32_t stride;

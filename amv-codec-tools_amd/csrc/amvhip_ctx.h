@@ -1,7 +1,7 @@
 // amvhip_ctx.h -- the context behind the C ABI of include/amvhip.h, and what its files share (internal to libamvhip.so).
 //
 // The ABI is split by domain: amvhip_context.hip (context, timing, statistics), amvhip_decode.hip, amvhip_encode.hip
-// (encoders, picture rescale), amvhip_pixfmt.hip (img_convert, the sws_scale shim, the video front end) and amvhip_audio.hip (resampler, ADPCM).
+// (encoders, picture rescale), amvhip_pixfmt.hip (img_convert, the sws_scale shim, the video front end, the postprocessing) and amvhip_audio.hip (resampler, ADPCM).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -17,6 +17,7 @@
 #include "amv_host_plan.h"
 #include "amv_kernels.h"
 #include "amv_nr_plan.h"
+#include "amv_pp_plan.h"
 #include "amv_qns_plan.h"
 #include "amv_rate_plan.h"
 #include "amv_requant_plan.h"
@@ -74,6 +75,8 @@ struct amvhip_ctx {
     DevBuf pix_in, pix_out, pix_dec;
     // the video front end: the deinterlaced (and cropped) source ahead of the shim
     DevBuf fe_deint;
+    // amvhip_decode_pp_batch_dev: the postprocessed planes ahead of a conversion (the decoder's own are in pix_dec)
+    DevBuf pp_planes;
     // audio resampler: filter banks by (in_rate << 32 | out_rate), uploaded once and kept; the tile counts of the last call
     std::map<uint64_t, DevBuf> audio_banks;
     DevBuf audio_tiles;

@@ -1,5 +1,5 @@
 // amvhip_pixfmt.hip -- pixel formats behind the C ABI: img_convert, the sws_scale shim, the shim joined to the encoder and
-// the decoder, and the stages of ffmpeg's video front end around it (deinterlace, crop, pad).
+// the decoder, the stages of ffmpeg's video front end around it (deinterlace, crop, pad), and the decode-side postprocessing.
 #include "amvhip_ctx.h"
 
 using namespace amv;
@@ -734,4 +734,141 @@ extern "C" int amvhip_picture_sse(amvhip_ctx* c, int fmt, const uint8_t* a0, con
     HIP_TRY(c, hipMemcpyAsync(sse, c->h_out.p, (size_t)n * 24u, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));
     return AMVHIP_OK;
+}
+
+// ---- decode-side postprocessing: the reference's pp_postprocess for hb / vb / dr (amv_postprocess.hip, amv_pp_plan.h) -----
+namespace {
+
+// what the entries ask of mode, format and size; *qp: the QP of every frame that d_qp does not give
+int pp_args_ok(amvhip_ctx* c, const char* what, int fmt, const amvhip_pp_mode* m, uint32_t w, uint32_t h, int* qp) {
+    if (fmt != AMVHIP_PIX_YUV420P && fmt != AMVHIP_PIX_YUVJ420P) return fail(c, AMVHIP_ERR_ARG, "%s: format %d is not YUV420P / YUVJ420P", what, fmt);
+    if (!m) return fail(c, AMVHIP_ERR_ARG, "%s: mode is NULL", what);
+    if (!pp_mode_ok(m->lum_mode & ~kPpForceQuant) || !pp_mode_ok(m->chrom_mode & ~kPpForceQuant))
+        return fail(c, AMVHIP_ERR_ARG, "%s: mode bits beyond hb, vb, dr, or dr without vb (its output is no function of the picture)", what);
+    const bool forced = m->lum_mode & kPpForceQuant;
+    if (forced && (m->forced_quant < 0 || m->forced_quant > 63)) return fail(c, AMVHIP_ERR_ARG, "%s: forced QP %d outside 0 .. 63", what, m->forced_quant);
+    if (!pp_size_ok(w, h))
+        return fail(c, AMVHIP_ERR_ARG, "%s: %ux%u is not taken (widths multiples of 16, even heights, 16x16 .. %ux%u)", what, w, h, kPpMaxWidth, kPpMaxHeight);
+    *qp = forced ? m->forced_quant : 1;
+    return AMVHIP_OK;
+}
+
+// tight planes on both sides (the caller checked), n frames, on st; the context is locked
+int pp_launch(amvhip_ctx* c, const amvhip_pp_mode* m, int qp, const PixPicture& src, const PixPicture& dst, uint32_t w, uint32_t h, uint32_t n,
+              const uint8_t* d_qp, hipStream_t st) {
+    Timed t(c, AMVHIP_K_PIXFMT, st);
+    PpJobs jobs{};
+    // a plane whose mode has none of the three filters is copied: all the reference's loop does then is its block copy
+    for (uint32_t p = 0; p < 3; ++p)
+        jobs.j[p] = PpPlaneJob{src.p[p], dst.p[p], src.frame[p], dst.frame[p], p ? w / 2 : w, p ? h / 2 : h, (p ? m->chrom_mode : m->lum_mode) & kPpFilterBits};
+    jobs.qp = qp;
+    jobs.base_dc_diff = m->base_dc_diff;
+    jobs.flat_thr = m->flatness_threshold;
+    jobs.d_qp = d_qp;
+    launch_postprocess(jobs, n, st);
+    return check_launch(c, "postprocess");
+}
+
+int pp_tight(const PixPicture& pic, uint32_t w) {
+    if (pic.stride[0] != w || pic.stride[1] != w / 2 || pic.stride[2] != w / 2) return 0;
+    for (uint32_t p = 0; p < 3; ++p)
+        if (pic.frame[p] & 3u) return 0;
+    return 1;
+}
+
+}  // namespace
+
+extern "C" int amvhip_postprocess_supported(uint32_t w, uint32_t h) { return pp_size_ok(w, h) ? 1 : 0; }
+
+extern "C" int amvhip_postprocess_dev(amvhip_ctx* c, int fmt, const amvhip_pp_mode* mode, const uint8_t* d_src0, const uint8_t* d_src1,
+                                      const uint8_t* d_src2, uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride,
+                                      uint64_t src_c_frame_stride, uint8_t* d_dst0, uint8_t* d_dst1, uint8_t* d_dst2, uint32_t dst_stride,
+                                      uint32_t dst_c_stride, uint64_t dst_frame_stride, uint64_t dst_c_frame_stride, uint32_t w, uint32_t h,
+                                      uint32_t n, const uint8_t* d_qp, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    int qp;
+    if (int r = pp_args_ok(c, "postprocess", fmt, mode, w, h, &qp)) return r;
+    const PixPicture src = make_picture(d_src0, d_src1, d_src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    const PixPicture dst = make_picture(d_dst0, d_dst1, d_dst2, dst_stride, dst_c_stride, dst_frame_stride, dst_c_frame_stride);
+    if (!pix_picture_ok(fmt, src, w, h) || !pix_picture_ok(fmt, dst, w, h)) return fail(c, AMVHIP_ERR_ARG, "postprocess: null or misaligned plane");
+    if (!pp_tight(src, w) || !pp_tight(dst, w))
+        return fail(c, AMVHIP_ERR_ARG, "postprocess: row pitches must be width and width / 2 (the dering's row-end window reads the next row's first "
+                                       "columns), frame pitches multiples of 4");
+    for (uint32_t i = 0; i < 3; ++i)
+        for (uint32_t k = 0; k < 3; ++k) {
+            uintptr_t s0, s1, d0, d1;
+            plane_span(fmt, src, i, w, h, n, &s0, &s1);
+            plane_span(fmt, dst, k, w, h, n, &d0, &d1);
+            if (s0 < d1 && d0 < s1) return fail(c, AMVHIP_ERR_ARG, "postprocess: source and destination overlap");
+        }
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return pp_launch(c, mode, qp, src, dst, w, h, n, d_qp, (hipStream_t)stream);
+}
+
+extern "C" int amvhip_postprocess(amvhip_ctx* c, int fmt, const amvhip_pp_mode* mode, const uint8_t* src0, const uint8_t* src1, const uint8_t* src2,
+                                  uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride, uint8_t* dst0,
+                                  uint8_t* dst1, uint8_t* dst2, uint32_t dst_stride, uint32_t dst_c_stride, uint64_t dst_frame_stride,
+                                  uint64_t dst_c_frame_stride, uint32_t w, uint32_t h, uint32_t n, const uint8_t* qp_of_frame) {
+    if (!c) return AMVHIP_ERR_ARG;
+    int qp;
+    if (int r = pp_args_ok(c, "postprocess", fmt, mode, w, h, &qp)) return r;
+    const PixPicture hs = make_picture(src0, src1, src2, src_stride, src_c_stride, src_frame_stride, src_c_frame_stride);
+    const PixPicture hd = make_picture(dst0, dst1, dst2, dst_stride, dst_c_stride, dst_frame_stride, dst_c_frame_stride);
+    for (uint32_t i = 0; i < 3; ++i)
+        for (uint32_t k = 0; k < 3; ++k) {
+            if (!hs.p[i] || !hd.p[k]) return fail(c, AMVHIP_ERR_ARG, "postprocess: null plane");
+            uintptr_t s0, s1, d0, d1;
+            plane_span(fmt, hs, i, w, h, n, &s0, &s1);
+            plane_span(fmt, hd, k, w, h, n, &d0, &d1);
+            if (s0 < d1 && d0 < s1) return fail(c, AMVHIP_ERR_ARG, "postprocess: source and destination overlap");
+        }
+    for (uint32_t i = 0; qp_of_frame && i < n; ++i)
+        if (qp_of_frame[i] > 63) return fail(c, AMVHIP_ERR_ARG, "postprocess: QP %u of frame %u is above 63", qp_of_frame[i], i);
+    // the staged planes are tight (rows of exactly the row's bytes, planes 16-byte aligned): what the kernel asks for
+    return host_staged(c, "postprocess", fmt, hs, fmt, hd, w, h, n, [&](const PixPicture& ds, const PixPicture& dd, hipStream_t st) {
+        const uint8_t* d_qp = nullptr;
+        if (qp_of_frame) {
+            if (int r = stage(c, c->h_aux, n, qp_of_frame, n, st)) return r;
+            d_qp = (const uint8_t*)c->h_aux.p;
+        }
+        return pp_launch(c, mode, qp, ds, dd, w, h, n, d_qp, st);
+    });
+}
+
+// the decoder of the patched FFmpeg, the postprocessing, then the planes or img_convert: amvhip_decode_lowres_batch_dev's route
+extern "C" int amvhip_decode_pp_batch_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens,
+                                          uint32_t n, uint32_t w, uint32_t h, uint32_t flags, int dst_fmt, uint8_t* d_out, uint32_t out_stride,
+                                          int32_t* d_status, const amvhip_pp_mode* mode, const uint8_t* d_qp, void* stream) {
+    if (!c) return AMVHIP_ERR_ARG;
+    if (!(flags & AMVHIP_FLAG_FFMPEG)) return fail(c, AMVHIP_ERR_ARG, "decode_pp: AMVHIP_FLAG_FFMPEG is required (the planes are that decoder's)");
+    if (flags & AMVHIP_FLAG_FFMPEG_KEEP) return fail(c, AMVHIP_ERR_ARG, "decode_pp: AMVHIP_FLAG_FFMPEG_KEEP needs the caller's planes; d_out is not in plane form");
+    const bool planes_out = dst_fmt == AMVHIP_PIX_YUVJ420P;
+    if (!planes_out && pix_route(AMVHIP_PIX_YUVJ420P, dst_fmt) == kRouteNone)
+        return fail(c, AMVHIP_ERR_ARG, "decode_pp: no one-step route from YUVJ420P to format %d", dst_fmt);
+    int qp;
+    if (int r = pp_args_ok(c, "decode_pp", AMVHIP_PIX_YUVJ420P, mode, w, h, &qp)) return r;
+    if (int r = decode_args_ok(c, d_blob, d_offs, d_lens, n, w, h, flags, d_out, d_status)) return r;
+    if (planes_out ? out_stride != w : out_stride < w * pix_bpp(dst_fmt))
+        return fail(c, AMVHIP_ERR_ARG, "decode_pp: out_stride below the row (YUVJ420P: it must equal the width)");
+    const uint64_t out_frame = amvhip_pix_frame_bytes(dst_fmt, out_stride, h);
+    PixPicture dst = make_picture(d_out, nullptr, nullptr, out_stride, (out_stride + 1) / 2, out_frame, out_frame);
+    if (dst_fmt == AMVHIP_PIX_YUV420P) {
+        dst.p[1] = d_out + (uint64_t)out_stride * h;
+        dst.p[2] = dst.p[1] + (uint64_t)dst.stride[1] * ((h + 1) / 2);
+    }
+    if (n == 0) return AMVHIP_OK;
+    if (int r = use_device(c)) return r;
+    std::lock_guard<std::mutex> lk(c->mu);
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t fb = amvhip_yuv420_frame_bytes(w, h);
+    if (int r = ensure(c, c->pix_dec, fb * n)) return r;
+    if (!planes_out)
+        if (int r = ensure(c, c->pp_planes, fb * n)) return r;
+    if (int r = decode_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, flags, (uint8_t*)c->pix_dec.p, d_status, c->set[0], st, st)) return r;
+    const PixPicture decoded = tight_420((uint8_t*)c->pix_dec.p, w, h), cleaned = tight_420(planes_out ? d_out : (uint8_t*)c->pp_planes.p, w, h);
+    if (int r = pp_launch(c, mode, qp, decoded, cleaned, w, h, n, d_qp, st)) return r;
+    if (planes_out) return AMVHIP_OK;
+    return convert_launch(c, AMVHIP_PIX_YUVJ420P, cleaned, dst_fmt, dst, w, h, n, st);
 }

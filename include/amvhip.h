@@ -1140,6 +1140,75 @@ int amvhip_decode_lowres_batch(amvhip_ctx *ctx, const uint8_t *blob, uint64_t bl
 int amvhip_reconstruct_lowres_dev(amvhip_ctx *ctx, const int16_t *d_coef, const uint32_t *d_nmcu_ok, uint32_t n,
                                   uint32_t width, uint32_t height, uint32_t lowres, uint8_t *d_out, void *stream);
 /*
+ * Decode-side postprocessing: the reference's libpostproc (AMVmuxer/ffmpeg/libpostproc, pp_postprocess) for its horizontal
+ * and vertical deblocking filters and its deringing filter (`hb`, `vb`, `dr`; the preset `de`), byte for byte the C path of
+ * that library with a forced or absent quantiser table (`fq`; QP 1 without it, as the reference with a NULL QP_store).
+ *
+ * amvhip_pp_mode_parse restates pp_get_mode_by_name_and_quality for hb / hdeblock and vb / vdeblock with their `:diff:flat`
+ * numeric options, dr / dering, fq / forcequant, the option letters a, c, y, n, the `-` prefix, `,` and `/` between filters
+ * and the preset de / default.  Every other filter or preset the reference knows (h1 v1 ha va al lb li ci md fd l5 tn, the
+ * presets fa / fast and ac) and whatever the reference refuses returns AMVHIP_ERR_ARG with *out untouched: nothing is dropped
+ * silently.  No context or device needed.  lum_mode / chrom_mode carry the reference's own bit values; forced_quant is 0
+ * unless AMVHIP_PP_FORCE_QUANT is set.  base_dc_diff is parsed and kept, but with a forced or absent QP table the reference's
+ * classification never sees it (its nonBQP table stays zero: dcOffset = 1 whatever the option says), and so it is here.
+ *
+ * amvhip_postprocess_dev: n pictures, planes and pitches as in amvhip_deinterlace_dev, fmt AMVHIP_PIX_YUV420P or
+ * AMVHIP_PIX_YUVJ420P (chroma planes width / 2 x height / 2, the same QP, as PP_FORMAT_420).  AMVHIP_ERR_ARG, with nothing
+ * launched:
+ *   - a row pitch other than `width` (luma) and `width / 2` (chroma), on either side.  The reference's dering window of a
+ *     row's last block reads and writes one column behind the row: on a tight pitch that column is the next row's first, on
+ *     a wider one it is padding, and the output would depend on what the padding held.  The feature is defined on tight
+ *     pitches: the layout amvhip_decode_fmt_batch_dev writes.
+ *   - planes or frame pitches that are not 4-byte aligned; source and destination that overlap;
+ *   - mode bits outside AMVHIP_PP_V_DEBLOCK | AMVHIP_PP_H_DEBLOCK | AMVHIP_PP_DERING (| AMVHIP_PP_FORCE_QUANT in lum_mode),
+ *     and AMVHIP_PP_DERING without AMVHIP_PP_V_DEBLOCK in a plane's mode: the reference then copies one line ahead only and
+ *     its row-end window reads a destination pixel nobody has written -- its output depends on what the destination held;
+ *   - forced_quant above 63 or below 0 (with AMVHIP_PP_FORCE_QUANT);
+ *   - sizes amvhip_postprocess_supported refuses: it takes widths that are multiples of 16 and even heights, 16 x 16 up to
+ *     1024 x 1024.
+ * d_qp: NULL, or uint8 [n] on the device, a QP per frame (a batch may mix clips; entries above 63 count as 63); else
+ * mode->forced_quant for all frames with AMVHIP_PP_FORCE_QUANT, else 1.  With chrom_mode == 0 the chroma planes are copied.
+ * Asynchronous on `stream`, no host synchronisation; the source is never written.  amvhip_postprocess: the same from and to
+ * host buffers (any pitch >= the row there: the planes are staged tight), synchronous.
+ *
+ * amvhip_decode_pp_batch_dev: arguments as amvhip_decode_fmt_batch_dev, then mode and d_qp.  The frames are decoded into
+ * workspace planes, postprocessed, and written to d_out: straight out for AMVHIP_PIX_YUVJ420P (out_stride must equal width),
+ * through img_convert for every other format the decode entry writes -- the route amvhip_decode_lowres_batch_dev takes.  A
+ * frame with a non-zero status is postprocessed like any other; d_status is the decode's.
+ *
+ * For users of amvhip_prof_read: no kernel id was added.  amv_postprocess_kernel is counted under AMVHIP_K_PIXFMT, as
+ * amv_picture_sse_kernel is.
+ */
+#define AMVHIP_PP_V_DEBLOCK 0x01
+#define AMVHIP_PP_H_DEBLOCK 0x02
+#define AMVHIP_PP_DERING 0x04
+#define AMVHIP_PP_FORCE_QUANT 0x200000
+typedef struct amvhip_pp_mode {
+    int32_t lum_mode, chrom_mode;       /* AMVHIP_PP_* */
+    int32_t base_dc_diff;               /* hb / vb option 1; default 32 */
+    int32_t flatness_threshold;         /* hb / vb option 2; default 39 */
+    int32_t forced_quant;               /* fq's QP (default 15); 0 without AMVHIP_PP_FORCE_QUANT */
+} amvhip_pp_mode;
+int amvhip_pp_mode_parse(const char *name, int quality, amvhip_pp_mode *out);
+int amvhip_postprocess_supported(uint32_t width, uint32_t height);
+int amvhip_postprocess_dev(amvhip_ctx *ctx, int fmt, const amvhip_pp_mode *mode,
+                           const uint8_t *d_src0, const uint8_t *d_src1, const uint8_t *d_src2,
+                           uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                           uint8_t *d_dst0, uint8_t *d_dst1, uint8_t *d_dst2,
+                           uint32_t dst_stride, uint32_t dst_c_stride, uint64_t dst_frame_stride, uint64_t dst_c_frame_stride,
+                           uint32_t width, uint32_t height, uint32_t n, const uint8_t *d_qp, void *stream);
+int amvhip_postprocess(amvhip_ctx *ctx, int fmt, const amvhip_pp_mode *mode,
+                       const uint8_t *src0, const uint8_t *src1, const uint8_t *src2,
+                       uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride, uint64_t src_c_frame_stride,
+                       uint8_t *dst0, uint8_t *dst1, uint8_t *dst2,
+                       uint32_t dst_stride, uint32_t dst_c_stride, uint64_t dst_frame_stride, uint64_t dst_c_frame_stride,
+                       uint32_t width, uint32_t height, uint32_t n, const uint8_t *qp);
+int amvhip_decode_pp_batch_dev(amvhip_ctx *ctx, const uint8_t *d_blob, uint64_t blob_bytes,
+                               const uint64_t *d_offs, const uint32_t *d_lens, uint32_t n,
+                               uint32_t width, uint32_t height, uint32_t flags, int dst_fmt,
+                               uint8_t *d_out, uint32_t out_stride, int32_t *d_status,
+                               const amvhip_pp_mode *mode, const uint8_t *d_qp, void *stream);
+/*
  * The audio resampler in front of the ADPCM encoder: audio_resample (libavcodec/resample.c:129-242) over av_resample
  * (resample2.c:182-324), what ffmpeg.c:1639-1641 / :502 run for `-ac 1 -ar 22050` (AMVmuxer/Makefile:16).  16-tap (at
  * 0.8 of the lower rate's Nyquist: 40 taps at 44.1 kHz -> 22.05 kHz, 44 at 48 kHz, 88 at 96 kHz), 1024-phase, Kaiser-windowed
