@@ -18,7 +18,7 @@ OUT = os.path.join(HERE, "libamvhip.so")
 OBJ = os.path.join(HERE, "build")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["csrc/amv_decode.hip", "csrc/amv_decode_sync.hip", "csrc/amv_reconstruct.hip", "csrc/amv_reconstruct_ff.hip", "csrc/amv_reconstruct_lowres.hip", "csrc/amv_encode.hip", "csrc/amv_encode_par.hip", "csrc/amv_encode_nr.hip", "csrc/amv_encode_error.hip", "csrc/amv_encode_qns.hip", "csrc/amv_encode_rate.hip", "csrc/amv_encode_clip.hip", "csrc/amv_requant.hip", "csrc/amv_retable.hip", "csrc/amv_resample.hip", "csrc/amv_pixfmt.hip", "csrc/amv_picture_sse.hip", "csrc/amv_frontend.hip", "csrc/amv_postprocess.hip", "csrc/amv_audio_resample.hip", "csrc/amv_adpcm.hip", "csrc/amv_adpcm_trellis.hip", "csrc/amv_synth.hip",
+HIP_SOURCES = ["csrc/amv_decode.hip", "csrc/amv_decode_sync.hip", "csrc/amv_reconstruct.hip", "csrc/amv_reconstruct_ff.hip", "csrc/amv_reconstruct_lowres.hip", "csrc/amv_encode.hip", "csrc/amv_encode_par.hip", "csrc/amv_encode_nr.hip", "csrc/amv_encode_error.hip", "csrc/amv_encode_qns.hip", "csrc/amv_encode_rate.hip", "csrc/amv_encode_clip.hip", "csrc/amv_requant.hip", "csrc/amv_resample.hip", "csrc/amv_pixfmt.hip", "csrc/amv_picture_sse.hip", "csrc/amv_frontend.hip", "csrc/amv_postprocess.hip", "csrc/amv_audio_resample.hip", "csrc/amv_adpcm.hip", "csrc/amv_adpcm_trellis.hip", "csrc/amv_synth.hip",
                "csrc/amvhip_context.hip", "csrc/amvhip_decode.hip", "csrc/amvhip_encode.hip", "csrc/amvhip_requant.hip", "csrc/amvhip_pixfmt.hip", "csrc/amvhip_audio.hip"]
 C_SOURCES = ["host/amvlib_compat.c", "host/amv_container.c", "host/amvhip_pp_mode.c"]
 HEADERS = ["csrc/amv_tables.h", "csrc/amv_kernels.h", "csrc/amv_block_load.h", "csrc/amv_piece_map.h", "csrc/amv_segment.h", "csrc/amv_ff_dequant.h", "csrc/amv_simple_idct.h", "csrc/amv_wave.h", "csrc/amv_encode_common.h", "csrc/amv_host_plan.h", "csrc/amv_nr_plan.h", "csrc/amv_trellis_plan.h", "csrc/amv_qns_plan.h", "csrc/amv_rate_plan.h", "csrc/amv_clip_plan.h", "csrc/amv_requant_plan.h", "csrc/amv_retable_plan.h", "csrc/amv_pp_plan.h", "csrc/amv_adpcm_chain.h",

@@ -605,7 +605,7 @@ inline RatePlan rate_plan(uint32_t n, uint32_t rungs, uint32_t blocks) {
     return p;
 }
 
-// ---- video encode: what a clip entry's workspace holds beyond the rate plan (amv_clip_plan.h; clip_core) -------------------
+// ---- video encode: what a clip entry's workspace holds beyond the rate plan (amv_clip_plan.h; budget_passes) ---------------
 // All of it zeroed by a call: the counters of the passes -- word p, p = 1 .. clip_passes_most - 1: the frames redo pass p codes
 // again; the word behind the last takes what the last check and settle append, which is nothing -- the floor sums uint64 [16]
 // and the clip's state (ClipState, amv_kernels.h).  The rate plan's own counters lie idle in a clip call.

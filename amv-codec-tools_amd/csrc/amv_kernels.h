@@ -248,42 +248,38 @@ void launch_clip_start(const uint32_t* bits, const RateLadder& ladder, const uin
 void launch_clip_settle(const uint32_t* bits, const RateLadder& ladder, const uint32_t* budgets, uint32_t budget, uint32_t n, const ClipFrames& fr,
                         const uint32_t* lens, const uint64_t* F, uint64_t total, ClipState* state, uint32_t* rung, uint32_t* lambda, uint32_t* next,
                         uint32_t* next_count, uint64_t* clip, hipStream_t s);
-// Chunks requantised in the coefficient domain (amv_requant.hip, arithmetic in amv_requant_plan.h).  coef: a round of dense
-// lines of levels as the entropy stage's kernels leave them (slot p - base of item p; sel and items as launch_forward's).
-// src: the entropy stage's status and nmcu_ok (whole MCUs) of the call's frames, and, in the pass over the frames in records
-// form, their rec_count -- a frame whose count is ~0 is not in the round (nullptr: every frame of sel is).  launch_requant: a
-// frame that is coded gets its AC levels searched at lambdas[f] (lambdas nullptr: `lambda`), in place, and its planes' error
-// ADDED to err [n][3] (nullptr: not wanted; the caller zeroes it); every other frame of sel, and every block out of range,
-// lines of zeros; flags[f] (zeroed by the caller) != 0 afterwards: the frame has a block out of range.
+// Chunks requantised in the coefficient domain, or re-tabled (amv_requant.hip, arithmetic in amv_requant_plan.h and
+// amv_retable_plan.h).  coef: a round of dense lines of levels as the entropy stage's kernels leave them (slot p - base of
+// item p; sel and items as launch_forward's).  src: the entropy stage's status and nmcu_ok (whole MCUs) of the call's frames,
+// and, in the pass over the frames in records form, their rec_count -- a frame whose count is ~0 is not in the round (nullptr:
+// every frame of sel is).  rt: the tables the chunks were written against -- tables nullptr: AMV's own (the requant kernels);
+// else uint8 [count][2][64] on the device (luma then chroma, scan order, entries 1 .. 255), count 1 .. 64, and table_of:
+// uint8 [n] on the device, a frame's table (nullptr: table 0) (the re-table kernels: the line's DC and dc[] are the NEW DC, err
+// sums over all 64 positions).  launch_requant: a frame that is coded gets its AC levels searched at lambdas[f] (lambdas
+// nullptr: `lambda`), in place, and its planes' error ADDED to err [n][3] (nullptr: not wanted; the caller zeroes it); every
+// other frame of sel, and every block out of range, lines of zeros.  flags[f] (zeroed by the caller) afterwards, bit 0: the
+// frame has a block out of range; bit 1: table_of[f] names no table (the frame is not coded).
 // launch_requant_probe: the bits of the AC codes at every rung ADDED to bits [n][rungs], the DCs to dc [n][blocks] for
 // launch_rate_dc.  launch_requant_finish: d_status takes the range flag (and AMVHIP_ST_TRUNCATED where a decode stopped early
 // without saying why); a frame that is not coded gets lens 0, err 0, bits 0 and rung (rungs - 1) | kRateOver -- each where
-// the pointer is not null.
+// the pointer is not null.  launch_retable_status, behind it: the status of a frame whose index named no table becomes
+// AMVHIP_ST_TABLE.
 struct RequantSource {
     const int32_t* status;
     const uint32_t* nmcu_ok;
     const uint32_t* rec_count;
 };
-void launch_requant(int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const RequantSource& src, uint32_t lambda,
-                    const uint32_t* lambdas, uint32_t* flags, uint64_t* err, hipStream_t s);
-void launch_requant_probe(const int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const RequantSource& src,
-                          const RateLadder& ladder, uint32_t* flags, int16_t* dc, uint32_t* bits, hipStream_t s);
-void launch_requant_finish(uint32_t n, const FrameGeom& g, int32_t* status, const uint32_t* nmcu_ok, const uint32_t* flags, uint32_t* lens,
-                           uint64_t* err, uint32_t* rung, uint32_t* bits, uint32_t rungs, hipStream_t s);
-// Chunks re-tabled (amv_retable.hip, arithmetic in amv_retable_plan.h): launch_requant / launch_requant_probe with the tables
-// the chunks were written against.  tables: uint8 [count][2][64] on the device (luma then chroma, scan order, entries 1 ..
-// 255), count 1 .. 64; table_of: uint8 [n] on the device, a frame's table (nullptr: table 0).  The line's DC and dc[] are the
-// NEW DC; err sums over all 64 positions.  flags[f] bit 0: a block out of range; bit 1: table_of[f] names no table (the frame
-// is not coded).  launch_retable_status, behind launch_requant_finish: such a frame's status becomes AMVHIP_ST_TABLE.
 struct RetableTables {
     const uint8_t* tables;
     uint32_t count;
     const uint8_t* table_of;
 };
-void launch_retable(int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const RequantSource& src,
+void launch_requant(int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const RequantSource& src,
                     const RetableTables& rt, uint32_t lambda, const uint32_t* lambdas, uint32_t* flags, uint64_t* err, hipStream_t s);
-void launch_retable_probe(const int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const RequantSource& src,
+void launch_requant_probe(const int16_t* coef, uint32_t n, const FrameSel& sel, uint32_t items, const FrameGeom& g, const RequantSource& src,
                           const RetableTables& rt, const RateLadder& ladder, uint32_t* flags, int16_t* dc, uint32_t* bits, hipStream_t s);
+void launch_requant_finish(uint32_t n, const FrameGeom& g, int32_t* status, const uint32_t* nmcu_ok, const uint32_t* flags, uint32_t* lens,
+                           uint64_t* err, uint32_t* rung, uint32_t* bits, uint32_t rungs, hipStream_t s);
 void launch_retable_status(uint32_t n, int32_t* status, const uint32_t* flags, hipStream_t s);
 // exclusive scan of lens -> offs (single workgroup), then gather tmp -> blob.  A chunk that would end past
 // blob_cap is not copied and its lens entry becomes 0; *overflow = 1 when the total exceeds blob_cap.

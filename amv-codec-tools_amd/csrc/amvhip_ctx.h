@@ -7,6 +7,7 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <functional>
 #include <map>
 #include <mutex>
 #include <string>
@@ -269,7 +270,7 @@ int rate_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const QuantR
 int rate_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, const RateArg& rate,
                      uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung, hipStream_t stream);
 // What a clip entry asks beyond its rate sibling (amv_clip_plan.h): the bytes of the whole clip and where the clip record goes.
-// clip_args_ok: d_clip.  clip_scaled_tail: rate_scaled_tail's counterpart through clip_core.
+// clip_args_ok: d_clip.  clip_scaled_tail: rate_scaled_tail's counterpart, through rate_core with the clip.
 struct ClipArg {
     uint64_t total;
     uint64_t* d_clip;
@@ -278,6 +279,15 @@ int clip_args_ok(amvhip_ctx* c, uint32_t n, const uint64_t* d_clip);
 int clip_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, const RateArg& rate,
                      const ClipArg& clip, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung,
                      hipStream_t stream);
+// The byte-budget flow of the rate and clip entries, the encoder's and the requant side's (amvhip_requant.hip), written once:
+// see its definition.  The three steps a caller brings return 0 to go on.  (std::function, not a template over callables:
+// the body is amvhip_encode.hip's, the callers' lambdas two files'.)
+using BudgetProbe = std::function<int(uint32_t* bits)>;
+using BudgetFirstPass = std::function<int(const uint32_t* lambda)>;
+using BudgetRedoRound = std::function<int(const FrameSel& sel, uint32_t items, const uint32_t* lambda)>;
+int budget_passes(amvhip_ctx* c, const RateArg& rate, const ClipArg* clip, const ClipFrames& frames, uint32_t n, uint32_t blocks, uint32_t round,
+                  uint32_t* d_lens, uint32_t* d_rung, const char* who, hipStream_t stream, const BudgetProbe& probe,
+                  const BudgetFirstPass& first_pass, const BudgetRedoRound& redo_round);
 int resample_launch(amvhip_ctx* c, const PixPicture& src, uint32_t src_w, uint32_t src_h, const PixPicture& dst, uint32_t dst_w, uint32_t dst_h,
                     uint32_t n, bool to_jpeg, hipStream_t st);
 

@@ -423,11 +423,11 @@ int amv::rate_args_ok(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, const Q
     return AMVHIP_OK;
 }
 
-// The bits of n frames at every rung, ADDED to bits [n][rungs] (the context is locked, c->rate_ws holds `plan`): the probe's
-// two launches, as many frames at a time as a grid takes.  offsets: the frames' -nr offsets, or nullptr.
+// The bits of n frames at every rung, ADDED to bits [n][rungs] (the context is locked, c->rate_ws holds the call's rate_plan):
+// the probe's two launches, as many frames at a time as a grid takes.  offsets: the frames' -nr offsets, or nullptr.
 static int rate_probe(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, const uint16_t* offsets,
-                      const RateLadder& ladder, const RatePlan& plan, uint32_t* bits, hipStream_t stream) {
-    int16_t* const dc = (int16_t*)((uint8_t*)c->rate_ws.p + plan.dc);
+                      const RateLadder& ladder, uint32_t* bits, hipStream_t stream) {
+    int16_t* const dc = (int16_t*)((uint8_t*)c->rate_ws.p + rate_plan(n, ladder.rungs, g.blocks).dc);
     const uint64_t segs = (uint64_t)g.mcu_rows * seg_split(g).nseg;
     const uint32_t most = (uint32_t)((1ull << 30) / segs);      // frames per launch: >= 1 (a picture has at most 2^20 MCUs)
     Timed t(c, AMVHIP_K_FDCT, stream);
@@ -454,79 +454,124 @@ static int probe_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGe
         if (int r = nr_quantiser(c, in, n, g, nr, copy, nullptr, &quant, stream)) return r;
         offsets = std::get<const uint16_t*>(quant);
     }
-    return rate_probe(c, in, n, g, qbias, offsets, ladder, plan, d_bits, stream);
+    return rate_probe(c, in, n, g, qbias, offsets, ladder, d_bits, stream);
 }
 
-// amvhip_encode_*_rate_stream_dev's core (the context is locked, the request checked, n > 0).  Everything is queued on
-// `stream`, nothing is read back:
-//   with nr > 0 passes A and B once, in front (the state moves as in _nr_trellis_stream); the probe -> the bits table;
-//   the choice: every frame's first floor-fit -> d_rung, the frame's lambda;
-//   the first pass: amv_forward_kernel with the frames' lambdas + amv_pack_kernel over all frames, a round of the coefficient
-//   workspace at a time (default launches over the round's part of the source); the check: a frame over its budget moves to
-//   its next floor-fit and joins a list;
-//   up to rungs - 1 redo passes over that list (FrameSel rounds: small launches, usually with nothing to do -- the host
-//   cannot know), each with its check behind it; the compaction.
-// The one-kernel encoder takes no part: it has no instantiation with a lambda per frame, so both entropy modes run this.
-static int rate_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, uint32_t nr, int32_t* d_state,
-                     const RateArg& rate, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung,
-                     hipStream_t stream) {
-    const uint32_t bound = amvhip_encode_bound(g.width, g.height);
-    const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
-    const uint32_t round = fallback_round(n, g, 1024u, 2u);
-    const uint32_t rungs = rate.ladder.rungs;
-    const RatePlan plan = rate_plan(n, rungs, g.blocks);
-    if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
-    if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
-    if (int r = ensure(c, c->flag, 16)) return r;
+// The byte-budget flow, once, for the encoder's and the requant side's rate and clip entries (the context is locked).
+// Everything is queued on `stream`, nothing is read back:
+//   the workspaces: rate_ws, and clip_ws with a clip; the spans a call zeroes;
+//   probe(bits) -> the bits table;
+//   the choice: every frame's first floor-fit -> d_rung, the frame's lambda.  With a clip, in its place: the floor sums over
+//   `frames`, and the start: the first clip rung whose floor sum fits, every frame's record and lambda there;
+//   first_pass(lambda): every frame coded at its lambda, its length in d_lens; the check: a frame over its budget moves to its
+//   next floor-fit and joins a list.  With a clip, behind every check the settle: with every frame inside its budget the
+//   lengths are summed, and the clip is final or moves on and lists the frames it takes along;
+//   up to rungs - 1 (with a clip: clip_passes_most - 1) redo passes over that list, redo_round(sel, items, lambda) a round of
+//   the coefficient workspace at a time (FrameSel rounds: small launches, usually with nothing to do -- the host cannot know),
+//   each pass with its check (and settle) behind it.
+// The counters of the passes are the rate plan's without a clip, the clip plan's with one.  who: the entry, for check_launch.
+int amv::budget_passes(amvhip_ctx* c, const RateArg& rate, const ClipArg* clip, const ClipFrames& frames, uint32_t n, uint32_t blocks,
+                       uint32_t round, uint32_t* d_lens, uint32_t* d_rung, const char* who, hipStream_t stream, const BudgetProbe& probe,
+                       const BudgetFirstPass& first_pass, const BudgetRedoRound& redo_round) {
+    const RateLadder& lad = rate.ladder;
+    const uint32_t rungs = lad.rungs;
+    const RatePlan plan = rate_plan(n, rungs, blocks);
+    const ClipPlan cplan = clip_plan();
     if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
+    if (clip)
+        if (int r = ensure(c, c->clip_ws, cplan.bytes)) return r;
     uint8_t* const ws = (uint8_t*)c->rate_ws.p;
-    uint32_t* const counters = (uint32_t*)(ws + plan.counters);
+    uint8_t* const cws = clip ? (uint8_t*)c->clip_ws.p : nullptr;
+    uint32_t* const counters = clip ? (uint32_t*)(cws + cplan.counters) : (uint32_t*)(ws + plan.counters);
+    uint64_t* const F = clip ? (uint64_t*)(cws + cplan.F) : nullptr;
+    ClipState* const state = clip ? (ClipState*)(cws + cplan.state) : nullptr;
     uint32_t* const bits = (uint32_t*)(ws + plan.bits);
     uint32_t* const lambda = (uint32_t*)(ws + plan.lambda);
     uint32_t* const lists[2] = {(uint32_t*)(ws + plan.list[0]), (uint32_t*)(ws + plan.list[1])};
     HIP_TRY(c, hipMemsetAsync(ws + plan.zero, 0, plan.zero_bytes, stream));
-    const uint16_t* offsets = nullptr;
-    if (nr) {
-        Quantiser with_offsets;
-        if (int r = nr_quantiser(c, in, n, g, nr, d_state, nullptr, &with_offsets, stream)) return r;
-        offsets = std::get<const uint16_t*>(with_offsets);
+    if (clip) HIP_TRY(c, hipMemsetAsync(cws, 0, cplan.bytes, stream));
+    if (int r = probe(bits)) return r;
+    if (clip) {
+        launch_clip_floor(bits, rungs, rate.d_budget, rate.budget, n, frames, F, stream);
+        launch_clip_start(bits, lad, rate.d_budget, rate.budget, n, frames, F, clip->total, state, d_rung, lambda, stream);
+        if (int r = check_launch(c, (std::string(who) + ": floor + start").c_str())) return r;
+    } else {
+        launch_rate_choose(bits, lad, rate.d_budget, rate.budget, n, d_rung, lambda, stream);
     }
-    if (int r = rate_probe(c, in, n, g, qbias, offsets, rate.ladder, plan, bits, stream)) return r;
-    launch_rate_choose(bits, rate.ladder, rate.d_budget, rate.budget, n, d_rung, lambda, stream);
-    const Quantiser quant = offsets ? Quantiser{NrTrellisFrames{offsets, lambda}} : Quantiser{TrellisFrames{lambda}};
-    for (uint32_t base = 0; base < n; base += round) {
-        const uint32_t items = n - base < round ? n - base : round;
-        {
-            Timed t(c, AMVHIP_K_FDCT, stream);
-            launch_forward(frames_from(in, base, g), items, kAllFrames, items, g, qbias, frames_from(quant, base), (int16_t*)c->coef.p, stream);
-        }
-        {
-            Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
-            launch_pack((const int16_t*)c->coef.p, items, kAllFrames, items, g, book, (uint8_t*)c->tmp.p + (uint64_t)base * bound, bound,
-                        d_lens + base, stream);
-        }
-        if (int r = check_launch(c, "rate: forward + pack")) return r;
-    }
-    launch_rate_check(bits, rate.ladder, rate.d_budget, rate.budget, n, d_lens, nullptr, nullptr, d_rung, lambda, lists[0], counters + 1, stream);
-    for (uint32_t pass = 1; pass < rungs; ++pass) {
+    if (int r = first_pass(lambda)) return r;
+    // behind a pass over list[0 .. *count) (nullptr: over all n)
+    const auto check = [&](const uint32_t* list, const uint32_t* count, uint32_t* next, uint32_t* next_count) {
+        launch_rate_check(bits, lad, rate.d_budget, rate.budget, n, d_lens, list, count, d_rung, lambda, next, next_count, stream);
+        if (clip)
+            launch_clip_settle(bits, lad, rate.d_budget, rate.budget, n, frames, d_lens, F, clip->total, state, d_rung, lambda, next, next_count,
+                               clip->d_clip, stream);
+    };
+    check(nullptr, nullptr, lists[0], counters + 1);
+    const uint32_t passes = clip ? clip_passes_most(rungs) : rungs;
+    for (uint32_t pass = 1; pass < passes; ++pass) {
         const uint32_t* const list = lists[(pass - 1u) & 1u];
         const uint32_t* const count = counters + pass;
         for (uint32_t base = 0; base < n; base += round) {
             const uint32_t items = n - base < round ? n - base : round;
-            const FrameSel sel{list, count, base, items};
-            {
-                Timed t(c, AMVHIP_K_FDCT, stream);
-                launch_forward(in, n, sel, items, g, qbias, quant, (int16_t*)c->coef.p, stream);
-            }
-            {
-                Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
-                launch_pack((const int16_t*)c->coef.p, n, sel, items, g, book, (uint8_t*)c->tmp.p, bound, d_lens, stream);
-            }
+            if (int r = redo_round(FrameSel{list, count, base, items}, items, lambda)) return r;
         }
-        launch_rate_check(bits, rate.ladder, rate.d_budget, rate.budget, n, d_lens, list, count, d_rung, lambda, lists[pass & 1u],
-                          counters + pass + 1u, stream);
-        if (int r = check_launch(c, "rate: redo pass")) return r;
+        check(list, count, lists[pass & 1u], counters + pass + 1u);
+        if (int r = check_launch(c, (std::string(who) + ": redo pass").c_str())) return r;
     }
+    return AMVHIP_OK;
+}
+
+// amvhip_encode_*_rate_stream_dev's and (clip not null) amvhip_encode_*_clip_stream_dev's core (the context is locked, the
+// request checked, n > 0): budget_passes over the pictures.  With nr > 0 passes A and B run once, in front of the probe (the
+// state moves as in _nr_trellis_stream).  The first pass is amv_forward_kernel with the frames' lambdas + amv_pack_kernel over
+// all frames, a round of the coefficient workspace at a time (default launches over the round's part of the source); a redo
+// round is the same pair over a FrameSel; the compaction ends the call.
+// The one-kernel encoder takes no part: it has no instantiation with a lambda per frame, so both entropy modes run this.
+static int rate_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, uint32_t nr, int32_t* d_state,
+                     const RateArg& rate, const ClipArg* clip, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
+                     uint32_t* d_rung, hipStream_t stream) {
+    const uint32_t bound = amvhip_encode_bound(g.width, g.height);
+    const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
+    const uint32_t round = fallback_round(n, g, 1024u, 2u);
+    if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
+    if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
+    if (int r = ensure(c, c->flag, 16)) return r;
+    const uint16_t* offsets = nullptr;
+    const auto quant_of = [&](const uint32_t* lambda) { return offsets ? Quantiser{NrTrellisFrames{offsets, lambda}} : Quantiser{TrellisFrames{lambda}}; };
+    // forward + pack of one launch: `frames` of src, their chunks and lengths from frame `base` on
+    const auto code = [&](const Source& src, uint32_t frames, const FrameSel& sel, uint32_t items, const Quantiser& quant, uint32_t base) {
+        {
+            Timed t(c, AMVHIP_K_FDCT, stream);
+            launch_forward(src, frames, sel, items, g, qbias, quant, (int16_t*)c->coef.p, stream);
+        }
+        Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
+        launch_pack((const int16_t*)c->coef.p, frames, sel, items, g, book, (uint8_t*)c->tmp.p + (uint64_t)base * bound, bound, d_lens + base,
+                    stream);
+    };
+    if (int r = budget_passes(
+            c, rate, clip, kClipAllFrames, n, g.blocks, round, d_lens, d_rung, clip ? "clip" : "rate", stream,
+            [&](uint32_t* bits) {
+                if (nr) {
+                    Quantiser with_offsets;
+                    if (int r = nr_quantiser(c, in, n, g, nr, d_state, nullptr, &with_offsets, stream)) return r;
+                    offsets = std::get<const uint16_t*>(with_offsets);
+                }
+                return rate_probe(c, in, n, g, qbias, offsets, rate.ladder, bits, stream);
+            },
+            [&](const uint32_t* lambda) {
+                const Quantiser quant = quant_of(lambda);
+                for (uint32_t base = 0; base < n; base += round) {
+                    const uint32_t items = n - base < round ? n - base : round;
+                    code(frames_from(in, base, g), items, kAllFrames, items, frames_from(quant, base), base);
+                    if (int r = check_launch(c, clip ? "clip: forward + pack" : "rate: forward + pack")) return r;
+                }
+                return (int)AMVHIP_OK;
+            },
+            [&](const FrameSel& sel, uint32_t items, const uint32_t* lambda) {
+                code(in, n, sel, items, quant_of(lambda), 0u);
+                return (int)AMVHIP_OK;
+            }))
+        return r;
     {
         Timed t(c, AMVHIP_K_COMPACT, stream);
         launch_compact((const uint8_t*)c->tmp.p, bound, d_lens, n, d_offs, d_blob, blob_cap, (int32_t*)c->flag.p, stream);
@@ -539,7 +584,7 @@ static const NrTrellisRequest& rate_nr_of(const QuantRequest& req) { return std:
 int amv::rate_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, const RateArg& rate,
                           uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung, hipStream_t stream) {
     return rate_core(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, rate_nr_of(req).nr,
-                     rate_nr_of(req).state, rate, d_blob, blob_cap, d_offs, d_lens, d_rung, stream);
+                     rate_nr_of(req).state, rate, nullptr, d_blob, blob_cap, d_offs, d_lens, d_rung, stream);
 }
 
 static int rate_probe_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, const amvhip_quant* q, const uint32_t* ladder,
@@ -568,8 +613,8 @@ static int rate_stream_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
-    return rate_core(c, in, n, make_geom(w, h), q->qbias, rate_nr_of(req).nr, rate_nr_of(req).state, rate, d_blob, blob_cap, d_offs, d_lens, d_rung,
-                     (hipStream_t)stream);
+    return rate_core(c, in, n, make_geom(w, h), q->qbias, rate_nr_of(req).nr, rate_nr_of(req).state, rate, nullptr, d_blob, blob_cap, d_offs, d_lens,
+                     d_rung, (hipStream_t)stream);
 }
 
 extern "C" int amvhip_encode_rate_probe_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w, uint32_t h,
@@ -606,97 +651,11 @@ int amv::clip_args_ok(amvhip_ctx* c, uint32_t n, const uint64_t* d_clip) {
     return AMVHIP_OK;
 }
 
-// amvhip_encode_*_clip_stream_dev's core (the context is locked, the request checked, n > 0): rate_core with the choice per
-// clip above the choice per frame.  Everything is queued on `stream`, nothing is read back:
-//   passes A and B and the probe as in rate_core; the floor sums; the start: the first clip rung whose floor sum fits, every
-//   frame's record and lambda there; the first pass over all frames; the check, and behind it the settle: with every frame
-//   inside its budget the lengths are summed, and the clip is final or moves on and lists the frames it takes along;
-//   clip_passes_most - 1 redo passes over the lists (FrameSel rounds as in rate_core, nearly all with nothing to do), each
-//   with its check and settle behind it; the compaction.
-static int clip_core(amvhip_ctx* c, const Source& in, uint32_t n, const FrameGeom& g, uint32_t qbias, uint32_t nr, int32_t* d_state,
-                     const RateArg& rate, const ClipArg& clip, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens,
-                     uint32_t* d_rung, hipStream_t stream) {
-    const uint32_t bound = amvhip_encode_bound(g.width, g.height);
-    const HuffEncodeImage* book = (const HuffEncodeImage*)c->d_enc.p;
-    const uint32_t round = fallback_round(n, g, 1024u, 2u);
-    const uint32_t rungs = rate.ladder.rungs;
-    const RatePlan plan = rate_plan(n, rungs, g.blocks);
-    const ClipPlan cplan = clip_plan();
-    if (int r = ensure(c, c->coef, (size_t)round * g.blocks * 128)) return r;
-    if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
-    if (int r = ensure(c, c->flag, 16)) return r;
-    if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
-    if (int r = ensure(c, c->clip_ws, cplan.bytes)) return r;
-    uint8_t* const ws = (uint8_t*)c->rate_ws.p;
-    uint8_t* const cws = (uint8_t*)c->clip_ws.p;
-    uint32_t* const counters = (uint32_t*)(cws + cplan.counters);
-    uint64_t* const F = (uint64_t*)(cws + cplan.F);
-    ClipState* const state = (ClipState*)(cws + cplan.state);
-    uint32_t* const bits = (uint32_t*)(ws + plan.bits);
-    uint32_t* const lambda = (uint32_t*)(ws + plan.lambda);
-    uint32_t* const lists[2] = {(uint32_t*)(ws + plan.list[0]), (uint32_t*)(ws + plan.list[1])};
-    HIP_TRY(c, hipMemsetAsync(ws + plan.zero, 0, plan.zero_bytes, stream));
-    HIP_TRY(c, hipMemsetAsync(cws, 0, cplan.bytes, stream));
-    const uint16_t* offsets = nullptr;
-    if (nr) {
-        Quantiser with_offsets;
-        if (int r = nr_quantiser(c, in, n, g, nr, d_state, nullptr, &with_offsets, stream)) return r;
-        offsets = std::get<const uint16_t*>(with_offsets);
-    }
-    if (int r = rate_probe(c, in, n, g, qbias, offsets, rate.ladder, plan, bits, stream)) return r;
-    launch_clip_floor(bits, rungs, rate.d_budget, rate.budget, n, kClipAllFrames, F, stream);
-    launch_clip_start(bits, rate.ladder, rate.d_budget, rate.budget, n, kClipAllFrames, F, clip.total, state, d_rung, lambda, stream);
-    if (int r = check_launch(c, "clip: floor + start")) return r;
-    const Quantiser quant = offsets ? Quantiser{NrTrellisFrames{offsets, lambda}} : Quantiser{TrellisFrames{lambda}};
-    for (uint32_t base = 0; base < n; base += round) {
-        const uint32_t items = n - base < round ? n - base : round;
-        {
-            Timed t(c, AMVHIP_K_FDCT, stream);
-            launch_forward(frames_from(in, base, g), items, kAllFrames, items, g, qbias, frames_from(quant, base), (int16_t*)c->coef.p, stream);
-        }
-        {
-            Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
-            launch_pack((const int16_t*)c->coef.p, items, kAllFrames, items, g, book, (uint8_t*)c->tmp.p + (uint64_t)base * bound, bound,
-                        d_lens + base, stream);
-        }
-        if (int r = check_launch(c, "clip: forward + pack")) return r;
-    }
-    launch_rate_check(bits, rate.ladder, rate.d_budget, rate.budget, n, d_lens, nullptr, nullptr, d_rung, lambda, lists[0], counters + 1, stream);
-    launch_clip_settle(bits, rate.ladder, rate.d_budget, rate.budget, n, kClipAllFrames, d_lens, F, clip.total, state, d_rung, lambda, lists[0],
-                       counters + 1, clip.d_clip, stream);
-    for (uint32_t pass = 1; pass < clip_passes_most(rungs); ++pass) {
-        const uint32_t* const list = lists[(pass - 1u) & 1u];
-        const uint32_t* const count = counters + pass;
-        for (uint32_t base = 0; base < n; base += round) {
-            const uint32_t items = n - base < round ? n - base : round;
-            const FrameSel sel{list, count, base, items};
-            {
-                Timed t(c, AMVHIP_K_FDCT, stream);
-                launch_forward(in, n, sel, items, g, qbias, quant, (int16_t*)c->coef.p, stream);
-            }
-            {
-                Timed t(c, AMVHIP_K_PACK_SERIAL, stream);
-                launch_pack((const int16_t*)c->coef.p, n, sel, items, g, book, (uint8_t*)c->tmp.p, bound, d_lens, stream);
-            }
-        }
-        launch_rate_check(bits, rate.ladder, rate.d_budget, rate.budget, n, d_lens, list, count, d_rung, lambda, lists[pass & 1u],
-                          counters + pass + 1u, stream);
-        launch_clip_settle(bits, rate.ladder, rate.d_budget, rate.budget, n, kClipAllFrames, d_lens, F, clip.total, state, d_rung, lambda,
-                           lists[pass & 1u], counters + pass + 1u, clip.d_clip, stream);
-        if (int r = check_launch(c, "clip: redo pass")) return r;
-    }
-    {
-        Timed t(c, AMVHIP_K_COMPACT, stream);
-        launch_compact((const uint8_t*)c->tmp.p, bound, d_lens, n, d_offs, d_blob, blob_cap, (int32_t*)c->flag.p, stream);
-    }
-    return check_launch(c, "compact");
-}
-
 int amv::clip_scaled_tail(amvhip_ctx* c, uint32_t n, uint32_t w, uint32_t h, uint32_t qbias, const QuantRequest& req, const RateArg& rate,
                           const ClipArg& clip, uint8_t* d_blob, uint64_t blob_cap, uint64_t* d_offs, uint32_t* d_lens, uint32_t* d_rung,
                           hipStream_t stream) {
-    return clip_core(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, rate_nr_of(req).nr,
-                     rate_nr_of(req).state, rate, clip, d_blob, blob_cap, d_offs, d_lens, d_rung, stream);
+    return rate_core(c, yuv_source(yuv_source_of(tight_420((uint8_t*)c->scaled.p, w, h))), n, make_geom(w, h), qbias, rate_nr_of(req).nr,
+                     rate_nr_of(req).state, rate, &clip, d_blob, blob_cap, d_offs, d_lens, d_rung, stream);
 }
 
 static int clip_stream_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t w, uint32_t h, const amvhip_quant* q, const amvhip_rate* rate_in,
@@ -712,8 +671,9 @@ static int clip_stream_dev(amvhip_ctx* c, const Source& in, uint32_t n, uint32_t
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
-    return clip_core(c, in, n, make_geom(w, h), q->qbias, rate_nr_of(req).nr, rate_nr_of(req).state, rate, ClipArg{total, d_clip}, d_blob, blob_cap,
-                     d_offs, d_lens, d_rung, (hipStream_t)stream);
+    const ClipArg clip{total, d_clip};
+    return rate_core(c, in, n, make_geom(w, h), q->qbias, rate_nr_of(req).nr, rate_nr_of(req).state, rate, &clip, d_blob, blob_cap, d_offs, d_lens,
+                     d_rung, (hipStream_t)stream);
 }
 
 extern "C" int amvhip_encode_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_pix, uint32_t pix_stride, int is_bgr, uint32_t n, uint32_t w,

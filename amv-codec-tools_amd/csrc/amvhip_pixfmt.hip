@@ -609,7 +609,7 @@ extern "C" int amvhip_encode_frontend_rate_stream_dev(amvhip_ctx* c, int src_fmt
     return rate_scaled_tail(c, n, w, h, q->qbias, req, rate, d_blob, blob_cap, d_offs, d_lens, d_rung, (hipStream_t)stream);
 }
 
-// ... with a byte budget for the whole call above it (amv_clip_plan.h): the same, through clip_core
+// ... with a byte budget for the whole call above it (amv_clip_plan.h): the same, through rate_core with the clip
 extern "C" int amvhip_encode_frontend_clip_stream_dev(amvhip_ctx* c, int src_fmt, const uint8_t* d_src0, const uint8_t* d_src1, const uint8_t* d_src2,
                                                       uint32_t src_stride, uint32_t src_c_stride, uint64_t src_frame_stride,
                                                       uint64_t src_c_frame_stride, uint32_t src_w, uint32_t src_h, uint32_t n,

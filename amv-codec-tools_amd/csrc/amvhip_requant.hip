@@ -1,7 +1,8 @@
 // amvhip_requant.hip -- AMV chunks requantised in the coefficient domain behind the C ABI: chunks in, chunks out, no pixel in
 // between.  The decoder's entropy stage (amvhip_decode.hip: entropy_records, amv_huffman_kernel) in front, amv_requant.hip in
 // the place of the encoder's front half, the encoder's coder, choice and compaction behind it.  The re-table entries are the
-// same four bodies with amv_retable.hip in amv_requant.hip's place: chunks written against foreign tables, made AMV's.
+// same three cores with the call's tables in Front::rt (chunks written against foreign tables, made AMV's); the rate and the
+// clip entries share one, the encoder's budget_passes (amvhip_encode.hip) over the chunks' levels.
 #include "amvhip_ctx.h"
 
 using namespace amv;
@@ -66,7 +67,7 @@ struct Front {
     RetableTables rt;             // the re-table entries: the call's tables on the device (tables nullptr: a requant entry)
 };
 
-// The four entries come in two forms, requant and re-table (amv_retable_plan.h): one body each, `rt` the re-table form's
+// The entries come in two forms, requant and re-table (amv_retable_plan.h): one core each, `rt` the re-table form's
 // argument and nullptr for the requant form.  What the re-table form asks beyond its sibling:
 struct Retable {
     const amvhip_retable* rt;
@@ -148,8 +149,7 @@ int code_round(amvhip_ctx* c, const Front& f, const FrameSel& sel, uint32_t item
                const uint32_t* lambdas, uint64_t* d_err, uint32_t bound, uint32_t* d_lens, hipStream_t st) {
     {
         Timed t(c, AMVHIP_K_FDCT, st);
-        if (f.rt.tables) launch_retable(f.coef, f.n, sel, items, f.g, src, f.rt, lambda, lambdas, f.flags, d_err, st);
-        else launch_requant(f.coef, f.n, sel, items, f.g, src, lambda, lambdas, f.flags, d_err, st);
+        launch_requant(f.coef, f.n, sel, items, f.g, src, f.rt, lambda, lambdas, f.flags, d_err, st);
     }
     {
         Timed t(c, AMVHIP_K_PACK_SERIAL, st);
@@ -164,13 +164,12 @@ int compact(amvhip_ctx* c, uint32_t n, uint32_t bound, uint32_t* d_lens, uint64_
     return check_launch(c, "requant: compact");
 }
 
-// The bits of every frame at every rung into bits [n][rungs] (zeroed by the caller); rate_ws holds `plan`
-int probe_pass(amvhip_ctx* c, const Front& f, const RateLadder& ladder, const RatePlan& plan, uint32_t* bits, hipStream_t st) {
-    int16_t* const dc = (int16_t*)((uint8_t*)c->rate_ws.p + plan.dc);
+// The bits of every frame at every rung into bits [n][rungs] (zeroed by the caller); rate_ws holds the call's rate_plan
+int probe_pass(amvhip_ctx* c, const Front& f, const RateLadder& ladder, uint32_t* bits, hipStream_t st) {
+    int16_t* const dc = (int16_t*)((uint8_t*)c->rate_ws.p + rate_plan(f.n, ladder.rungs, f.g.blocks).dc);
     if (int r = each_round(c, f, st, [&](const FrameSel& sel, uint32_t items, const RequantSource& src) {
             Timed t(c, AMVHIP_K_FDCT, st);
-            if (f.rt.tables) launch_retable_probe(f.coef, f.n, sel, items, f.g, src, f.rt, ladder, f.flags, dc, bits, st);
-            else launch_requant_probe(f.coef, f.n, sel, items, f.g, src, ladder, f.flags, dc, bits, st);
+            launch_requant_probe(f.coef, f.n, sel, items, f.g, src, f.rt, ladder, f.flags, dc, bits, st);
             return check_launch(c, "requant: probe");
         }))
         return r;
@@ -228,147 +227,60 @@ int probe_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const 
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t st = (hipStream_t)stream;
     const FrameGeom g = make_geom(w, h);
-    const RatePlan plan = rate_plan(n, rungs, g.blocks);
-    if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
+    if (int r = ensure(c, c->rate_ws, rate_plan(n, rungs, g.blocks).bytes)) return r;
     if (int r = ensure(c, c->requant_status, (size_t)n * 4)) return r;    // the entry hands out no statuses: a zero row says `not coded`
     int32_t* const d_status = (int32_t*)c->requant_status.p;
     Front f;
     if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, t, &f)) return r;
     HIP_TRY(c, hipMemsetAsync(d_bits, 0, (size_t)n * rungs * 4u, st));
-    if (int r = probe_pass(c, f, lad, plan, d_bits, st)) return r;
+    if (int r = probe_pass(c, f, lad, d_bits, st)) return r;
     return finish(c, f, nullptr, nullptr, nullptr, d_bits, rungs, st);
 }
 
-// amv_encode_rate.hip's flow (amvhip_encode.hip: rate_core) with the chunks' levels as the source: the probe over every frame,
-// the choice, a first pass at the frames' lambdas, the check, and up to rungs - 1 redo passes over device-built lists.  A redo
-// pass takes its frames' lines from the serial kernel, whichever kernel decoded them first: it decodes any frame of the call
-// into any slot, and a list names few.
-int rate_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
-                                              const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_rate* rate, uint8_t* d_out,
-                                              uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status, uint32_t* d_rung,
-                                              void* stream, const Retable& t) {
+// The rate entries' and (clip not null) the clip entries' core: the encoder's flow (amvhip_encode.hip: budget_passes) with the
+// chunks' levels as the source.  The probe and the first pass go over every frame, a round at a time as the entropy stage left
+// them.  A redo round takes its frames' lines from the serial kernel, whichever kernel decoded them first: it decodes any
+// frame of the call into any slot, and a list names few.  With a clip (amv_clip_plan.h) the floor sums and the start go over
+// the frames that are coded: a frame that is not coded adds nothing to a sum.
+int rate_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs, const uint32_t* d_lens, uint32_t n, uint32_t w,
+              uint32_t h, const amvhip_rate* rate, const ClipArg* clip, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens,
+              int32_t* d_status, uint32_t* d_rung, void* stream, const Retable& t) {
     if (!c) return AMVHIP_ERR_ARG;
     if (!rate) return fail(c, AMVHIP_ERR_ARG, "requant_rate: the rate request or its ladder is null");
-    RateLadder lad;
-    if (int r = requant_ladder_of(c, rate->ladder, rate->rungs, &lad)) return r;
+    RateArg arg{RateLadder{}, rate->budget, rate->d_budget};
+    if (int r = requant_ladder_of(c, rate->ladder, rate->rungs, &arg.ladder)) return r;
     if ((uintptr_t)rate->d_budget & 3u) return fail(c, AMVHIP_ERR_ARG, "requant_rate: d_budget is not 4-byte aligned");
     if (int r = requant_args_ok(c, d_blob, d_offs, d_lens, n, w, h, d_status)) return r;
     if (int r = requant_outputs_ok(c, n, d_out, d_out_offs, d_out_lens)) return r;
     if (int r = requant_rate_size_ok(c, n, w, h, d_rung)) return r;
+    if (clip)
+        if (int r = clip_args_ok(c, n, clip->d_clip)) return r;
     if (int r = retable_args_ok(c, t)) return r;
     if (n == 0) return AMVHIP_OK;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
     hipStream_t st = (hipStream_t)stream;
     const FrameGeom g = make_geom(w, h);
-    const uint32_t bound = amvhip_encode_bound(w, h), rungs = lad.rungs;
-    const RatePlan plan = rate_plan(n, rungs, g.blocks);
+    const uint32_t bound = amvhip_encode_bound(w, h);
     if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
     if (int r = ensure(c, c->flag, 16)) return r;
-    if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
-    uint8_t* const ws = (uint8_t*)c->rate_ws.p;
-    uint32_t* const counters = (uint32_t*)(ws + plan.counters);
-    uint32_t* const bits = (uint32_t*)(ws + plan.bits);
-    uint32_t* const lambda = (uint32_t*)(ws + plan.lambda);
-    uint32_t* const lists[2] = {(uint32_t*)(ws + plan.list[0]), (uint32_t*)(ws + plan.list[1])};
     Front f;
     if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, t, &f)) return r;
-    HIP_TRY(c, hipMemsetAsync(ws + plan.zero, 0, plan.zero_bytes, st));
-    if (int r = probe_pass(c, f, lad, plan, bits, st)) return r;
-    launch_rate_choose(bits, lad, rate->d_budget, rate->budget, n, d_rung, lambda, st);
-    if (int r = each_round(c, f, st, [&](const FrameSel& sel, uint32_t items, const RequantSource& src) {
-            return code_round(c, f, sel, items, src, 0u, lambda, nullptr, bound, d_out_lens, st);
-        }))
+    const ClipFrames coded{f.status, f.nmcu, f.flags, g.mcus};       // (read behind the probe, which sets the range flags)
+    if (int r = budget_passes(
+            c, arg, clip, coded, n, g.blocks, f.round, d_out_lens, d_rung, clip ? "requant_clip" : "requant_rate", st,
+            [&](uint32_t* bits) { return probe_pass(c, f, arg.ladder, bits, st); },
+            [&](const uint32_t* lambda) {
+                return each_round(c, f, st, [&](const FrameSel& sel, uint32_t items, const RequantSource& src) {
+                    return code_round(c, f, sel, items, src, 0u, lambda, nullptr, bound, d_out_lens, st);
+                });
+            },
+            [&](const FrameSel& sel, uint32_t items, const uint32_t* lambda) {
+                if (int r = serial_round(c, f, sel.list, sel.count, sel.base, items, st)) return r;
+                return code_round(c, f, sel, items, RequantSource{f.status, f.nmcu, nullptr}, 0u, lambda, nullptr, bound, d_out_lens, st);
+            }))
         return r;
-    launch_rate_check(bits, lad, rate->d_budget, rate->budget, n, d_out_lens, nullptr, nullptr, d_rung, lambda, lists[0], counters + 1, st);
-    for (uint32_t pass = 1; pass < rungs; ++pass) {
-        const uint32_t* const list = lists[(pass - 1u) & 1u];
-        const uint32_t* const count = counters + pass;
-        for (uint32_t base = 0; base < n; base += f.round) {
-            const uint32_t items = n - base < f.round ? n - base : f.round;
-            if (int r = serial_round(c, f, list, count, base, items, st)) return r;
-            if (int r = code_round(c, f, FrameSel{list, count, base, items}, items, RequantSource{f.status, f.nmcu, nullptr}, 0u, lambda, nullptr,
-                                   bound, d_out_lens, st))
-                return r;
-        }
-        launch_rate_check(bits, lad, rate->d_budget, rate->budget, n, d_out_lens, list, count, d_rung, lambda, lists[pass & 1u], counters + pass + 1u,
-                          st);
-        if (int r = check_launch(c, "requant_rate: redo pass")) return r;
-    }
-    if (int r = finish(c, f, d_out_lens, nullptr, d_rung, nullptr, rungs, st)) return r;
-    return compact(c, n, bound, d_out_lens, d_out_offs, d_out, out_cap, st);
-}
-
-// amvhip_requant_rate_stream_dev's flow with the choice per clip above the choice per frame (amvhip_encode.hip: clip_core;
-// amv_clip_plan.h): the probe, the floor sums and the start over the frames that are coded, the first pass, and behind every
-// check the settle; clip_passes_most - 1 redo passes.  A frame that is not coded adds nothing to a sum.
-int clip_core(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
-                                              const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_rate* rate, uint64_t total,
-                                              uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status,
-                                              uint32_t* d_rung, uint64_t* d_clip, void* stream, const Retable& t) {
-    if (!c) return AMVHIP_ERR_ARG;
-    if (!rate) return fail(c, AMVHIP_ERR_ARG, "requant_rate: the rate request or its ladder is null");
-    RateLadder lad;
-    if (int r = requant_ladder_of(c, rate->ladder, rate->rungs, &lad)) return r;
-    if ((uintptr_t)rate->d_budget & 3u) return fail(c, AMVHIP_ERR_ARG, "requant_rate: d_budget is not 4-byte aligned");
-    if (int r = requant_args_ok(c, d_blob, d_offs, d_lens, n, w, h, d_status)) return r;
-    if (int r = requant_outputs_ok(c, n, d_out, d_out_offs, d_out_lens)) return r;
-    if (int r = requant_rate_size_ok(c, n, w, h, d_rung)) return r;
-    if (int r = clip_args_ok(c, n, d_clip)) return r;
-    if (int r = retable_args_ok(c, t)) return r;
-    if (n == 0) return AMVHIP_OK;
-    if (int r = use_device(c)) return r;
-    std::lock_guard<std::mutex> lk(c->mu);
-    hipStream_t st = (hipStream_t)stream;
-    const FrameGeom g = make_geom(w, h);
-    const uint32_t bound = amvhip_encode_bound(w, h), rungs = lad.rungs;
-    const RatePlan plan = rate_plan(n, rungs, g.blocks);
-    const ClipPlan cplan = clip_plan();
-    if (int r = ensure(c, c->tmp, (size_t)n * bound)) return r;
-    if (int r = ensure(c, c->flag, 16)) return r;
-    if (int r = ensure(c, c->rate_ws, plan.bytes)) return r;
-    if (int r = ensure(c, c->clip_ws, cplan.bytes)) return r;
-    uint8_t* const ws = (uint8_t*)c->rate_ws.p;
-    uint8_t* const cws = (uint8_t*)c->clip_ws.p;
-    uint32_t* const counters = (uint32_t*)(cws + cplan.counters);
-    uint64_t* const F = (uint64_t*)(cws + cplan.F);
-    ClipState* const state = (ClipState*)(cws + cplan.state);
-    uint32_t* const bits = (uint32_t*)(ws + plan.bits);
-    uint32_t* const lambda = (uint32_t*)(ws + plan.lambda);
-    uint32_t* const lists[2] = {(uint32_t*)(ws + plan.list[0]), (uint32_t*)(ws + plan.list[1])};
-    Front f;
-    if (int r = front_of(c, d_blob, blob_bytes, d_offs, d_lens, n, g, d_status, st, t, &f)) return r;
-    HIP_TRY(c, hipMemsetAsync(ws + plan.zero, 0, plan.zero_bytes, st));
-    HIP_TRY(c, hipMemsetAsync(cws, 0, cplan.bytes, st));
-    if (int r = probe_pass(c, f, lad, plan, bits, st)) return r;
-    const ClipFrames coded{f.status, f.nmcu, f.flags, g.mcus};       // (the probe has set the range flags)
-    launch_clip_floor(bits, rungs, rate->d_budget, rate->budget, n, coded, F, st);
-    launch_clip_start(bits, lad, rate->d_budget, rate->budget, n, coded, F, total, state, d_rung, lambda, st);
-    if (int r = check_launch(c, "requant_clip: floor + start")) return r;
-    if (int r = each_round(c, f, st, [&](const FrameSel& sel, uint32_t items, const RequantSource& src) {
-            return code_round(c, f, sel, items, src, 0u, lambda, nullptr, bound, d_out_lens, st);
-        }))
-        return r;
-    launch_rate_check(bits, lad, rate->d_budget, rate->budget, n, d_out_lens, nullptr, nullptr, d_rung, lambda, lists[0], counters + 1, st);
-    launch_clip_settle(bits, lad, rate->d_budget, rate->budget, n, coded, d_out_lens, F, total, state, d_rung, lambda, lists[0], counters + 1, d_clip,
-                       st);
-    for (uint32_t pass = 1; pass < clip_passes_most(rungs); ++pass) {
-        const uint32_t* const list = lists[(pass - 1u) & 1u];
-        const uint32_t* const count = counters + pass;
-        for (uint32_t base = 0; base < n; base += f.round) {
-            const uint32_t items = n - base < f.round ? n - base : f.round;
-            if (int r = serial_round(c, f, list, count, base, items, st)) return r;
-            if (int r = code_round(c, f, FrameSel{list, count, base, items}, items, RequantSource{f.status, f.nmcu, nullptr}, 0u, lambda, nullptr,
-                                   bound, d_out_lens, st))
-                return r;
-        }
-        launch_rate_check(bits, lad, rate->d_budget, rate->budget, n, d_out_lens, list, count, d_rung, lambda, lists[pass & 1u], counters + pass + 1u,
-                          st);
-        launch_clip_settle(bits, lad, rate->d_budget, rate->budget, n, coded, d_out_lens, F, total, state, d_rung, lambda, lists[pass & 1u],
-                           counters + pass + 1u, d_clip, st);
-        if (int r = check_launch(c, "requant_clip: redo pass")) return r;
-    }
-    if (int r = finish(c, f, d_out_lens, nullptr, d_rung, nullptr, rungs, st)) return r;
+    if (int r = finish(c, f, d_out_lens, nullptr, d_rung, nullptr, arg.ladder.rungs, st)) return r;
     return compact(c, n, bound, d_out_lens, d_out_offs, d_out, out_cap, st);
 }
 
@@ -388,13 +300,14 @@ extern "C" int amvhip_requant_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_bl
                                               const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_rate* rate, uint8_t* d_out,
                                               uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status, uint32_t* d_rung,
                                               void* stream) {
-    return rate_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, stream, kNoRetable);
+    return rate_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, nullptr, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, stream, kNoRetable);
 }
 extern "C" int amvhip_requant_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
                                               const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_rate* rate, uint64_t total,
                                               uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens, int32_t* d_status,
                                               uint32_t* d_rung, uint64_t* d_clip, void* stream) {
-    return clip_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, total, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, d_clip, stream,
+    const ClipArg clip{total, d_clip};
+    return rate_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, &clip, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, stream,
                      kNoRetable);
 }
 
@@ -415,14 +328,15 @@ extern "C" int amvhip_retable_rate_stream_dev(amvhip_ctx* c, const uint8_t* d_bl
                                               const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_retable* rt,
                                               const amvhip_rate* rate, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offs, uint32_t* d_out_lens,
                                               int32_t* d_status, uint32_t* d_rung, void* stream) {
-    return rate_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, stream,
+    return rate_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, nullptr, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, stream,
                      Retable{rt, true});
 }
 extern "C" int amvhip_retable_clip_stream_dev(amvhip_ctx* c, const uint8_t* d_blob, uint64_t blob_bytes, const uint64_t* d_offs,
                                               const uint32_t* d_lens, uint32_t n, uint32_t w, uint32_t h, const amvhip_retable* rt,
                                               const amvhip_rate* rate, uint64_t total, uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_offs,
                                               uint32_t* d_out_lens, int32_t* d_status, uint32_t* d_rung, uint64_t* d_clip, void* stream) {
-    return clip_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, total, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, d_clip, stream,
+    const ClipArg clip{total, d_clip};
+    return rate_core(c, d_blob, blob_bytes, d_offs, d_lens, n, w, h, rate, &clip, d_out, out_cap, d_out_offs, d_out_lens, d_status, d_rung, stream,
                      Retable{rt, true});
 }
 

@@ -391,6 +391,36 @@ def test_requant_entry(ctx, pkg, both_modes):
     both_modes(run)
 
 
+def test_requant_two_workspace_rounds_and_one_bump(ctx, pkg, both_modes):
+    """16x16 x 1030, the eight synthetic chunks cycling, a total one byte below S(0): every frame is coded at rung 0, the sum is
+    over, the clip moves to rung 1 and takes along every frame below it -- frames 1024 .. 1029 among them, which a redo pass
+    finds in the second round of the coefficient workspace (the serial kernel's round with base 1024).  Rung 1 makes one of the
+    eight chunks a byte longer, so S(1) > S(0) and the walk goes on to rung 2 the same way: the model says where it ends."""
+    w, h, n = 16, 16, 1030
+    eight = Q.synth_chunks(w, h, 8)
+    lens8, coded8 = C.requant_lens(eight, w, h, Q.LADDER)
+    bits8 = Q.bits_table(eight, w, h, Q.LADDER)
+    assert all(coded8)
+    cycle = [i % 8 for i in range(n)]
+    chunks, lens, bits = [eight[i] for i in cycle], lens8[cycle], bits8[cycle]
+    S, F = C.sums(lens, C.NO_CAP), C.floor_sums(bits, C.NO_CAP)
+    total = S[0] - 1
+    walk = C.device_walk(bits, lens, C.NO_CAP, total)
+    c = walk[0]
+    assert F[0] <= total and walk[6][:2] == [0, 1] and walk[6][-1] == c                       # the clip moves to rung 1
+    assert walk[4] == len(walk[6]) and all(k == walk[4] for k in walk[5][1024:])              # and takes frames 1024 .. 1029 along
+    assert walk[1:4] == (False, S[c], [c] * n)
+    at_c = Q.requant(eight, w, h, Q.LADDER[c])[0]
+
+    def run(mode):
+        got = _requant_clip(ctx, pkg, chunks, w, h, Q.LADDER, C.NO_CAP, total)
+        assert got[5] == [c, S[c]], "%s: d_clip %s" % (mode, got[5])
+        TQ._check(got, [at_c[i] for i in cycle], [0] * n, "requant, 1030 chunks, %s" % mode)
+        assert list(got[4]) == walk[3], mode
+
+    both_modes(run)
+
+
 # ---- a blob that is too small ---------------------------------------------------------------------------------------------------------
 
 def test_blob_one_byte_short(ctx, pkg):
