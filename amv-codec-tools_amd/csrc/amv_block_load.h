@@ -63,13 +63,20 @@ __device__ __forceinline__ bool next_item(const PieceMap& pm, uint32_t& item) {
     return true;
 }
 
+// Stage A comes in two steps, so that a kernel with more than one reader of the coefficients can fetch them where it
+// reads them: stage_segment_blocks brings a records frame's segment into LDS and says what form the frame has,
+// fetch_block loads the lane's block from wherever it is.  load_segment_blocks is the two in a row.
+// records, small_ac: wave-uniform.  small_ac: a records frame without the entropy stage's mark (kRecCountBigAc) -- every
+// AC of it has at most nine magnitude bits, |value| <= 511.  Dense lines promise nothing.
+struct BlockForm { bool records, small_ac; int dc_base; };
+
 // s_img: kSegImageBytes + 128 bytes of LDS, 16-byte aligned; the caller may reuse it after a seg_sync().
 // Returns true when this lane holds a block (lane < cnt * 6).
 // dense_only: a round launch -- the frame's lines are in slot `slot` whatever rec_count says.  A default launch over
 // records leaves frames that went to the serial kernel alone: skip = true (for the whole workgroup), nothing loaded.
-__device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, const Segment& sg, bool dense_only, const FrameGeom& g,
-                                                    uint32_t lane, uint8_t* s_img, uint32_t (&c)[32], bool& skip) {
-    const uint32_t f = sg.f, slot = sg.slot, segidx = sg.segidx, nsegs = sg.nsegs, mcu0 = sg.mcu0, cnt = sg.cnt, ok = sg.ok;
+__device__ __forceinline__ bool stage_segment_blocks(const SyncSinks& in, const Segment& sg, bool dense_only, const FrameGeom& g,
+                                                     uint32_t lane, uint8_t* s_img, BlockForm& form, bool& skip) {
+    const uint32_t f = sg.f, segidx = sg.segidx, nsegs = sg.nsegs, mcu0 = sg.mcu0, cnt = sg.cnt, ok = sg.ok;
     const uint32_t nb = cnt * 6u;
     // What the wave must know before it can ask for its records: the form of the frame and the segment's record range
     // (asked for together here), how far the frame was decoded (segment_of's load) and where its records begin
@@ -88,6 +95,7 @@ __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, const S
         r1 = ss[3];
     }
     const bool records = rc != 0xffffffffu;
+    form = BlockForm{records, records && !(rc & kRecCountBigAc), 0};
     skip = !records && in.rec != nullptr && !dense_only;   // a round launch reconstructs this frame
     if (skip) return false;
     int dc_base = 0;
@@ -189,8 +197,15 @@ __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, const S
         }
         seg_sync();
     }
-    if (lane >= nb) return false;
-    if (records) {
+    form.dc_base = dc_base;
+    return lane < nb;
+}
+
+// the block of a lane that stage_segment_blocks said holds one
+__device__ __forceinline__ void fetch_block(const SyncSinks& in, const Segment& sg, const FrameGeom& g, uint32_t lane, const uint8_t* s_img,
+                                            const BlockForm& form, uint32_t (&c)[32]) {
+    const uint32_t mcu0 = sg.mcu0;
+    if (form.records) {
         const uint4* src = reinterpret_cast<const uint4*>(s_img) + lane * 8u;
         const uint32_t swz = (lane + mcu0 * 6u - g.blocks) & 7u;   // the low bits of this block's field: the scatter's swizzle
 #pragma unroll
@@ -198,15 +213,22 @@ __device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, const S
             const uint4 q = src[(uint32_t)i ^ swz];
             c[4 * i] = q.x; c[4 * i + 1] = q.y; c[4 * i + 2] = q.z; c[4 * i + 3] = q.w;
         }
-        c[0] = (c[0] & 0xffff0000u) | ((c[0] + (uint32_t)dc_base) & 0xffffu);   // int16 arithmetic, as the predictors wrap
+        c[0] = (c[0] & 0xffff0000u) | ((c[0] + (uint32_t)form.dc_base) & 0xffffu);   // int16 arithmetic, as the predictors wrap
     } else {
-        const uint4* src = reinterpret_cast<const uint4*>(in.coef + (((uint64_t)slot * g.mcus + mcu0) * 6u + lane) * 64u);
+        const uint4* src = reinterpret_cast<const uint4*>(in.coef + (((uint64_t)sg.slot * g.mcus + mcu0) * 6u + lane) * 64u);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const uint4 q = src[i];
             c[4 * i] = q.x; c[4 * i + 1] = q.y; c[4 * i + 2] = q.z; c[4 * i + 3] = q.w;
         }
     }
+}
+
+__device__ __forceinline__ bool load_segment_blocks(const SyncSinks& in, const Segment& sg, bool dense_only, const FrameGeom& g,
+                                                    uint32_t lane, uint8_t* s_img, uint32_t (&c)[32], bool& skip) {
+    BlockForm form;
+    if (!stage_segment_blocks(in, sg, dense_only, g, lane, s_img, form, skip)) return false;
+    fetch_block(in, sg, g, lane, s_img, form, c);
     return true;
 }
 

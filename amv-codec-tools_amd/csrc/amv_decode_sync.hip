@@ -675,6 +675,9 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
         uint32_t recpos = 0;         // end of the last line this lane wrote
         uint32_t seg_next = 0, seg_col = 0, seg_blk = 0;   // the next MCU-row segment whose first DC symbol has not come yet
         uint32_t end_blocks = 0;     // whole blocks when the walk stopped
+        // OR of the frame's entries, not of a stride's: its kFastBigAc marks the frame.  The trouble test below reads the
+        // same word: it is guarded by `alive`, and a lane that met "no such code" is stopped in that very stride.
+        uint32_t seen = 0u;
 #pragma unroll
         for (uint32_t q = 0; q < 2u * kFlush; ++q) stage_put<kFlush>(stage, q, kDummyRecord);
         if (__ballot(alive) != 0ull) do {
@@ -696,7 +699,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
                 const bool running = alive;
                 s.rp8 = stride_no << 11;     // this stride's eight slots
                 const FastState start = s;
-                uint32_t worst = ~0u, seen = 0u;
+                uint32_t worst = ~0u;
                 fast_stride<kFlush, false>(ringb, stageb, sumb, 0u, s, seen, worst);
                 const bool trouble = alive && (worst < 15u || (seen & kFastInvalid) != 0u);
                 if (__ballot(trouble) != 0ull) {   // a damaged stream
@@ -759,7 +762,9 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_fast_kernel(
             } else {
                 status[frame] = (int32_t)st;
                 nmcu_ok[frame] = out.ok_in_blocks ? end_blocks : end_blocks / 6u;
-                out.rec_count[frame] = recpos;
+                const uint32_t big = (seen & kFastBigAc) * (kRecCountBigAc / kFastBigAc);
+                out.rec_count[frame] = recpos | big;
+                if (stats && big) atomicAdd(&stats[10], 1ull);
             }
         }
         if (stats != nullptr && lane == 0 && task < kTraceTasks) {   // ... and when it ended
@@ -1069,6 +1074,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
             seg_next = row * sg.per_row + seg_col;
             seg_blk = (row * sg.mcu_cols + seg_col * kSegMcus) * 6u;
         }
+        uint32_t seen = 0u;          // OR of the lane's entries over its whole share (kFastBigAc; the trouble test is guarded by `alive`)
         if (__ballot(alive) != 0ull) {
         fast_open_at(win, alive ? (s.t + 1u) >> 5 : 0u);
         bool have_words = true;      // fast_open_at asked for the next eight words
@@ -1081,7 +1087,7 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
             }
             const bool running = alive;
             const FastState start = s;
-            uint32_t worst = ~0u, seen = 0u;
+            uint32_t worst = ~0u;
             fast_stride<kFlush, true>(ringb, stageb, sumb, wlim1, s, seen, worst);
             const bool trouble = alive && (worst < 15u || (seen & kFastInvalid) != 0u);
             if (__ballot(trouble) != 0ull) {   // a damaged stream (or a lane right of the true path's end)
@@ -1137,6 +1143,8 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
         } else {
             st = kStFormat; good_blocks = 0;   // unreachable: the last lane runs until the frame ends or fails
         }
+        // the frame's mark: an AC of ten magnitude bits or more in the share of any lane on the true path
+        const bool big = (__ballot((seen & kFastBigAc) != 0u && (int)lane <= stop_lane) & seg) != 0ull;
 
         // ---- 5. DC prediction: the sums of the lanes to the left are a lane's base; it goes into the frame's lane table
         // and the reader adds it
@@ -1181,7 +1189,8 @@ __global__ __launch_bounds__(kWave * 16) void amv_huffman_sync2_kernel(
             } else {
                 status[frame] = (int32_t)st;
                 nmcu_ok[frame] = out.ok_in_blocks ? good_blocks : good_blocks / 6u;
-                out.rec_count[frame] = rec_total | ((uint32_t)(L - 1) << 24);   // (a frame holds < 2^21 records: amv_host_plan.h)
+                out.rec_count[frame] = rec_total | ((uint32_t)(L - 1) << 24) | (big ? kRecCountBigAc : 0u);   // (a frame holds < 2^21 records: amv_host_plan.h)
+                if (stats && big) atomicAdd(&stats[10], 1ull);
             }
         }
     }   // next task

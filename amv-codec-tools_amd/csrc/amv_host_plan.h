@@ -78,6 +78,14 @@ inline void build_images(HuffDecodeImage& dec, HuffEncodeImage& enc) {
     }
 }
 
+// The image as the device gets it: kFastBigAc on the entries of the two AC tables with ten magnitude bits or more
+// (amv_tables.h).  A step of its own behind build_images, whose image stays the documented entry and nothing else.
+inline void mark_big_ac(HuffDecodeImage& dec) {
+    for (int t = 2; t < 4; ++t)
+        for (uint32_t& e : dec.fast[t])
+            if ((e & 15u) >= 10u) e |= kFastBigAc;   // (the size field; "no such code" and end-of-block have 0 there)
+}
+
 // ---- video decode: what the entropy stage of n frames in blob_bytes of chunks is given -------------------------------
 
 struct EntropyPlan {

@@ -44,8 +44,10 @@ constexpr size_t kStatsBytes = (size_t)(kTraceBase + 8u * kTraceTasks) * 8u;
 // ahead of `to`, with only records of this segment's first <= 4 blocks in between (the exact position twice, or the
 // record counts around the eight symbols in which the segment began), lane_tab[lanes] = {first block,
 // DC base Y, Cb, Cr} of each of the lanes that decoded the frame (a row of `lanes` entries per frame; how many of them a
-// frame used is in its rec_count), rec_count (bits 0-23 total, bits 24-29 lanes that decoded the frame - 1; or ~0 = this
+// frame used is in its rec_count), rec_count (bits 0-23 total, bits 24-29 lanes that decoded the frame - 1, bit 30
+// kRecCountBigAc: the frame's walk met an AC symbol of ten magnitude bits or more; or ~0 = this
 // frame is in dense form in coef because it went through amv_huffman_kernel).
+constexpr uint32_t kRecCountBigAc = 1u << 30;
 struct SyncSinks {
     int16_t* coef;
     uint32_t* rec;

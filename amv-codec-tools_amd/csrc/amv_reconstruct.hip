@@ -10,7 +10,9 @@
 //   B. the whole 8x8 block stays in that lane's registers: de-zig-zag is register renaming (plus
 //      one select for amvlib's [3][4] table entry), dequantisation one multiply per coefficient,
 //      then 8 row transforms and 8 column transforms with the reference's exact integer
-//      arithmetic -- no transposition, no LDS between the passes;
+//      arithmetic -- no transposition, no LDS between the passes.  The row pass has two forms: a records frame in
+//      which the entropy stage met no AC of ten magnitude bits takes it as dot products over pairs of 16-bit
+//      halves (idct8_row_pairs), every other frame and every dense line the general 32-bit form;
 //   C. results go to 16-row Y and 8-row U/V planes in LDS (one 16-byte store per block row; the
 //      planes reuse the space of the records' image, which every lane has read by then);
 //   D. colour conversion of a 4x2-pixel patch per lane step, two bytes per instruction in packed
@@ -77,26 +79,12 @@ constexpr uint32_t inverse_of_odd(uint32_t a) {   // modulo 2^32 (Newton: each s
 constexpr int kRowSeed = (int)((64u * inverse_of_odd(181u)) & 0x7fffffffu);
 static_assert(181u * 2u * (uint32_t)kRowSeed == 128u, "the seed puts 128 into both 181-products");
 
-template <bool kColumn, RowKind kKind = kRowPlain>
-__device__ __forceinline__ void idct8(int& v0, int& v1, int& v2, int& v3, int& v4, int& v5, int& v6, int& v7) {
-    constexpr int W1 = 2841, W2 = 2676, W3 = 2408, W5 = 1609, W6 = 1108, W7 = 565;
-    constexpr int kBias = kKind == kRow0 ? 128 + 8192 : 128;
-    constexpr int kRound = kColumn ? 4 : 0;
-    constexpr int kDown = kColumn ? 3 : 0;
-    constexpr int kOut = kColumn ? 7 : 8;
-    constexpr int kSeed = kColumn ? 0 : kRowSeed, kHalf = kColumn ? 128 : 0;
-    int a0 = kColumn ? v0 : v0 * 2048 + kBias, a1 = kColumn ? v4 : v4 * 2048;   // (<<11; the column's <<8 is done)
-    const int i2 = v6, i3 = v2, i4 = v1, i5 = v7, i6 = v5, i7 = v3;
-    int t;
-    int a4 = mad24(i4, W1, mad24(i5, W7, kRound + kSeed)) >> kDown;     // W7*(x4+x5) + (W1-W7)*x4
-    int a5 = mad24(i4, W7, mad24(i5, -W1, kRound)) >> kDown;    // W7*(x4+x5) - (W1+W7)*x5
-    int a6 = mad24(i6, W5, mad24(i7, W3, kRound - kSeed)) >> kDown;     // W3*(x6+x7) - (W3-W5)*x6
-    int a7 = mad24(i6, W3, mad24(i7, -W5, kRound)) >> kDown;    // W3*(x6+x7) - (W3+W5)*x7
-    t = a0 + a1;
-    a0 -= a1;
-    int a2 = mad24(i3, W6, mad24(i2, -W2, kRound)) >> kDown;    // W6*(x3+x2) - (W2+W6)*x2
-    int a3 = mad24(i3, W2, mad24(i2, W6, kRound)) >> kDown;     // W6*(x3+x2) + (W2-W6)*x3
-    a1 = a4 + a6;
+// What follows the eight linear forms of a pass: the butterflies, the two 181-products, the shift or mask on the way out.
+template <bool kColumn, RowKind kKind>
+__device__ __forceinline__ void idct8_tail(int t, int a0, int a2, int a3, int a4, int a5, int a6, int a7,
+                                           int& v0, int& v1, int& v2, int& v3, int& v4, int& v5, int& v6, int& v7) {
+    constexpr int kOut = kColumn ? 7 : 8, kHalf = kColumn ? 128 : 0;
+    int a1 = a4 + a6;
     a4 -= a6;
     a6 = a5 + a7;
     a5 -= a7;
@@ -121,6 +109,27 @@ __device__ __forceinline__ void idct8(int& v0, int& v1, int& v2, int& v3, int& v
     }
 }
 
+template <bool kColumn, RowKind kKind = kRowPlain>
+__device__ __forceinline__ void idct8(int& v0, int& v1, int& v2, int& v3, int& v4, int& v5, int& v6, int& v7) {
+    constexpr int W1 = 2841, W2 = 2676, W3 = 2408, W5 = 1609, W6 = 1108, W7 = 565;
+    constexpr int kBias = kKind == kRow0 ? 128 + 8192 : 128;
+    constexpr int kRound = kColumn ? 4 : 0;
+    constexpr int kDown = kColumn ? 3 : 0;
+    constexpr int kSeed = kColumn ? 0 : kRowSeed;
+    int a0 = kColumn ? v0 : v0 * 2048 + kBias, a1 = kColumn ? v4 : v4 * 2048;   // (<<11; the column's <<8 is done)
+    const int i2 = v6, i3 = v2, i4 = v1, i5 = v7, i6 = v5, i7 = v3;
+    int t;
+    int a4 = mad24(i4, W1, mad24(i5, W7, kRound + kSeed)) >> kDown;     // W7*(x4+x5) + (W1-W7)*x4
+    int a5 = mad24(i4, W7, mad24(i5, -W1, kRound)) >> kDown;    // W7*(x4+x5) - (W1+W7)*x5
+    int a6 = mad24(i6, W5, mad24(i7, W3, kRound - kSeed)) >> kDown;     // W3*(x6+x7) - (W3-W5)*x6
+    int a7 = mad24(i6, W3, mad24(i7, -W5, kRound)) >> kDown;    // W3*(x6+x7) - (W3+W5)*x7
+    t = a0 + a1;
+    a0 -= a1;
+    int a2 = mad24(i3, W6, mad24(i2, -W2, kRound)) >> kDown;    // W6*(x3+x2) - (W2+W6)*x2
+    int a3 = mad24(i3, W2, mad24(i2, W6, kRound)) >> kDown;     // W6*(x3+x2) + (W2-W6)*x3
+    idct8_tail<kColumn, kKind>(t, a0, a2, a3, a4, a5, a6, a7, v0, v1, v2, v3, v4, v5, v6, v7);
+}
+
 // the quantiser steps, scan order, four to a dword: [0] luma, [1] chroma.  A lane reads its component's sixteen dwords
 // once and multiplies by bytes of them (a select between two literals per coefficient cost 40 instructions a block).
 struct QuantWords { uint32_t w[2][16]; };
@@ -133,6 +142,111 @@ constexpr QuantWords pack_quant() {
     return q;
 }
 __device__ const QuantWords kQuantWords = pack_quant();
+
+// ---- Stage B for a records frame without the entropy stage's mark (load_segment_blocks: small_ac): the row pass on
+// paired 16-bit halves.  The eight linear forms in front of a row's butterflies are two-element dot products over the
+// pairs (n0, n4), (n1, n7), (n5, n3), (n2, n6) of the row's dequantised inputs: v_dot2_i32_i16 with the weights in a
+// scalar register and the bias or seed as its accumulator, the low 32 bits of the exact sum as mad24 gives them.  That
+// needs every input as an int16: an AC of at most nine magnitude bits times the largest step does fit (asserted below),
+// one of ten need not -- what the mark is for.  The DC times its step does not fit either; it enters row 0's even forms
+// alone and stays a 32-bit number there.
+constexpr uint32_t pair16(int lo, int hi) { return ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16); }   // two int16 in a dword
+constexpr int kPairCol[4][2] = {{0, 4}, {1, 7}, {5, 3}, {2, 6}};   // columns of a row's pair q: low half, high half
+constexpr int pair_scan(int pair, int half) { return kScanOfNatural[8 * (pair >> 2) + kPairCol[pair & 3][half]]; }   // pair = 4 * row + q
+constexpr int largest_step() {
+    int m = 0;
+    for (int i = 0; i < 64; ++i) m = kQuantLuma[i] > m ? kQuantLuma[i] : m;
+    for (int i = 0; i < 64; ++i) m = kQuantChroma[i] > m ? kQuantChroma[i] : m;
+    return m;
+}
+static_assert(largest_step() * 511 <= 32767, "nine magnitude bits times any step is an int16");
+constexpr bool pairs_cover_the_scan() {   // the 64 halves are the 64 scan positions, each once; the DC is pair 0's low half
+    bool seen[64] = {};
+    for (int pair = 0; pair < 32; ++pair)
+        for (int half = 0; half < 2; ++half) {
+            if (seen[pair_scan(pair, half)]) return false;
+            seen[pair_scan(pair, half)] = true;
+        }
+    return pair_scan(0, 0) == 0;
+}
+static_assert(pairs_cover_the_scan(), "kPairCol through kScanOfNatural");
+static_assert(kAmvlibQuirkNatural % 8 == kPairCol[0][1], "amvlib's entry is the high half of its row's first pair");
+
+// Dequantisation into pair registers: one multiply per coefficient as in the general form -- a sign-extended word of c[]
+// times a byte of qw[] -- whose product's low 16 bits go to one half of the pair.  The low half's multiply writes the
+// whole register, the high half's (dst_sel:WORD_1, UNUSED_PRESERVE) the upper half in place.  Written as the
+// instructions, volatile, so that they stand in the order they are called in: a row's four low halves, its four high
+// halves, then its dot products, first those of the pair whose high half was written first -- nothing reads a register
+// straight after half of it was written.  (Row by row, not the whole block's low halves before all its high ones: with
+// c[], qw[] and 32 pairs alive at once the kernel does not fit the 96 registers of five waves a SIMD.)
+template <int kScan>
+__device__ __forceinline__ void pair_lo(uint32_t& d, const uint32_t (&c)[32], const uint32_t (&qw)[16]) {
+    asm volatile("v_mul_i32_i24_sdwa %0, sext(%1), %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_%3 src1_sel:BYTE_%4"
+                 : "=v"(d) : "v"(c[kScan >> 1]), "v"(qw[kScan >> 2]), "n"(kScan & 1), "n"(kScan & 3));
+}
+template <int kScan>
+__device__ __forceinline__ void pair_hi(uint32_t& d, const uint32_t (&c)[32], const uint32_t (&qw)[16]) {
+    asm volatile("v_mul_i32_i24_sdwa %0, sext(%1), %2 dst_sel:WORD_1 dst_unused:UNUSED_PRESERVE src0_sel:WORD_%3 src1_sel:BYTE_%4"
+                 : "+v"(d) : "v"(c[kScan >> 1]), "v"(qw[kScan >> 2]), "n"(kScan & 1), "n"(kScan & 3));
+}
+// pair 0 has no low half to keep (the DC goes its own way): its high half's multiply zeroes the rest
+template <int kScan>
+__device__ __forceinline__ void pair_hi_alone(uint32_t& d, const uint32_t (&c)[32], const uint32_t (&qw)[16]) {
+    asm volatile("v_mul_i32_i24_sdwa %0, sext(%1), %2 dst_sel:WORD_1 dst_unused:UNUSED_PAD src0_sel:WORD_%3 src1_sel:BYTE_%4"
+                 : "=v"(d) : "v"(c[kScan >> 1]), "v"(qw[kScan >> 2]), "n"(kScan & 1), "n"(kScan & 3));
+}
+// the four pairs of row kRow (amvlib: its table reads scan position 37 at natural (3,4), one more half write in row 3)
+template <int kRow>
+__device__ __forceinline__ void dequant_row_pairs(uint32_t (&p)[4], const uint32_t (&c)[32], const uint32_t (&qw)[16], bool amvlib) {
+    constexpr int k = 4 * kRow;
+    if (kRow != 0) pair_lo<pair_scan(k, 0)>(p[0], c, qw);
+    pair_lo<pair_scan(k + 1, 0)>(p[1], c, qw);
+    pair_lo<pair_scan(k + 2, 0)>(p[2], c, qw);
+    pair_lo<pair_scan(k + 3, 0)>(p[3], c, qw);
+    if (kRow != 0) pair_hi<pair_scan(k, 1)>(p[0], c, qw);
+    else pair_hi_alone<pair_scan(k, 1)>(p[0], c, qw);
+    if (kRow == kAmvlibQuirkNatural / 8 && amvlib) pair_hi<kAmvlibQuirkScan>(p[0], c, qw);
+    pair_hi<pair_scan(k + 1, 1)>(p[1], c, qw);
+    pair_hi<pair_scan(k + 2, 1)>(p[2], c, qw);
+    pair_hi<pair_scan(k + 3, 1)>(p[3], c, qw);
+}
+
+// a.lo * w.lo + a.hi * w.hi (+ acc), 32-bit wrapping: the weights in a scalar register, the accumulator a vector one
+// (this family takes one scalar operand an instruction) or the inline constant 0
+__device__ __forceinline__ int dot2(uint32_t a, uint32_t w, int acc) {
+    int d;
+    asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(w), "v"(acc));
+    return d;
+}
+__device__ __forceinline__ int dot2(uint32_t a, uint32_t w) {
+    int d;
+    asm("v_dot2_i32_i16 %0, %1, %2, 0" : "=v"(d) : "v"(a), "s"(w));
+    return d;
+}
+// One row from its four pairs; what it leaves in v0..v7 is what idct8<false, kKind> leaves.  even: the accumulator of
+// the two even forms -- the bias, and in row 0 the DC's 2048 * dc + bias on top (its pair's low half is 0).
+template <RowKind kKind>
+__device__ __forceinline__ void idct8_row_pairs(uint32_t p04, uint32_t p17, uint32_t p53, uint32_t p26, int even,
+                                                int& v0, int& v1, int& v2, int& v3, int& v4, int& v5, int& v6, int& v7) {
+    constexpr int W1 = 2841, W2 = 2676, W3 = 2408, W5 = 1609, W6 = 1108, W7 = 565;
+    const int t = dot2(p04, pair16(2048, 2048), even);
+    const int a0 = dot2(p04, pair16(2048, -2048), even);
+    const int a4 = dot2(p17, pair16(W1, W7), kRowSeed);
+    const int a5 = dot2(p17, pair16(W7, -W1));
+    const int a6 = dot2(p53, pair16(W5, W3), -kRowSeed);
+    const int a7 = dot2(p53, pair16(W3, -W5));
+    const int a2 = dot2(p26, pair16(W6, -W2));
+    const int a3 = dot2(p26, pair16(W2, W6));
+    idct8_tail<false, kKind>(t, a0, a2, a3, a4, a5, a6, a7, v0, v1, v2, v3, v4, v5, v6, v7);
+}
+// row kRow of the block: dequantised into its pairs, transformed into v[8 kRow ..]
+template <int kRow>
+__device__ __forceinline__ void pair_row(const uint32_t (&c)[32], const uint32_t (&qw)[16], bool amvlib, int even, int (&v)[64]) {
+    uint32_t p[4];
+    dequant_row_pairs<kRow>(p, c, qw, amvlib);
+    int* const o = v + 8 * kRow;
+    idct8_row_pairs<kRow == 0 ? kRow0 : (kRow == 4 ? kRow4 : kRowPlain)>(p[0], p[1], p[2], p[3], even, o[0], o[1], o[2], o[3], o[4], o[5], o[6], o[7]);
+}
 
 // iclp[] of AmvJpeg.c:1073-1080 (table spans -512..511; beyond it the reference reads out of bounds, defined here as
 // saturation) of two column sums x >> 14, as two int16 in a dword.  The column pass hands over x >> 7, and for every
@@ -149,7 +263,6 @@ __device__ __forceinline__ uint32_t clamp_pack(int lo, int hi) {
 
 // a.lo * w.lo + a.hi * w.hi + 32768 (16-bit signed halves): the three-operand form, so that the bias stays in its
 // register (the builtin becomes the accumulating form plus a move to reload the accumulator)
-constexpr uint32_t pair16(int lo, int hi) { return ((uint32_t)lo & 0xffffu) | ((uint32_t)hi << 16); }
 __device__ __forceinline__ uint32_t dot2_bias(uint32_t a, uint32_t w) {
     uint32_t d;
     asm("v_dot2_i32_i16 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(w), "v"(32768u));
@@ -207,6 +320,29 @@ __device__ __forceinline__ Px12 patch_row(uint2 yy, const ChromaTerms& c) {
     return v;
 }
 
+// The column pass over a block whose rows are done, and stage C: GetYUV (AmvJpeg.c:754-787), one 16-byte row at a time.
+// The +128 of IQtIZzBlock (:1023,1047) joins the chroma terms in stage D (it cannot ride through the column pass on the
+// DC term: the reference's 32-bit arithmetic wraps on absurd coefficients, and the parity tests hold the kernel to that).
+// s_mem: the segment's planes -- 16 rows of Y, 8 of U, 8 of V; lane: the block in the segment.
+__device__ __forceinline__ void columns_to_plane(int (&v)[64], uint32_t lane, int16_t* s_mem) {
+    constexpr uint32_t kPitchY = kSegMcus * 16, kPitchC = kSegMcus * 8;   // int16 units
+#pragma unroll
+    for (int col = 0; col < 8; ++col)
+        idct8<true>(v[col], v[8 + col], v[16 + col], v[24 + col], v[32 + col], v[40 + col], v[48 + col], v[56 + col]);
+    const uint32_t m = lane / 6u, k6 = lane % 6u;
+    const bool chroma = k6 >= 4u;
+    int16_t* dst = chroma ? s_mem + 16 * kPitchY + (k6 == 4u ? 0u : 8 * kPitchC) + m * 8u
+                          : s_mem + ((k6 >> 1) * 8u) * kPitchY + m * 16u + (k6 & 1u) * 8u;
+    const uint32_t pitch = chroma ? kPitchC : kPitchY;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        uint32_t w[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) w[q] = clamp_pack(v[8 * r + 2 * q], v[8 * r + 2 * q + 1]);
+        *reinterpret_cast<uint4*>(dst + r * pitch) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+}
+
 }  // namespace
 
 // kRound: a round launch (FrameSel::round != 0), whose workgroups walk the items of the round
@@ -246,42 +382,47 @@ __global__ __launch_bounds__(kWave * kRows) void amv_reconstruct_kernel(
     const uint32_t m0 = sg.m0, cnt = sg.cnt, ok = sg.ok, mcu0 = sg.mcu0;
 
     // ---- A + B + C: one block per lane
-    uint32_t c[32];
+    BlockForm form;
     bool skip;
-    if (load_segment_blocks(in, sg, kRound, g, lane, s_img, c, skip)) {
-        const uint32_t m = lane / 6u, k6 = lane % 6u;
-        const bool chroma = k6 >= 4u;
-        // IQtIZzBlock's gather (AmvJpeg.c:1035-1042): out[nat] = coef[scan(nat)] * step[scan(nat)]
+    if (stage_segment_blocks(in, sg, kRound, g, lane, s_img, form, skip)) {
+        uint32_t c[32];
         int v[64];
-#pragma unroll
-        for (int nat = 0; nat < 64; ++nat) {
-            const int scan = kScanOfNatural[nat];
-            v[nat] = coef_at(c, scan) * (int)((qw[scan >> 2] >> (8 * (scan & 3))) & 255u);
-        }
-        if (!(flags & kFlagZigzagFixed))     // amvlib's table reads scan position 37 at natural (3,4)
-            v[kAmvlibQuirkNatural] = coef_at(c, kAmvlibQuirkScan) * (int)((qw[kAmvlibQuirkScan >> 2] >> (8 * (kAmvlibQuirkScan & 3))) & 255u);
+        // Stage B's row pass in two forms; each fetches its block itself (fetched in front of the branch, the 32 registers
+        // that come from LDS or from dense lines have two readers, the compiler keeps both sets, and the kernel no longer
+        // fits the 96 registers of five waves a SIMD).
+        if (form.small_ac) {   // (wave-uniform) no AC of the frame has ten magnitude bits: the row pass on paired halves
+            fetch_block(in, sg, g, lane, s_img, BlockForm{true, true, form.dc_base}, c);
+            const bool amvlib = !(flags & kFlagZigzagFixed);
+            const int dc = coef_at(c, 0) * (int)(qw[0] & 255u);
+            pair_row<0>(c, qw, amvlib, dc * 2048 + (128 + 8192), v);
+            pair_row<1>(c, qw, amvlib, 128, v);
+            pair_row<2>(c, qw, amvlib, 128, v);
+            pair_row<3>(c, qw, amvlib, 128, v);
+            pair_row<4>(c, qw, amvlib, 128, v);
+            pair_row<5>(c, qw, amvlib, 128, v);
+            pair_row<6>(c, qw, amvlib, 128, v);
+            pair_row<7>(c, qw, amvlib, 128, v);
+        } else {   // the general form: marked frames, dense lines
+        fetch_block(in, sg, g, lane, s_img, form, c);
+        // IQtIZzBlock's gather (AmvJpeg.c:1035-1042): out[nat] = coef[scan(nat)] * step[scan(nat)], a row at a time in
+        // front of the row's transform and held there (sched_barrier): all 64 products ahead of the rows, as the compiler
+        // places them when left alone, need seven registers more than the kernel has beside the other form
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
+#pragma unroll
+            for (int nat = 8 * r; nat < 8 * r + 8; ++nat) {
+                const int scan = kScanOfNatural[nat];
+                v[nat] = coef_at(c, scan) * (int)((qw[scan >> 2] >> (8 * (scan & 3))) & 255u);
+            }
+            if (r == kAmvlibQuirkNatural / 8 && !(flags & kFlagZigzagFixed))     // amvlib's table reads scan position 37 at natural (3,4)
+                v[kAmvlibQuirkNatural] = coef_at(c, kAmvlibQuirkScan) * (int)((qw[kAmvlibQuirkScan >> 2] >> (8 * (kAmvlibQuirkScan & 3))) & 255u);
             if (r == 0) idct8<false, kRow0>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
             else if (r == 4) idct8<false, kRow4>(v[32], v[33], v[34], v[35], v[36], v[37], v[38], v[39]);
             else idct8<false>(v[8 * r], v[8 * r + 1], v[8 * r + 2], v[8 * r + 3], v[8 * r + 4], v[8 * r + 5], v[8 * r + 6], v[8 * r + 7]);
+            __builtin_amdgcn_sched_barrier(0);
         }
-#pragma unroll
-        for (int col = 0; col < 8; ++col)
-            idct8<true>(v[col], v[8 + col], v[16 + col], v[24 + col], v[32 + col], v[40 + col], v[48 + col], v[56 + col]);
-        // GetYUV (AmvJpeg.c:754-787): one 16-byte row at a time.  The +128 of IQtIZzBlock (:1023,1047) joins the
-        // chroma terms in stage D (it cannot ride through the column pass on the DC term: the reference's 32-bit
-        // arithmetic wraps on absurd coefficients, and the parity tests hold the kernel to that).
-        int16_t* dst = chroma ? (k6 == 4u ? s_u : s_v) + m * 8u
-                              : s_y + ((k6 >> 1) * 8u) * kPitchY + m * 16u + (k6 & 1u) * 8u;
-        const uint32_t pitch = chroma ? kPitchC : kPitchY;
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            uint32_t w[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) w[q] = clamp_pack(v[8 * r + 2 * q], v[8 * r + 2 * q + 1]);
-            *reinterpret_cast<uint4*>(dst + r * pitch) = make_uint4(w[0], w[1], w[2], w[3]);
         }
+        columns_to_plane(v, lane, s_mem);
     }
     if (skip) return;   // (wave-uniform) not this launch's frame
     seg_sync();

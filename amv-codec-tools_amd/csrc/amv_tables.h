@@ -109,10 +109,15 @@ static constexpr int kLut2Pages = 16;
 // coefficient index moves (run + 1; 1 for a DC symbol; 192 for end-of-block: bit 6 of index + 192 is set for every
 // index 1..63 and the sum stays clear of 65..79, an over-long run; 0 for "no such code"), byte 3 code length +
 // magnitude bits (1 for "no such code": a walk from a guessed start slips one bit there, the strict walk stops).
+// Bit 9 (kFastBigAc), AC tables only, set in the image the device gets (mark_big_ac, amv_host_plan.h, behind
+// build_images): ten magnitude bits or more -- |value| >= 512, which no encoder-made stream carries.  No field of the
+// walk reads it; it rides in the OR of the entries a walk keeps anyway and marks the frame (kRecCountBigAc,
+// amv_kernels.h) for the reconstruction, whose 16-bit row pass is exact only without such a value.
 static constexpr uint32_t kFastWords = 2048;          // per table: 8 KB, a power of two (the table is chosen by OR-ing address bits)
 static constexpr uint32_t kFastM2Word = 512;          // the long-code half of a table starts here
 static constexpr uint32_t kFastLongFirst = 0xfc00u;   // 16-bit windows from here on begin with six one-bits
 static constexpr uint32_t kFastInvalid = 1u << 5, kFastEmit = 1u << 8, kFastEobAdvance = 192u;
+static constexpr uint32_t kFastBigAc = 1u << 9;
 struct HuffDecodeImage {
     uint16_t l1[4][1 << kLut1Bits];
     uint16_t l2[kLut2Pages][1 << kLut2Bits];

@@ -119,7 +119,7 @@ extern "C" int amvhip_create(amvhip_ctx** out, int device) {
     static HuffDecodeImage dec;
     static HuffEncodeImage enc;
     static std::once_flag once;
-    std::call_once(once, [] { build_images(dec, enc); });
+    std::call_once(once, [] { build_images(dec, enc); mark_big_ac(dec); });
     auto die = [&](int code) { amvhip_destroy(c); return code; };
     if (hipSetDevice(device) != hipSuccess) return die(AMVHIP_ERR_DEVICE);
     int cus = 0;
@@ -211,15 +211,15 @@ extern "C" int amvhip_set_entropy_mode(amvhip_ctx* c, int mode) {
     return AMVHIP_OK;
 }
 
-extern "C" int amvhip_entropy_stats(amvhip_ctx* c, int enable, uint64_t out[10]) {
+extern "C" int amvhip_entropy_stats(amvhip_ctx* c, int enable, uint64_t out[11]) {
     if (!c) return AMVHIP_ERR_ARG;
     if (int r = use_device(c)) return r;
     std::lock_guard<std::mutex> lk(c->mu);
     if (int r = ensure(c, c->stats, amv::kStatsBytes)) return r;
     HIP_TRY(c, hipDeviceSynchronize());
     if (out) {
-        if (c->want_stats) HIP_TRY(c, hipMemcpy(out, c->stats.p, 80, hipMemcpyDeviceToHost));
-        else memset(out, 0, 80);
+        if (c->want_stats) HIP_TRY(c, hipMemcpy(out, c->stats.p, 88, hipMemcpyDeviceToHost));
+        else memset(out, 0, 88);
         // frames of the LAST decode call that the synchronising kernel handed to the one-lane-per-frame kernel (chunk
         // over the workspace window, long FF run, more records than the record space holds: see blob_bytes in amvhip.h)
         uint32_t handed = 0;

@@ -291,9 +291,10 @@ int amvhip_set_entropy_mode(amvhip_ctx *ctx, int mode);
  * gathered since the last call in out[] = {frames, sum of synchronisation rounds, max rounds, frames the LAST decode
  * call handed to the one-lane-per-frame kernel (always reported, whether gathering is on or not),
  * then shader clocks summed over waves for: coefficient zeroing, first walk, synchronisation
- * rounds, writing pass, DC pass, and the number of waves}, clears them and switches gathering on
- * or off (off by default; costs a few atomics per frame). */
-int amvhip_entropy_stats(amvhip_ctx *ctx, int enable, uint64_t out[10]);
+ * rounds, writing pass, DC pass, the number of waves, and the frames that left the entropy stage marked as carrying an
+ * AC coefficient of ten magnitude bits or more (the reconstruction takes its general row pass for those)}, clears them
+ * and switches gathering on or off (off by default; costs a few atomics per frame). */
+int amvhip_entropy_stats(amvhip_ctx *ctx, int enable, uint64_t out[11]);
 /* ... and, per task (wave) of the last launch of the several-lanes-per-frame kernel while gathering was on, a line of
  * eight words: {constant-rate clock (100 MHz) at the task's begin, at its end, shader clocks of the first walk, the
  * synchronisation rounds, the strict pass, the DC pass, rounds of the wave's worst frame | share length in bits << 32,
